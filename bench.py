@@ -9,14 +9,17 @@ a seeded velocity field (sigma = 0.2 cells / iteration, `--flow`) is added on th
 the lane's own cell; the figure for the still start state is reported next to it (`at_rest`).
 For N > 1 the same grid is cut into N column slabs (strong scaling) with a ring halo exchange over RCCL, overlapped with compute
 on a side stream; `--workload dry --X 32768 --Y 4096` runs BASELINE's north-star stencil the same way. Typed without a launcher
-(`python bench.py --gpus 8`: no WORLD_SIZE in the environment) the script re-executes itself under `torch.distributed.run`, one rank
-per GPU. An N-rank grid run is self-validating by default (`--no-verify` switches it off): every rank checksums its owned columns and
+(`python bench.py --gpus 8`: no WORLD_SIZE in the environment) the script starts itself again as a child under `torch.distributed.run`,
+one rank per GPU. An N-rank grid run is self-validating by default (`--no-verify` switches it off): every rank checksums its owned columns and
 rank 0 compares them with an undecomposed run of the same state (`"verify": "ok"`, `ranks_seen`, `transport` in the line).
 Prints one JSON line on rank 0 (contract in the task description): throughput with inputs resident in HBM, plus `roofline`
 (dominant kernel, HIP-event timed on the engine's stream), `cpu_baseline` (the CPU oracle timed on this box's host cores, N = 1 only),
 `hbm_ceiling` (tools/ubench_hbm: read / write / copy streams with the kernels' own access pattern) and `north_star_dry` (N = 1 only):
 BASELINE.json's north-star stencil -- the fused pressure + velocity + advection kernel on a 32768 x 4096 dry grid -- measured in
 the same process with its own roofline, at rest and on the moving fluid.
+`--dump-outputs DIR` (N = 1) writes what the last timed iteration left in the handle -- the fields a caller of wx_step reads back -- as
+DIR/<field>.npy (see dump_outputs()). Everything that runs on the timed handle before that point is a fixed number of iterations of a
+seeded start state, so two runs with the same arguments (of this build or of another one) write the same arrays.
 """
 import argparse
 import datetime
@@ -81,8 +84,12 @@ def parse():
     ap.add_argument("--verify", dest="verify", action="store_true", default=True,
                     help="N > 1, grid only (default ON): checksum every rank's owned columns against an undecomposed run of the same state on rank 0")
     ap.add_argument("--no-verify", dest="verify", action="store_false", help="N > 1: skip the self-validation of the decomposed run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps write the fields the last timed iteration produced as DIR/<field>.npy (float32; at most 64 MB: a seeded sample of the cells of a larger grid)")
     a = ap.parse_args()
     a.frame = max(1, a.frame)  # (0 or a negative value would never advance run_frames)
+    if a.dump_outputs and a.gpus != 1:
+        ap.error("--dump-outputs writes the undecomposed handle's fields: --gpus 1 only")
     return a
 
 
@@ -90,15 +97,17 @@ def reference_cpu_path():
     """the reference itself (its shaders under HeadlessChrome + SwiftShader, the `kaleido` pip package, driven by
     oracle/golden/harness.js) is the preferred CPU baseline IF it can run on this box. It needs three things, none of which is part of
     this repository's snapshot: the kaleido package, the reference checkout (its shader files are loaded at run time and may not
-    travel) and the harness next to it. Probe and say what is there; the timing itself is `oracle/golden/gen_golden.py save100raw`
-    (2.0-2.2 Mcell-steps/s at 100 x 100 on 8 vCPU in the build container)."""
+    travel; WX_REFERENCE names it, as for oracle/golden/gen_host_golden.py) and the harness next to it. Probe and say what is there;
+    the timing itself is `oracle/golden/gen_golden.py save100raw` (2.0-2.2 Mcell-steps/s at 100 x 100 on 8 vCPU in the build container,
+    BASELINE.md)."""
     import importlib.util
     have_kaleido = importlib.util.find_spec("kaleido") is not None
-    have_ref = os.path.isdir("/root/reference/shaders")
+    ref = os.environ.get("WX_REFERENCE")
+    have_ref = bool(ref) and os.path.isdir(os.path.join(ref, "shaders"))
     have_harness = os.path.exists(os.path.join(ROOT, "oracle", "golden", "harness.js"))
     if have_kaleido and have_ref and have_harness:
-        return "present (kaleido + /root/reference + harness): time it with oracle/golden/gen_golden.py; not run inside the bench"
-    missing = [n for n, ok in (("kaleido package", have_kaleido), ("/root/reference checkout", have_ref), ("oracle/golden/harness.js", have_harness)) if not ok]
+        return "present (kaleido + the reference checkout + harness): time it with oracle/golden/gen_golden.py; not run inside the bench"
+    missing = [n for n, ok in (("kaleido package", have_kaleido), ("the reference checkout (WX_REFERENCE)", have_ref), ("oracle/golden/harness.js", have_harness)) if not ok]
     return "absent on this box (missing: " + ", ".join(missing) + ")"
 
 
@@ -225,18 +234,35 @@ def run_frames(step, n, frame):
 
 
 CONDITION_S = 0.25  # see condition_clocks()
+# conditioning_iterations(): the rates its fixed counts are sized with -- above what the kernels reach (wet 49 000, dry pairs 200 000
+# Mcell-steps/s), so that the count lasts CONDITION_S and more -- and the shortest iteration of a launch-bound grid
+CONDITION_MCELLS_PER_S = {"wet": 60e3, "dry": 250e3}
+CONDITION_MIN_ITERATION_S = 25e-6
 
 
-def condition_clocks(step, sync, frame, seconds=CONDITION_S, agree=None):
+def conditioning_iterations(cells, frame, workload):
+    """The conditioning of the single-GPU handle whose state --dump-outputs writes, as a NUMBER of iterations (whole frames): a function
+    of the arguments alone -- a count found by the clock differs from run to run and from build to build, and with it the state the timed
+    region starts from and ends in. Sized to last CONDITION_S at a rate no kernel reaches; what it did last is in the line."""
+    n = CONDITION_S / max(cells / (CONDITION_MCELLS_PER_S[workload] * 1e6), CONDITION_MIN_ITERATION_S)
+    return -(-int(n) // frame) * frame
+
+
+def condition_clocks(step, sync, frame, seconds=CONDITION_S, agree=None, iters=None):
     """Untimed iterations for at least `seconds` of wall time, issued right before a timed region, whatever --warmup says.
 
     The chip needs ~30-40 ms of continuous load to reach its sustained clocks after ANY idle phase (allocation, the placement search's
     frees, a host-side pause): from idle the first frames of 10 iterations run at 0.92 / 0.83 / 0.77 / 0.745 ms per iteration before the
     kernel settles at 0.737 (profiles/r04_driver_gap.txt). A region of `--warmup 5 --steps 20` (4 + 16 ms) would sit entirely on that
     ramp and report the power management, not the kernel. Returns the number of iterations run. `agree` (N ranks): a callable that
-    turns this rank's "keep going" into the job's (an all-reduce), so that every rank runs the same number of iterations."""
-    n = 0
+    turns this rank's "keep going" into the job's (an all-reduce), so that every rank runs the same number of iterations. `iters`
+    (conditioning_iterations()): exactly that many instead, for a handle whose state must not depend on the clock."""
     sync()
+    if iters is not None:
+        run_frames(step, iters, frame)
+        sync()
+        return iters
+    n = 0
     t0 = time.perf_counter()
     more = True
     while more:
@@ -423,7 +449,7 @@ def other_configs(a, pkg):
                                                  "under SwiftShader on 8 vCPU: 2.0-2.2 Mcell-steps/s (BASELINE.md)")
     h.close()
     # the reference's OWN grid sizes: a new simulation is 2500 x 300 by default and the resolution sliders end at 16000 x 500
-    # (/root/reference/index.html:325, 335); its frame is IterPerFrame = 10 iterations (app.js:398). Full wet iteration, setup-pass terrain.
+    # (the reference's index.html:325, 335); its frame is IterPerFrame = 10 iterations (app.js:398). Full wet iteration, setup-pass terrain.
     gui = pkg.params.merge_settings(None)
     gui["sunAngle"] = 50.0
     for X, Y, name in ((2500, 300, "ref_default_2500x300"), (16000, 500, "ref_largest_16000x500")):
@@ -466,6 +492,52 @@ def other_configs(a, pkg):
     return out
 
 
+# What a caller of wx_step reads back (include/wxsim.h): the state carried into the next iteration, then what the step's last iteration
+# leaves for the display side. The dry stencil touches the base and wall textures only.
+DUMP_FIELDS = {"wet": ("BASE_CUR", "WATER_CUR", "WALL_CUR", "LIGHT_0", "LIGHT_1", "BASE_DISP", "WATER_0", "WALL_DISP", "CURL", "EMITTED"),
+               "dry": ("BASE_CUR", "BASE_DISP", "WALL_CUR")}
+DUMP_PARTICLE_FIELDS = ("PRECIP_FB", "PRECIP_DEP")
+DUMP_SAMPLE_BYTES = 32 << 20  # the cell sample of all fields together; the row / column sums of a 16384 x 2048 grid add 6 MB
+
+
+def dump_outputs(h, a):
+    """--dump-outputs DIR: the fields of DUMP_FIELDS as the last timed iteration left them, every one read back whole (wx_read_rect)
+    and written as float32 DIR/<FIELD>.npy [Y, X, channels] if all of them fit in DUMP_SAMPLE_BYTES -- otherwise as [K, channels], the
+    values at K cells drawn once without replacement by numpy's default_rng(0) from the Y * X cells (ascending y * X + x; the same cells
+    for every field), next to float64 sums over all rows (DIR/<FIELD>_colsum.npy [X, channels]) and over all columns
+    (DIR/<FIELD>_rowsum.npy [Y, channels]), which see every cell of the grid. With particles: DIR/DROPS.npy [n, 5], whole. Returns the
+    entry of the JSON line."""
+    import numpy as np
+    from weather_sandbox_amd.engine import FIELD_CHANNELS
+    fields = DUMP_FIELDS[a.workload] + (DUMP_PARTICLE_FIELDS if a.particles else ())
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    X, Y = h.X, h.Y
+    per_cell = 4 * sum(FIELD_CHANNELS.get(f, 4) for f in fields)
+    K = DUMP_SAMPLE_BYTES // per_cell
+    cells = None if K >= X * Y else np.sort(np.random.default_rng(0).choice(X * Y, K, replace=False))
+    written = 0
+
+    def save(name, arr):
+        nonlocal written
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        written += arr.nbytes
+
+    for f in fields:
+        v = h.read_rect(f).astype(np.float32, copy=False)
+        if cells is None:
+            save(f, v)
+        else:
+            save(f, v.reshape(X * Y, -1)[cells])
+            save(f + "_colsum", v.sum(axis=0, dtype=np.float64))
+            save(f + "_rowsum", v.sum(axis=1, dtype=np.float64))
+        del v
+    if a.particles:
+        save("DROPS", h.read_particles())
+    assert written <= 64 << 20, written
+    return {"dir": a.dump_outputs, "iteration": h.iter, "fields": list(fields) + (["DROPS"] if a.particles else []), "bytes": written,
+            "cells": "all" if cells is None else f"{K} of {X * Y}: numpy default_rng(0).choice without replacement, ascending; sums over all rows / columns in <FIELD>_colsum / _rowsum"}
+
+
 def p2p_selftest(dist, torch, rank, world, device):
     """First contact with the transport: every rank sends its rank number to both ring neighbours and checks what arrives, with a
     bounded wait -- so that a broken RCCL path fails here, readably, instead of hanging in the timed region."""
@@ -488,14 +560,16 @@ def p2p_selftest(dist, torch, rank, world, device):
 
 
 def self_launch(a):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment): re-execute this script under
-    `torch.distributed.run`, one rank per GPU, rendezvous on 127.0.0.1 (the container's hostname may not resolve) -- the command the
-    driver types for N > 1, typed for it. Returns only if there is nothing to launch."""
+    """`python bench.py --gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment): run this script as a child
+    under `torch.distributed.run`, one rank per GPU, rendezvous on 127.0.0.1 (the container's hostname may not resolve) -- the command
+    the driver types for N > 1, typed for it -- and exit with its code. This process never opens the GPU itself (the devices are counted
+    by a short-lived child): only the ranks hold it. Returns only if there is nothing to launch."""
     if a.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     import socket
-    import torch
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    count = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                           stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
+    have = int(count.stdout.decode().split()[-1]) if count.returncode == 0 and count.stdout.strip() else 0
     if have < a.gpus and not os.environ.get("WX_BENCH_SHARE_GPU"):
         print(json.dumps({"error": f"--gpus {a.gpus} asked, {have} HIP device(s) visible on this box", "n_gpus": a.gpus, "devices_visible": have}), flush=True)
         sys.exit(2)
@@ -508,7 +582,7 @@ def self_launch(a):
            "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -602,9 +676,11 @@ def main():
             placement = {"tries": "implicit: 6, inside the handle's first wx_step (WX_OPT_PLACEMENT_SEARCH; what a host that never calls wx_tune_placement gets)",
                          "ms_per_iteration_first_allocation": pi[0], "ms_per_iteration_kept": pi[1]}
     at_rest = None
+    # one GPU: a fixed count (the state after the timed region is a function of the arguments: --dump-outputs); N ranks: by the clock, agreed
+    cond_iters = conditioning_iterations(X * Y, a.frame, a.workload) if world == 1 else None
     if world == 1 and a.flow > 0 and not a.no_extras and not a.particles:  # the still start state first (round 2's definition)
         run_frames(step, a.warmup, a.frame)
-        condition_clocks(step, sync, a.frame)
+        condition_clocks(step, sync, a.frame, iters=cond_iters)
         dt0, _ = timed_run(stepper, a.steps, a.frame, profile=False)
         at_rest = {"value": X * Y * a.steps / dt0 / 1e6, "ms_per_step": dt0 / a.steps * 1e3, "flow": devtools.flow_stats(stepper),
                    "state": "still start state (what round 2 timed)", "placement": "the kept one (same as value)"}
@@ -613,15 +689,17 @@ def main():
     flow0 = devtools.flow_stats(stepper)
 
     run_frames(step, a.warmup, a.frame)
-    # the --warmup iterations above are the contract's; the clocks are conditioned by TIME on top of them (condition_clocks), so that a
-    # short region (the driver's --warmup 5 --steps 20 is 20 ms in all) measures the kernel at its sustained clocks
+    # the --warmup iterations above are the contract's; the clocks are conditioned for CONDITION_S on top of them (condition_clocks), so
+    # that a short region (the driver's --warmup 5 --steps 20 is 20 ms in all) measures the kernel at its sustained clocks
     agree = None
     if world > 1:
         def agree(more):
             t = torch.tensor([1 if more else 0], dtype=torch.int32, device=device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             return bool(t.item())
-    conditioning_iters = condition_clocks(step, sync, a.frame, agree=agree)
+    t0 = time.perf_counter()
+    conditioning_iters = condition_clocks(step, sync, a.frame, agree=agree, iters=cond_iters)
+    conditioning_s = time.perf_counter() - t0
     sync()
     barrier()
     # per-kernel HIP events (4 event records per iteration) are cheap next to a 1 ms iteration on one GPU; on N GPUs an
@@ -630,11 +708,13 @@ def main():
     if profile_inline:
         stepper.profile(True)
     sync()
+    iter0 = stepper.iter
     t0 = time.perf_counter()
     run_frames(step, a.steps, a.frame)
     sync()
     barrier()
     dt = time.perf_counter() - t0
+    assert stepper.iter - iter0 == a.steps, f"the timed region ran {stepper.iter - iter0} iterations, --steps {a.steps}"
     extra_iters = 0
     if not profile_inline:
         stepper.profile(True)
@@ -645,6 +725,7 @@ def main():
     stepper.profile(False)
     prof_steps = a.steps if profile_inline else 16
     flow1 = devtools.flow_stats(stepper)
+    dumped = dump_outputs(stepper, a) if a.dump_outputs else None
     verify = "n/a (single rank)" if world == 1 else "off (--no-verify)"
     whole, n1, per_rank = None, None, None
     # largest |velocity component| the exact path of the wet kernel saw during the run (0: nothing reached 0.9 cells / iteration). On
@@ -768,7 +849,8 @@ def main():
         out = {
             "metric": "Mcell-steps/s", "value": value, "unit": "Mcell-steps/s", "n_gpus": world, "steps": a.steps,
             "arith": "fast (tolerance build, NOT the parity build)" if pkg.engine.lib().wx_arith() == 1 else "exact",
-            "warmup": a.warmup, "clock_conditioning": {"untimed_iterations_after_warmup": conditioning_iters, "min_seconds": CONDITION_S,
+            "warmup": a.warmup, "clock_conditioning": {"untimed_iterations_after_warmup": conditioning_iters, "min_seconds": CONDITION_S, "seconds": conditioning_s,
+                                                       "count": "fixed by the arguments (conditioning_iterations)" if cond_iters else "by the clock, agreed between the ranks",
                                                        "why": "sustained clocks need ~40 ms of load after any idle phase (profiles/r04_driver_gap.txt)"},
             "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -785,6 +867,8 @@ def main():
             out["per_rank"] = per_rank
         if at_rest:
             out["at_rest"] = at_rest
+        if dumped:
+            out["dump_outputs"] = dumped
         if world == 1 and not a.no_extras and a.frame != 1 and not a.particles:
             condition_clocks(lambda k: run_frames(stepper.step, k, 1), sync, a.frame)
             dt1, _ = timed_run(stepper, a.steps, 1, profile=False)  # round 1's definition: the display fields after EVERY iteration

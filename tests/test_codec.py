@@ -1,5 +1,6 @@
 """.weathersandbox codec + settings merge + derived parameters (SURVEY.md Appendix B numbers)."""
 import json
+import os
 
 import numpy as np
 import pytest
@@ -36,15 +37,15 @@ def test_js_number_formatting(pkg):
     assert pkg.codec.js_json({"a": [1.0, 0.00001, "x"], "b": None, "c": {"d": False, "e": 1e-7}}) == '{"a":[1,0.00001,"x"],"b":null,"c":{"d":false,"e":1e-7}}'
 
 
-REF_SAVE = "/root/reference/saves/100 X 100 Test.weathersandbox"
+REF_SAVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "save100.weathersandbox")  # the reference's "100 X 100 Test" save, unchanged
 
 
-@pytest.mark.skipif(not __import__("os").path.exists(REF_SAVE), reason="the reference tree is only present in the build container")
 def test_reencoding_the_reference_save_is_byte_identical(pkg):
     """decode -> encode of the reference's own save: the deflated PAYLOAD (dimensions, three textures, droplets, stations and the
     guiControls JSON written by JSON.stringify, app.js:6610-6621) comes out byte for byte; only the deflate stream differs."""
     import zlib
-    blob = open(REF_SAVE, "rb").read()
+    with open(REF_SAVE, "rb") as f:
+        blob = f.read()
     sf = pkg.codec.decode(blob)
     again = pkg.codec.encode(sf)
     assert again[:4] == blob[:4]
