@@ -1,4 +1,5 @@
-// wx_comm.h -- the halo exchange INSIDE the library (included at the end of wxsim.hip, inside its extern "C" block).
+// wx_comm.h -- the halo exchange INSIDE the library (included at the end of wxsim.hip, behind its extern "C" block: the entry points
+// defined here are declared extern "C" by include/wxsim.h).
 //
 // BASELINE north_star: "x-slab decomposition ... one-cell halo exchange on RCCL send/recv over xGMI overlapped on a side HIP
 // stream; host code stays in JavaScript". Rounds 1-3 packed and unpacked halos in the library but left the transport to the Python
@@ -85,7 +86,7 @@ static size_t pool_stride(const wx_sim *s)
   // (exact mode sends a round after EVERY iteration: until the first counts are in, 262 144 events per rank and round -- eight times
   // the start-up burst of configs[4] -- instead of the whole buffer; the per-period protocol's first exchange carries a whole period's
   // burst and takes everything)
-  const long long ev = (s->pool_exact && s->pool_stride_events > (1 << 18)) ? (1 << 18) : s->pool_stride_events;
+  const long long ev = (s->opt.pool_exact && s->pool.stride_events > (1 << 18)) ? (1 << 18) : s->pool.stride_events;
   const size_t want = (POOL_HDR + sizeof(PoolEvent) * (size_t)(1 + ev) + 4095) / 4096 * 4096;
   return std::min(want, wx_pool_event_bytes(s));
 }
@@ -95,62 +96,62 @@ static int transport_prepare(wx_sim *s, int world)
 {
   if (s->halo == 0) return fail(s, WX_E_STATE, "the handle has no ghost columns (wx_create_slab with halo > 0)");
   const size_t bytes = wx_halo_bytes(s);
-  if (s->xbytes != bytes) {
+  if (s->tx.xbytes != bytes) {
     for (int i = 0; i < 2; i++) {
-      hipFree(s->xsend[i]);
-      hipFree(s->xrecv[i]);
-      s->xsend[i] = s->xrecv[i] = nullptr;
-      if (hipMalloc((void **)&s->xsend[i], bytes) != hipSuccess || hipMalloc((void **)&s->xrecv[i], bytes) != hipSuccess)
+      hipFree(s->tx.xsend[i]);
+      hipFree(s->tx.xrecv[i]);
+      s->tx.xsend[i] = s->tx.xrecv[i] = nullptr;
+      if (hipMalloc((void **)&s->tx.xsend[i], bytes) != hipSuccess || hipMalloc((void **)&s->tx.xrecv[i], bytes) != hipSuccess)
         return fail(s, WX_E_NOMEM, "halo buffers: 4 x %zu bytes", bytes);
     }
-    s->xbytes = bytes;
+    s->tx.xbytes = bytes;
   }
-  if (s->pool_remote && (!s->ev_mine || s->ev_world != world)) {
-    hipFree(s->ev_mine);
-    hipFree(s->ev_all);
-    s->ev_mine = s->ev_all = nullptr;
+  if (s->pool.remote && (!s->pool.ev_mine || s->pool.ev_world != world)) {
+    hipFree(s->pool.ev_mine);
+    hipFree(s->pool.ev_all);
+    s->pool.ev_mine = s->pool.ev_all = nullptr;
     const size_t eb = wx_pool_event_bytes(s), gb = wx_pool_edge_bytes(s);
-    if (hipMalloc((void **)&s->ev_mine, eb) != hipSuccess || hipMalloc((void **)&s->ev_all, eb * (size_t)world) != hipSuccess)
+    if (hipMalloc((void **)&s->pool.ev_mine, eb) != hipSuccess || hipMalloc((void **)&s->pool.ev_all, eb * (size_t)world) != hipSuccess)
       return fail(s, WX_E_NOMEM, "droplet-pool event buffers: %zu bytes", eb * (size_t)(world + 1));
-    if (!s->ev_seen_host) {
-      HIPCHK(s, hipHostMalloc((void **)&s->ev_seen_host, sizeof(int), hipHostMallocDefault));
-      *s->ev_seen_host = 0;
-      HIPCHK(s, hipEventCreateWithFlags(&s->ev_counted, hipEventDisableTiming));
+    if (!s->pool.ev_seen_host) {
+      HIPCHK(s, hipHostMalloc((void **)&s->pool.ev_seen_host, sizeof(int), hipHostMallocDefault));
+      *s->pool.ev_seen_host = 0;
+      HIPCHK(s, hipEventCreateWithFlags(&s->pool.ev_counted, hipEventDisableTiming));
     }
-    s->pool_stride_events = 1 << 30; // a new ring: everything until the first counts are in
-    s->count_pending = false;
+    s->pool.stride_events = 1 << 30; // a new ring: everything until the first counts are in
+    s->pool.count_pending = false;
     for (int i = 0; i < 2; i++) {
-      hipFree(s->psend[i]);
-      hipFree(s->precv[i]);
-      if (hipMalloc((void **)&s->psend[i], gb) != hipSuccess || hipMalloc((void **)&s->precv[i], gb) != hipSuccess) return fail(s, WX_E_NOMEM, "droplet-pool edge buffers");
+      hipFree(s->pool.psend[i]);
+      hipFree(s->pool.precv[i]);
+      if (hipMalloc((void **)&s->pool.psend[i], gb) != hipSuccess || hipMalloc((void **)&s->pool.precv[i], gb) != hipSuccess) return fail(s, WX_E_NOMEM, "droplet-pool edge buffers");
     }
-    s->ev_world = world;
+    s->pool.ev_world = world;
   }
-  if (!s->vx_dev || s->vx_world != world) { // the slabs' measured |vx| maxima: one word each, all-gathered / copied with every exchange
-    hipFree(s->vx_dev);
-    if (s->vx_host) hipHostFree(s->vx_host);
-    s->vx_dev = nullptr;
-    s->vx_host = nullptr;
-    if (hipMalloc((void **)&s->vx_dev, sizeof(int) * (size_t)(1 + world)) != hipSuccess || hipHostMalloc((void **)&s->vx_host, sizeof(int) * 2 * (size_t)world, hipHostMallocDefault) != hipSuccess)
+  if (!s->vx.dev || s->vx.world != world) { // the slabs' measured |vx| maxima: one word each, all-gathered / copied with every exchange
+    hipFree(s->vx.dev);
+    if (s->vx.host) hipHostFree(s->vx.host);
+    s->vx.dev = nullptr;
+    s->vx.host = nullptr;
+    if (hipMalloc((void **)&s->vx.dev, sizeof(int) * (size_t)(1 + world)) != hipSuccess || hipHostMalloc((void **)&s->vx.host, sizeof(int) * 2 * (size_t)world, hipHostMallocDefault) != hipSuccess)
       return fail(s, WX_E_NOMEM, "the |vx| words of the exchange");
-    memset(s->vx_host, 0, sizeof(int) * 2 * (size_t)world);
+    memset(s->vx.host, 0, sizeof(int) * 2 * (size_t)world);
     for (int i = 0; i < 2; i++)
-      if (!s->ev_vx[i]) HIPCHK(s, hipEventCreateWithFlags(&s->ev_vx[i], hipEventDisableTiming));
-    s->vx_have[0] = s->vx_have[1] = false;
-    s->vx_slot = 0;
-    s->vx_world = world;
+      if (!s->vx.ev[i]) HIPCHK(s, hipEventCreateWithFlags(&s->vx.ev[i], hipEventDisableTiming));
+    s->vx.have[0] = s->vx.have[1] = false;
+    s->vx.slot = 0;
+    s->vx.world = world;
   }
   // the side stream of the exchange; the exact particle mode runs everything in order on the compute stream (wx_set_option may have
   // switched modes since the last call)
-  const bool in_order = (s->pool_remote && s->pool_exact) || s->exchange_in_order;
+  const bool in_order = (s->pool.remote && s->opt.pool_exact) || s->opt.exchange_in_order;
   if (!in_order && !s->comm_stream) {
-    if (!s->own_comm_stream) { // highest priority: its small pack / unpack kernels run next to a marching kernel that holds every wave slot
+    if (!s->tx.own_comm_stream) { // highest priority: its small pack / unpack kernels run next to a marching kernel that holds every wave slot
       int prio_lo = 0, prio_hi = 0;
       if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
-      HIPCHK(s, hipStreamCreateWithPriority(&s->own_comm_stream, hipStreamNonBlocking, prio_hi));
+      HIPCHK(s, hipStreamCreateWithPriority(&s->tx.own_comm_stream, hipStreamNonBlocking, prio_hi));
     }
-    if (int rc = wx_set_comm_stream(s, s->own_comm_stream)) return rc;
-  } else if (in_order && s->comm_stream && s->comm_stream == s->own_comm_stream) {
+    if (int rc = wx_set_comm_stream(s, s->tx.own_comm_stream)) return rc;
+  } else if (in_order && s->comm_stream && s->comm_stream == s->tx.own_comm_stream) {
     if (int rc = wx_set_comm_stream(s, nullptr)) return rc;
   }
   return WX_OK;
@@ -158,48 +159,48 @@ static int transport_prepare(wx_sim *s, int world)
 
 void transport_release(wx_sim *s)
 {
-  if (s->comm) {
-    if (RcclApi *a = rccl_api()) a->CommDestroy((ncclComm_t)s->comm);
-    s->comm = nullptr;
+  if (s->tx.comm) {
+    if (RcclApi *a = rccl_api()) a->CommDestroy((ncclComm_t)s->tx.comm);
+    s->tx.comm = nullptr;
   }
   for (int i = 0; i < 2; i++) {
-    hipFree(s->xsend[i]);
-    hipFree(s->xrecv[i]);
-    hipFree(s->psend[i]);
-    hipFree(s->precv[i]);
-    s->xsend[i] = s->xrecv[i] = s->psend[i] = s->precv[i] = nullptr;
+    hipFree(s->tx.xsend[i]);
+    hipFree(s->tx.xrecv[i]);
+    hipFree(s->pool.psend[i]);
+    hipFree(s->pool.precv[i]);
+    s->tx.xsend[i] = s->tx.xrecv[i] = s->pool.psend[i] = s->pool.precv[i] = nullptr;
   }
-  hipFree(s->ev_mine);
-  hipFree(s->ev_all);
-  s->ev_mine = s->ev_all = nullptr;
-  hipFree(s->vx_dev);
-  s->vx_dev = nullptr;
-  if (s->vx_host) hipHostFree(s->vx_host);
-  s->vx_host = nullptr;
-  s->vx_world = 0;
+  hipFree(s->pool.ev_mine);
+  hipFree(s->pool.ev_all);
+  s->pool.ev_mine = s->pool.ev_all = nullptr;
+  hipFree(s->vx.dev);
+  s->vx.dev = nullptr;
+  if (s->vx.host) hipHostFree(s->vx.host);
+  s->vx.host = nullptr;
+  s->vx.world = 0;
   for (int i = 0; i < 2; i++) {
-    if (s->ev_vx[i]) hipEventDestroy(s->ev_vx[i]);
-    s->ev_vx[i] = nullptr;
+    if (s->vx.ev[i]) hipEventDestroy(s->vx.ev[i]);
+    s->vx.ev[i] = nullptr;
   }
-  if (s->ev_seen_host) hipHostFree(s->ev_seen_host);
-  s->ev_seen_host = nullptr;
-  if (s->ev_counted) hipEventDestroy(s->ev_counted);
-  s->ev_counted = nullptr;
-  s->count_pending = false;
-  s->xbytes = 0;
-  for (hipEvent_t *e : {&s->ev_packed, &s->ev_copied, &s->ev_evpacked, &s->ev_evcopied}) {
+  if (s->pool.ev_seen_host) hipHostFree(s->pool.ev_seen_host);
+  s->pool.ev_seen_host = nullptr;
+  if (s->pool.ev_counted) hipEventDestroy(s->pool.ev_counted);
+  s->pool.ev_counted = nullptr;
+  s->pool.count_pending = false;
+  s->tx.xbytes = 0;
+  for (hipEvent_t *e : {&s->tx.ev_packed, &s->tx.ev_copied, &s->pool.ev_evpacked, &s->pool.ev_evcopied}) {
     if (*e) hipEventDestroy(*e);
     *e = nullptr;
   }
-  if (s->own_comm_stream) {
-    if (s->comm_stream == s->own_comm_stream) s->comm_stream = nullptr;
-    hipStreamDestroy(s->own_comm_stream);
-    s->own_comm_stream = nullptr;
+  if (s->tx.own_comm_stream) {
+    if (s->comm_stream == s->tx.own_comm_stream) s->comm_stream = nullptr;
+    hipStreamDestroy(s->tx.own_comm_stream);
+    s->tx.own_comm_stream = nullptr;
   }
-  if (s->own_stream) {
-    if (s->stream == s->own_stream) s->stream = nullptr;
-    hipStreamDestroy(s->own_stream);
-    s->own_stream = nullptr;
+  if (s->tx.own_stream) {
+    if (s->stream == s->tx.own_stream) s->stream = nullptr;
+    hipStreamDestroy(s->tx.own_stream);
+    s->tx.own_stream = nullptr;
   }
 }
 
@@ -232,8 +233,9 @@ static int rpass(Ring &R, wx_sim *s, int rc)
   if (rc != WX_OK && R.err) *R.err = s->err;
   return rc;
 }
-// local transport: every slab's exchange stream waits for event `ev` of every OTHER slab (or of its two ring neighbours only)
-static int local_wait(Ring &R, hipEvent_t wx_sim::*ev, bool neighbours_only)
+// local transport: every slab's exchange stream waits for event `ev` (of the handle's group `grp`) of every OTHER slab (or of its two ring
+// neighbours only)
+template <class G> static int local_wait(Ring &R, G wx_sim::*grp, hipEvent_t G::*ev, bool neighbours_only)
 {
   const int n = (int)R.p.size();
   for (int i = 0; i < n; i++) {
@@ -241,16 +243,16 @@ static int local_wait(Ring &R, hipEvent_t wx_sim::*ev, bool neighbours_only)
     DeviceScope ds(s);
     for (int r = 0; r < n; r++) {
       if (r == i || (neighbours_only && r != (i + 1) % n && r != (i + n - 1) % n)) continue;
-      if (hipStreamWaitEvent(xstream(s), R.p[r].s->*ev, 0) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipStreamWaitEvent");
+      if (hipStreamWaitEvent(xstream(s), R.p[r].s->*grp.*ev, 0) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipStreamWaitEvent");
     }
   }
   return WX_OK;
 }
-static int local_record(Ring &R, hipEvent_t wx_sim::*ev)
+template <class G> static int local_record(Ring &R, G wx_sim::*grp, hipEvent_t G::*ev)
 {
   for (Party &q : R.p) {
     DeviceScope ds(q.s);
-    if (hipEventRecord(q.s->*ev, xstream(q.s)) != hipSuccess) return rfail(R, q.s, WX_E_DEVICE, "hipEventRecord");
+    if (hipEventRecord(q.s->*grp.*ev, xstream(q.s)) != hipSuccess) return rfail(R, q.s, WX_E_DEVICE, "hipEventRecord");
   }
   return WX_OK;
 }
@@ -261,29 +263,29 @@ static int pool_events_round(Ring &R, int mode)
 {
   const bool local = R.transport == WX_TRANSPORT_LOCAL;
   if (local) // nobody may still be copying my previous events
-    if (int rc = local_wait(R, &wx_sim::ev_evcopied, false)) return rc;
+    if (int rc = local_wait(R, &wx_sim::pool, &Pool::ev_evcopied, false)) return rc;
   for (Party &q : R.p) {
     DeviceScope ds(q.s);
-    if (int rc = rpass(R, q.s, pool_events_pack_mode(q.s, q.s->ev_mine, mode))) return rc;
+    if (int rc = rpass(R, q.s, pool_events_pack_mode(q.s, q.s->pool.ev_mine, mode))) return rc;
   }
   if (local) {
-    if (int rc = local_record(R, &wx_sim::ev_evpacked)) return rc;
-    if (int rc = local_wait(R, &wx_sim::ev_evpacked, false)) return rc;
+    if (int rc = local_record(R, &wx_sim::pool, &Pool::ev_evpacked)) return rc;
+    if (int rc = local_wait(R, &wx_sim::pool, &Pool::ev_evpacked, false)) return rc;
     for (Party &q : R.p) {
       wx_sim *s = q.s;
       DeviceScope ds(s);
       const size_t stride = pool_stride(s);
       for (Party &o : R.p)
-        if (hipMemcpyAsync(s->ev_all + (size_t)o.rank * stride, o.s->ev_mine, stride, hipMemcpyDefault, xstream(s)) != hipSuccess)
+        if (hipMemcpyAsync(s->pool.ev_all + (size_t)o.rank * stride, o.s->pool.ev_mine, stride, hipMemcpyDefault, xstream(s)) != hipSuccess)
           return rfail(R, s, WX_E_DEVICE, "device-to-device copy of the status-flip events");
     }
-    if (int rc = local_record(R, &wx_sim::ev_evcopied)) return rc;
+    if (int rc = local_record(R, &wx_sim::pool, &Pool::ev_evcopied)) return rc;
   } else {
     RcclApi *a = rccl_api();
     if (a->GroupStart() != ncclSuccess) return rfail(R, nullptr, WX_E_DEVICE, "ncclGroupStart");
     for (Party &q : R.p) {
       DeviceScope ds(q.s);
-      const ncclResult_t r = a->AllGather(q.s->ev_mine, q.s->ev_all, pool_stride(q.s), ncclUint8, q.comm, xstream(q.s));
+      const ncclResult_t r = a->AllGather(q.s->pool.ev_mine, q.s->pool.ev_all, pool_stride(q.s), ncclUint8, q.comm, xstream(q.s));
       if (r != ncclSuccess) {
         a->GroupEnd();
         return rfail(R, q.s, WX_E_DEVICE, "ncclAllGather of the status-flip events: %s", a->GetErrorString(r));
@@ -293,7 +295,7 @@ static int pool_events_round(Ring &R, int mode)
   }
   for (Party &q : R.p) {
     DeviceScope ds(q.s);
-    if (int rc = rpass(R, q.s, pool_events_apply_mode(q.s, q.s->ev_all, R.world, pool_stride(q.s), mode))) return rc;
+    if (int rc = rpass(R, q.s, pool_events_apply_mode(q.s, q.s->pool.ev_all, R.world, pool_stride(q.s), mode))) return rc;
   }
   return WX_OK;
 }
@@ -305,13 +307,13 @@ static int pool_stride_update(Ring &R)
 {
   for (Party &q : R.p) {
     wx_sim *s = q.s;
-    if (!s->count_pending) continue;
+    if (!s->pool.count_pending) continue;
     DeviceScope ds(s);
-    if (hipEventSynchronize(s->ev_counted) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "waiting for the status-flip counts: %s", hipGetErrorString(hipGetLastError()));
-    const long long seen = *s->ev_seen_host;
-    s->count_pending = false;
+    if (hipEventSynchronize(s->pool.ev_counted) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "waiting for the status-flip counts: %s", hipGetErrorString(hipGetLastError()));
+    const long long seen = *s->pool.ev_seen_host;
+    s->pool.count_pending = false;
     if (hipMemsetAsync(&s->state->pool_seen_max, 0, 4, pool_stream(s)) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipMemsetAsync");
-    s->pool_stride_events = (int)std::min<long long>(std::max<long long>(65536, 4 * seen), 1 << 30);
+    s->pool.stride_events = (int)std::min<long long>(std::max<long long>(65536, 4 * seen), 1 << 30);
   }
   return WX_OK;
 }
@@ -326,11 +328,11 @@ static float bits_to_float(int b)
 // After an upload: every slab looks at its state, the ring takes the maximum. The one place where the protocol waits for the device -- once
 // per upload, before the first iteration. With one rank per process the decision below is rank-local and the all-gather is a collective:
 // wx_upload / wx_setup_* on the slabs of an initialised ring are therefore COLLECTIVE calls (every rank, before the next exchange:
-// include/wxsim.h); nothing else sets vx_stale (velocities written through wx_device_ptr only mark the state for the next roll's scan).
+// include/wxsim.h); nothing else sets VxWatch::stale (velocities written through wx_device_ptr only mark the state for the next roll's scan).
 static int ring_vx_bootstrap(Ring &R)
 {
   bool stale = false;
-  for (Party &q : R.p) stale = stale || q.s->vx_stale;
+  for (Party &q : R.p) stale = stale || q.s->vx.stale;
   if (!stale) return WX_OK;
   float v = 0.0f;
   for (Party &q : R.p) {
@@ -346,16 +348,16 @@ static int ring_vx_bootstrap(Ring &R)
     int bits;
     memcpy(&bits, &v, 4);
     std::vector<int> all((size_t)R.world, 0);
-    if (hipMemcpyAsync(s->vx_dev, &bits, 4, hipMemcpyHostToDevice, xstream(s)) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipMemcpyAsync");
-    const ncclResult_t r = a->AllGather(s->vx_dev, s->vx_dev + 1, 1, ncclInt32, R.p[0].comm, xstream(s));
+    if (hipMemcpyAsync(s->vx.dev, &bits, 4, hipMemcpyHostToDevice, xstream(s)) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipMemcpyAsync");
+    const ncclResult_t r = a->AllGather(s->vx.dev, s->vx.dev + 1, 1, ncclInt32, R.p[0].comm, xstream(s));
     if (r != ncclSuccess) return rfail(R, s, WX_E_DEVICE, "ncclAllGather of the slabs' |vx|: %s", a->GetErrorString(r));
-    if (hipMemcpyAsync(all.data(), s->vx_dev + 1, 4 * (size_t)R.world, hipMemcpyDeviceToHost, xstream(s)) != hipSuccess || hipStreamSynchronize(xstream(s)) != hipSuccess)
+    if (hipMemcpyAsync(all.data(), s->vx.dev + 1, 4 * (size_t)R.world, hipMemcpyDeviceToHost, xstream(s)) != hipSuccess || hipStreamSynchronize(xstream(s)) != hipSuccess)
       return rfail(R, s, WX_E_DEVICE, "reading the slabs' |vx| back");
     for (int b : all) v = std::max(v, bits_to_float(b));
   }
   for (Party &q : R.p) {
     if (int rc = rpass(R, q.s, wx_slab_set_vx_bound(q.s, v))) return rc;
-    q.s->vx_have[0] = q.s->vx_have[1] = false;
+    q.s->vx.have[0] = q.s->vx.have[1] = false;
   }
   return WX_OK;
 }
@@ -366,21 +368,21 @@ static int ring_vx_roll(Ring &R)
 {
   wx_sim *s0 = R.p[0].s;
   const bool rccl = R.transport == WX_TRANSPORT_RCCL;
-  const int slot = s0->vx_slot, prev = slot ^ 1, W = R.world;
+  const int slot = s0->vx.slot, prev = slot ^ 1, W = R.world;
   // 1. the bound of the coming period, from what the earlier rolls left in the pinned words (read BEFORE the new roll overwrites `slot`)
-  float v = s0->vx_known;
-  if (s0->vx_have[prev]) {
+  float v = s0->vx.known;
+  if (s0->vx.have[prev]) {
     v = 0.0f;
     for (Party &q : R.p) {
       wx_sim *s = q.s;
       DeviceScope ds(s);
-      if (hipEventSynchronize(s->ev_vx[prev]) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "waiting for the slabs' |vx| of the previous exchange");
+      if (hipEventSynchronize(s->vx.ev[prev]) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "waiting for the slabs' |vx| of the previous exchange");
       for (int sl = 0; sl < 2; sl++) {
-        if (!s->vx_have[sl]) continue; // (the older roll too: a flow that slowed down for one period keeps its margin for one more)
+        if (!s->vx.have[sl]) continue; // (the older roll too: a flow that slowed down for one period keeps its margin for one more)
         if (rccl)
-          for (int r = 0; r < W; r++) v = std::max(v, bits_to_float(s->vx_host[sl * W + r]));
+          for (int r = 0; r < W; r++) v = std::max(v, bits_to_float(s->vx.host[sl * W + r]));
         else
-          v = std::max(v, bits_to_float(s->vx_host[sl * W + q.rank]));
+          v = std::max(v, bits_to_float(s->vx.host[sl * W + q.rank]));
       }
     }
   }
@@ -389,25 +391,25 @@ static int ring_vx_roll(Ring &R)
     wx_sim *s = q.s;
     DeviceScope ds(s);
     hipStream_t st = xstream(s);
-    if (s->vx_untracked) { // iterations of kernels that do not report their |vx|: look at the state they left
+    if (s->vx.untracked) { // iterations of kernels that do not report their |vx|: look at the state they left
       if (st != s->stream) { // (such kernels are never split: the exchange is behind the whole iteration)
-        if (!s->edges_recorded) {
-          if (hipEventRecord(s->ev_edges, s->stream) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipEventRecord");
-          s->edges_recorded = true;
+        if (!s->split.edges_recorded) {
+          if (hipEventRecord(s->split.ev_edges, s->stream) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipEventRecord");
+          s->split.edges_recorded = true;
         }
-        if (hipStreamWaitEvent(st, s->ev_edges, 0) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipStreamWaitEvent");
+        if (hipStreamWaitEvent(st, s->split.ev_edges, 0) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "hipStreamWaitEvent");
       }
       vx_scan_enqueue(s, st, true);
-      s->vx_untracked = false;
+      s->vx.untracked = false;
     }
-    hipLaunchKernelGGL(k_vx_roll, dim3(1), dim3(1), 0, st, s->state, s->vx_dev);
+    hipLaunchKernelGGL(k_vx_roll, dim3(1), dim3(1), 0, st, s->state, s->vx.dev);
   }
   if (rccl) {
     RcclApi *a = rccl_api();
     if (a->GroupStart() != ncclSuccess) return rfail(R, nullptr, WX_E_DEVICE, "ncclGroupStart");
     for (Party &q : R.p) {
       DeviceScope ds(q.s);
-      const ncclResult_t r = a->AllGather(q.s->vx_dev, q.s->vx_dev + 1, 1, ncclInt32, q.comm, xstream(q.s));
+      const ncclResult_t r = a->AllGather(q.s->vx.dev, q.s->vx.dev + 1, 1, ncclInt32, q.comm, xstream(q.s));
       if (r != ncclSuccess) {
         a->GroupEnd();
         return rfail(R, q.s, WX_E_DEVICE, "ncclAllGather of the slabs' |vx|: %s", a->GetErrorString(r));
@@ -419,11 +421,11 @@ static int ring_vx_roll(Ring &R)
     wx_sim *s = q.s;
     DeviceScope ds(s);
     hipStream_t st = xstream(s);
-    const hipError_t e = rccl ? hipMemcpyAsync(s->vx_host + slot * W, s->vx_dev + 1, 4 * (size_t)W, hipMemcpyDeviceToHost, st)
-                              : hipMemcpyAsync(s->vx_host + slot * W + q.rank, s->vx_dev, 4, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess || hipEventRecord(s->ev_vx[slot], st) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "copying the slabs' |vx| to the host");
-    s->vx_have[slot] = true;
-    s->vx_slot = prev;
+    const hipError_t e = rccl ? hipMemcpyAsync(s->vx.host + slot * W, s->vx.dev + 1, 4 * (size_t)W, hipMemcpyDeviceToHost, st)
+                              : hipMemcpyAsync(s->vx.host + slot * W + q.rank, s->vx.dev, 4, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess || hipEventRecord(s->vx.ev[slot], st) != hipSuccess) return rfail(R, s, WX_E_DEVICE, "copying the slabs' |vx| to the host");
+    s->vx.have[slot] = true;
+    s->vx.slot = prev;
     if (int rc = rpass(R, s, wx_slab_set_vx_bound(s, v))) return rc;
   }
   return WX_OK;
@@ -437,43 +439,43 @@ static int ring_exchange(Ring &R)
   const int n = (int)R.p.size();
   if (R.world < 2) return WX_OK;
   const bool local = R.transport == WX_TRANSPORT_LOCAL;
-  const bool particles = R.p[0].s->pool_remote != nullptr;
-  for (Party &q : R.p) q.s->xchg_inline = dry_runs_in_order(q.s); // (decided once per exchange: xstream() below is one stream throughout)
+  const bool particles = R.p[0].s->pool.remote != nullptr;
+  for (Party &q : R.p) q.s->tx.xchg_inline = dry_runs_in_order(q.s); // (decided once per exchange: xstream() below is one stream throughout)
   if (particles)
     if (int rc = pool_stride_update(R)) return rc;
   if (local) // my send buffers are free once both neighbours have copied the previous exchange out of them
-    if (int rc = local_wait(R, &wx_sim::ev_copied, true)) return rc;
+    if (int rc = local_wait(R, &wx_sim::tx, &Transport::ev_copied, true)) return rc;
   for (Party &q : R.p) { // (grid-only slabs: on the comm stream, behind the edge strips only)
     DeviceScope ds(q.s);
-    if (int rc = rpass(R, q.s, wx_halo_pack_both(q.s, q.s->xsend[0], q.s->xsend[1]))) return rc; // (one launch: see HaloBufs)
+    if (int rc = rpass(R, q.s, wx_halo_pack_both(q.s, q.s->tx.xsend[0], q.s->tx.xsend[1]))) return rc; // (one launch: see HaloBufs)
   }
   if (int rc = ring_vx_roll(R)) return rc; // the period that starts behind this exchange: how many ghost columns per iteration?
-  if (particles && !R.p[0].s->pool_exact)
+  if (particles && !R.p[0].s->opt.pool_exact)
     if (int rc = pool_events_round(R, 2)) return rc;
   if (particles)
     for (Party &q : R.p) { // ownership by position; the droplets near my edges become the neighbours' ghost copies
       wx_sim *s = q.s;
       DeviceScope ds(s);
-      const int refresh = !s->pool_exact && (s->iter / 600) != ((s->iter - s->since_exchange) / 600); // app.js:5957-5966: every 600 iterations
-      if (int rc = rpass(R, s, wx_pool_edges_pack(s, s->psend[0], s->psend[1], refresh))) return rc;
+      const int refresh = !s->opt.pool_exact && (s->run.iter / 600) != ((s->run.iter - s->tx.since_exchange) / 600); // app.js:5957-5966: every 600 iterations
+      if (int rc = rpass(R, s, wx_pool_edges_pack(s, s->pool.psend[0], s->pool.psend[1], refresh))) return rc;
     }
   if (local) {
-    if (int rc = local_record(R, &wx_sim::ev_packed)) return rc;
-    if (int rc = local_wait(R, &wx_sim::ev_packed, true)) return rc;
+    if (int rc = local_record(R, &wx_sim::tx, &Transport::ev_packed)) return rc;
+    if (int rc = local_wait(R, &wx_sim::tx, &Transport::ev_packed, true)) return rc;
     for (int i = 0; i < n; i++) {
       wx_sim *s = R.p[i].s, *L = R.p[(i + n - 1) % n].s, *Rt = R.p[(i + 1) % n].s;
       DeviceScope ds(s);
       const size_t mb = wx_halo_message_bytes(s); // (the base texture alone between slabs of the agreed water-free dry stencil)
-      bool ok = hipMemcpyAsync(s->xrecv[0], L->xsend[1], mb, hipMemcpyDefault, xstream(s)) == hipSuccess && // left ghosts <- left neighbour's right edge
-                hipMemcpyAsync(s->xrecv[1], Rt->xsend[0], mb, hipMemcpyDefault, xstream(s)) == hipSuccess; // right ghosts <- right neighbour's left edge
+      bool ok = hipMemcpyAsync(s->tx.xrecv[0], L->tx.xsend[1], mb, hipMemcpyDefault, xstream(s)) == hipSuccess && // left ghosts <- left neighbour's right edge
+                hipMemcpyAsync(s->tx.xrecv[1], Rt->tx.xsend[0], mb, hipMemcpyDefault, xstream(s)) == hipSuccess; // right ghosts <- right neighbour's left edge
       if (ok && particles) {
         const size_t gb = wx_pool_edge_bytes(s);
-        ok = hipMemcpyAsync(s->precv[0], L->psend[1], gb, hipMemcpyDefault, xstream(s)) == hipSuccess &&
-             hipMemcpyAsync(s->precv[1], Rt->psend[0], gb, hipMemcpyDefault, xstream(s)) == hipSuccess;
+        ok = hipMemcpyAsync(s->pool.precv[0], L->pool.psend[1], gb, hipMemcpyDefault, xstream(s)) == hipSuccess &&
+             hipMemcpyAsync(s->pool.precv[1], Rt->pool.psend[0], gb, hipMemcpyDefault, xstream(s)) == hipSuccess;
       }
       if (!ok) return rfail(R, s, WX_E_DEVICE, "device-to-device halo copy of slab %d: %s", i, hipGetErrorString(hipGetLastError()));
     }
-    if (int rc = local_record(R, &wx_sim::ev_copied)) return rc;
+    if (int rc = local_record(R, &wx_sim::tx, &Transport::ev_copied)) return rc;
   } else {
     // (two ranks: both neighbours are the same peer -- messages between a pair match in order, so what I receive first is the peer's
     // first send, its LEFT edge, which belongs into my RIGHT ghosts)
@@ -485,16 +487,16 @@ static int ring_exchange(Ring &R)
       const int left = (q.rank + R.world - 1) % R.world, right = (q.rank + 1) % R.world;
       hipStream_t st = xstream(s);
       const size_t mb = wx_halo_message_bytes(s); // (equal on every rank: the format changes only through collective calls)
-      ncclResult_t r = a->Send(s->xsend[0], mb, ncclUint8, left, q.comm, st);
-      if (r == ncclSuccess) r = a->Send(s->xsend[1], mb, ncclUint8, right, q.comm, st);
-      if (r == ncclSuccess) r = a->Recv(s->xrecv[1], mb, ncclUint8, right, q.comm, st);
-      if (r == ncclSuccess) r = a->Recv(s->xrecv[0], mb, ncclUint8, left, q.comm, st);
+      ncclResult_t r = a->Send(s->tx.xsend[0], mb, ncclUint8, left, q.comm, st);
+      if (r == ncclSuccess) r = a->Send(s->tx.xsend[1], mb, ncclUint8, right, q.comm, st);
+      if (r == ncclSuccess) r = a->Recv(s->tx.xrecv[1], mb, ncclUint8, right, q.comm, st);
+      if (r == ncclSuccess) r = a->Recv(s->tx.xrecv[0], mb, ncclUint8, left, q.comm, st);
       if (particles) {
         const size_t gb = wx_pool_edge_bytes(s);
-        if (r == ncclSuccess) r = a->Send(s->psend[0], gb, ncclUint8, left, q.comm, st);
-        if (r == ncclSuccess) r = a->Send(s->psend[1], gb, ncclUint8, right, q.comm, st);
-        if (r == ncclSuccess) r = a->Recv(s->precv[1], gb, ncclUint8, right, q.comm, st);
-        if (r == ncclSuccess) r = a->Recv(s->precv[0], gb, ncclUint8, left, q.comm, st);
+        if (r == ncclSuccess) r = a->Send(s->pool.psend[0], gb, ncclUint8, left, q.comm, st);
+        if (r == ncclSuccess) r = a->Send(s->pool.psend[1], gb, ncclUint8, right, q.comm, st);
+        if (r == ncclSuccess) r = a->Recv(s->pool.precv[1], gb, ncclUint8, right, q.comm, st);
+        if (r == ncclSuccess) r = a->Recv(s->pool.precv[0], gb, ncclUint8, left, q.comm, st);
       }
       if (r != ncclSuccess) {
         a->GroupEnd();
@@ -506,14 +508,14 @@ static int ring_exchange(Ring &R)
   for (Party &q : R.p) { // into the ghost columns (grid-only: records the event the next edge strips wait for)
     wx_sim *s = q.s;
     DeviceScope ds(s);
-    if (int rc = rpass(R, s, wx_halo_unpack_both(s, s->xrecv[0], s->xrecv[1]))) return rc;
+    if (int rc = rpass(R, s, wx_halo_unpack_both(s, s->tx.xrecv[0], s->tx.xrecv[1]))) return rc;
     if (particles) {
-      if (int rc = rpass(R, s, wx_pool_edges_apply(s, s->precv[0]))) return rc;
-      if (int rc = rpass(R, s, wx_pool_edges_apply(s, s->precv[1]))) return rc;
+      if (int rc = rpass(R, s, wx_pool_edges_apply(s, s->pool.precv[0]))) return rc;
+      if (int rc = rpass(R, s, wx_pool_edges_apply(s, s->pool.precv[1]))) return rc;
       if (int rc = rpass(R, s, wx_slab_period_begin(s))) return rc;
     }
-    s->since_exchange = 0;
-    s->exchanged = true;
+    s->tx.since_exchange = 0;
+    s->tx.exchanged = true;
   }
   return WX_OK;
 }
@@ -531,20 +533,20 @@ static int ring_step(Ring &R, int n_iter)
   }
   if (n_iter > 0)
     if (int rc = ring_vx_bootstrap(R)) return rc;
-  const bool particles = s0->pool_remote != nullptr, exact = particles && s0->pool_exact;
+  const bool particles = s0->pool.remote != nullptr, exact = particles && s0->opt.pool_exact;
   for (int done = 0; done < n_iter;) {
     const int ipe = iters_per_exchange(s0); // (the bound -- and with it the period -- is settled at every exchange)
-    if (s0->since_exchange >= ipe) { // (a bound that rose inside a period, through wx_slab_set_vx_bound: exchange first)
+    if (s0->tx.since_exchange >= ipe) { // (a bound that rose inside a period, through wx_slab_set_vx_bound: exchange first)
       if (int rc = ring_exchange(R)) return rc;
       continue;
     }
-    const int k = std::min(ipe - s0->since_exchange, n_iter - done);
+    const int k = std::min(ipe - s0->tx.since_exchange, n_iter - done);
     if (exact) { // one iteration at a time, each followed by the status flips / lightning requests of all slabs
       for (int it = 0; it < k; it++) {
         for (Party &q : R.p) {
           DeviceScope ds(q.s);
           if (int rc = rpass(R, q.s, wx_step_overlap(q.s, 1, done + it + 1 < n_iter ? WX_OVERLAP_MORE_TO_COME : 0u))) return rc;
-          q.s->since_exchange += 1;
+          q.s->tx.since_exchange += 1;
         }
         if (int rc = pool_events_round(R, 1)) return rc;
       }
@@ -554,14 +556,14 @@ static int ring_step(Ring &R, int n_iter)
         DeviceScope ds(s);
         // the iteration before an exchange launches its edge strips first, the one after it its interior strips first (wx_step_overlap;
         // with particles only the latter: the exchange -- grid, feedback texture and droplet pool -- hides behind the next interior)
-        const unsigned flags = ((s->since_exchange == 0 && s->exchanged) ? WX_OVERLAP_EDGES_LAST : 0u) | (s->since_exchange + k >= ipe ? WX_OVERLAP_EDGES_FIRST : 0u) |
+        const unsigned flags = ((s->tx.since_exchange == 0 && s->tx.exchanged) ? WX_OVERLAP_EDGES_LAST : 0u) | (s->tx.since_exchange + k >= ipe ? WX_OVERLAP_EDGES_FIRST : 0u) |
                                (done + k < n_iter ? WX_OVERLAP_MORE_TO_COME : 0u); // (only the call's last piece stores the display-side fields)
         if (int rc = rpass(R, s, wx_step_overlap(s, k, flags))) return rc;
-        s->since_exchange += k;
+        s->tx.since_exchange += k;
       }
     }
     done += k;
-    if (s0->since_exchange >= ipe)
+    if (s0->tx.since_exchange >= ipe)
       if (int rc = ring_exchange(R)) return rc;
   }
   return WX_OK;
@@ -590,17 +592,17 @@ int wx_comm_init(wx_sim *s, const void *id128, int rank, int world)
   if (world == 1 && s->halo != 0) return fail(s, WX_E_INVALID, "wx_comm_init: a job of one rank takes a handle without ghost columns (halo 0)");
   if (world > 1)
     if (int rc = transport_prepare(s, world)) return rc;
-  if (s->comm) {
-    a->CommDestroy((ncclComm_t)s->comm);
-    s->comm = nullptr;
+  if (s->tx.comm) {
+    a->CommDestroy((ncclComm_t)s->tx.comm);
+    s->tx.comm = nullptr;
   }
   ncclUniqueId id;
   memcpy(&id, id128, sizeof(id));
   ncclComm_t c = nullptr;
   NCCLCHK(s, a->CommInitRank(&c, world, id, rank));
-  s->comm = c;
-  s->comm_rank = rank;
-  s->comm_world = world;
+  s->tx.comm = c;
+  s->tx.comm_rank = rank;
+  s->tx.comm_world = world;
   s->rank = rank;
   return WX_OK;
 }
@@ -608,8 +610,8 @@ int wx_comm_init(wx_sim *s, const void *id128, int rank, int world)
 static Ring ring_of(wx_sim *s)
 {
   Ring R;
-  R.p.push_back(Party{s, (ncclComm_t)s->comm, s->comm_rank});
-  R.world = s->comm_world;
+  R.p.push_back(Party{s, (ncclComm_t)s->tx.comm, s->tx.comm_rank});
+  R.world = s->tx.comm_world;
   R.transport = WX_TRANSPORT_RCCL;
   return R;
 }
@@ -618,9 +620,9 @@ static Ring ring_of(wx_sim *s)
 int wx_exchange(wx_sim *s)
 {
   if (!s) return WX_E_INVALID;
-  if (!s->comm) return fail(s, WX_E_STATE, "wx_exchange before wx_comm_init");
-  if (s->comm_world > 1)
-    if (int rc = transport_prepare(s, s->comm_world)) return rc;
+  if (!s->tx.comm) return fail(s, WX_E_STATE, "wx_exchange before wx_comm_init");
+  if (s->tx.comm_world > 1)
+    if (int rc = transport_prepare(s, s->tx.comm_world)) return rc;
   Ring R = ring_of(s);
   return ring_exchange(R);
 }
@@ -628,9 +630,9 @@ int wx_exchange(wx_sim *s)
 int wx_slab_step(wx_sim *s, int n_iter)
 {
   if (!s || n_iter < 0) return WX_E_INVALID;
-  if (!s->comm) return fail(s, WX_E_STATE, "wx_slab_step before wx_comm_init");
-  if (s->comm_world > 1)
-    if (int rc = transport_prepare(s, s->comm_world)) return rc;
+  if (!s->tx.comm) return fail(s, WX_E_STATE, "wx_slab_step before wx_comm_init");
+  if (s->tx.comm_world > 1)
+    if (int rc = transport_prepare(s, s->tx.comm_world)) return rc;
   Ring R = ring_of(s);
   return ring_step(R, n_iter);
 }
@@ -733,11 +735,11 @@ int wx_group_create(int n_slabs, const int *devices, int X_global, int Y, int ha
     g->slab[i] = s;
     s->rank = i;
     // streams of the slab's own: the slabs of a group run concurrently (also when several share a device)
-    if (hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking) != hipSuccess) rc = gfail(nullptr, WX_E_DEVICE, "hipStreamCreate");
-    else s->stream = s->own_stream;
+    if (hipStreamCreateWithFlags(&s->tx.own_stream, hipStreamNonBlocking) != hipSuccess) rc = gfail(nullptr, WX_E_DEVICE, "hipStreamCreate");
+    else s->stream = s->tx.own_stream;
     if (rc == WX_OK && n_slabs > 1) {
       rc = transport_prepare(s, n_slabs);
-      for (hipEvent_t *e : {&s->ev_packed, &s->ev_copied, &s->ev_evpacked, &s->ev_evcopied})
+      for (hipEvent_t *e : {&s->tx.ev_packed, &s->tx.ev_copied, &s->pool.ev_evpacked, &s->pool.ev_evcopied})
         if (rc == WX_OK && hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) rc = gfail(nullptr, WX_E_DEVICE, "hipEventCreate");
       if (rc != WX_OK && g_create_error.empty()) g_create_error = s->err;
     }
