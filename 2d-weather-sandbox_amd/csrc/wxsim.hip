@@ -1113,6 +1113,7 @@ static void clear_particle_textures(wx_sim *s)
   const size_t n = ncell(s);
   hipMemsetAsync(s->fb, 0, n * 12, s->stream);
   hipMemsetAsync(s->dep, 0, n * 8, s->stream);
+  hipMemsetAsync(&s->state->mailbox_w, 0, 4, s->stream); // (texel (1,0)'s alpha, the one the texture has: kept in the state, cleared with the texture)
   if (s->sg.fb_zero) hipMemsetAsync(s->sg.fb_zero, 1, 2 * (size_t)s->sg.TXn * s->sg.TYn, s->stream);
   s->run.fb_dirty = false;
 }
@@ -1984,6 +1985,9 @@ int wx_tune_placement(wx_sim *s, int tries, int iters_per_try, float *ms_before,
   } busy(s);
   TuneSnap snap;
   if (s->store.blocks.empty() || !snap_take(s, snap)) return fail(s, WX_E_STATE, "wx_tune_placement: the handle's planes are not in registered blocks");
+  // (the pair kernel's control words are not in the blocks: what wx_pair_stats counts is saved here and put back behind the probes)
+  int pair_ctl[D2_WORDS] = {0};
+  if (s->pair.words) HIPCHK(s, hipMemcpy(pair_ctl, s->pair.words, sizeof(pair_ctl), hipMemcpyDeviceToHost));
   hipEvent_t e0, e1;
   HIPCHK(s, hipEventCreate(&e0));
   HIPCHK(s, hipEventCreate(&e1));
@@ -2099,6 +2103,9 @@ int wx_tune_placement(wx_sim *s, int tries, int iters_per_try, float *ms_before,
   if (copy_set(s, best, backup) != WX_OK || hipStreamSynchronize(s->stream) != hipSuccess) rc = WX_E_DEVICE;
   if (rebase(s, best) != WX_OK) rc = WX_E_DEVICE;
   snap_put(s, snap);
+  if (s->pair.words && (hipMemcpy(s->pair.words + D2_N_REDO, pair_ctl + D2_N_REDO, 4, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(s->pair.words + D2_FIXED, pair_ctl + D2_FIXED, 8, hipMemcpyHostToDevice) != hipSuccess))
+    rc = WX_E_DEVICE;
   for (auto &r : rejects) free_set(r);
   for (char *p : pads) hipFree(p);
   free_set(backup);
@@ -2456,6 +2463,9 @@ int wx_read_particles(wx_sim *s, int first, int count, float *dst)
   if (first < 0 || count < 0 || (long long)first + count > s->n_drops) return fail(s, WX_E_RANGE, "wx_read_particles: [%d, %d) outside 0..%d", first, first + count, s->n_drops);
   if (count == 0) return WX_OK;
   wait_unpacked(s); // (a pool exchange still running on the side stream)
+  // (a blocking call that hands out state: what the iterations have to report -- an overflowed exact-path list leaves the droplets of a
+  // wrong grid behind -- is reported here as by wx_read_rect, not with the next field somebody reads)
+  if (int rc = validate_ghost_flag(s)) return rc;
   HIPCHK(s, hipMemcpyAsync(dst, s->drops[s->run.drop_cur] + 5 * (size_t)first, (size_t)count * 20, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(s, hipStreamSynchronize(s->stream));
   return WX_OK;
@@ -2566,6 +2576,12 @@ void *wx_device_ptr(wx_sim *s, int field)
   if (field == WX_FIELD_EMITTED) return emitted_rect(s, 0, 0, s->X, s->Y) == WX_OK ? s->emitted : nullptr; // (whole grid, computed now)
   const void *ptr;
   int ch, el;
+  // baseTexture_1 of the marching wet kernel's display iteration is assembled from base_0 / wall_0 when it is asked for (field_info): a
+  // caller that gets one of the two writable may change it, so the texture is assembled whole NOW and is a stored one from here on
+  if ((field == WX_FIELD_BASE_CUR || field == WX_FIELD_WALL_CUR) && s->run.ran_fused && s->run.disp_lazy) {
+    if (field_info(s, WX_FIELD_BASE_DISP, &ptr, &ch, &el) || hipStreamSynchronize(s->stream) != hipSuccess) return nullptr; // (done before the caller's first write, whatever stream it is on)
+    s->run.disp_lazy = false;
+  }
   if (field_info(s, field, &ptr, &ch, &el)) return nullptr;
   // (the caller may write velocities through the pointer: devtools.seed_flow does. Rank-LOCAL knowledge: it must not change which collectives
   // this rank enqueues -- ADVICE round 5 -- so it only makes the next exchange's roll look at the state, with the period's bound checked)

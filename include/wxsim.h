@@ -92,7 +92,9 @@ enum {
   WX_FIELD_LIGHTNING = 12, /* 1x1 RGBA32F lightningDataTexture */
   /* RGBA16F emittedLight: the lighting pass's second render target (app.js:838, 5283, 5294; lightingShader.frag:15, 60-78,
    * 98-101, 143-166), read only by the renderer's ambient-light pyramid (app.js:6096). Not stored per iteration: computed for
-   * the requested rectangle when read, from what the most recent lighting pass sampled (zero before the first one). */
+   * the requested rectangle when read, from what the most recent lighting pass sampled (zero before the first one). The inputs of
+   * that pass live until the next iteration: after a step whose last iteration ran WITHOUT the lighting pass (pass_mask) the field
+   * reads zero, where the reference's texture would still show the last image drawn. */
   WX_FIELD_EMITTED = 13,
   WX_FIELD_COUNT = 14
 };
@@ -281,7 +283,8 @@ int wx_set_iter(wx_sim *s, int64_t iter);
 int wx_read_rect(wx_sim *s, int field, int x, int y, int w, int h, void *dst, int dtype);
 
 /* Replaces gl.getBufferSubData on the transform-feedback buffers (app.js:5019, 5086, 6597):
- * 5 floats per droplet (pos.xy, mass.xy, density) from the destination buffer of the last step. */
+ * 5 floats per droplet (pos.xy, mass.xy, density) from the destination buffer of the last step. A blocking call like wx_read_rect:
+ * whatever the iterations have to report (WX_E_STATE: an overflowed exact-path list, ...) is reported here instead of droplets. */
 int wx_read_particles(wx_sim *s, int first, int count, float *dst);
 
 /* Field streaming for a display consumer: what the reference's renderer binds every frame (app.js:6081-6219)
@@ -316,6 +319,9 @@ void *wx_device_ptr(wx_sim *s, int field);          /* device address of a field
                                                      * WX_FIELD_PRECIP_FB and (after the marching wet kernel, round 6) WX_FIELD_BASE_DISP are
                                                      * stored in another form (planes / on demand / three channels / post-advection P only): the
                                                      * pointer is to the RGBA texture made at the time of the call, valid until the next wx_step.
+                                                     * WX_FIELD_BASE_CUR / _WALL_CUR may be written through: the on-demand WX_FIELD_BASE_DISP,
+                                                     * which is assembled from them, is made whole first, so a later read still shows the last
+                                                     * display iteration's texture, not the host's edit.
                                                      * Slabs: velocities written through WX_FIELD_BASE_CUR are looked at by the next exchange
                                                      * (a |vx| beyond the current period's bound is REPORTED, WX_E_STATE); only wx_upload /
                                                      * wx_setup_* re-size the first period -- and on the slabs of an initialised ring those are

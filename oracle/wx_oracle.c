@@ -579,7 +579,10 @@ void wxo_boundary(const wxo_params *p, const float *initial_T, float iterNum, co
                 }
               }
               const int subInterval = iterI / 100;
-              if (subInterval % ((int)(w[SOIL_MOISTURE] * 0.1f + w[SNOW] * 0.5f) + 10) == 0 &&
+              /* (soil moisture / snow far below zero -- a wall brush can leave them there -- make the divisor 0: undefined in GLSL as
+               * above -> false; on the CPU the division would trap) */
+              const int fireDivisor = (int)(w[SOIL_MOISTURE] * 0.1f + w[SNOW] * 0.5f) + 10;
+              if (fireDivisor != 0 && subInterval % fireDivisor == 0 &&
                   wl[VEGETATION] >= 20 &&
                   (wL[TYPE] == WALLTYPE_FIRE || wR[TYPE] == WALLTYPE_FIRE || waterX0Yp[SMOKE] > 4.5f)) {
                 wl[TYPE] = WALLTYPE_FIRE;

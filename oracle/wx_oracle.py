@@ -192,6 +192,11 @@ class OracleSim:
         ct = C.c_float if dt == np.float32 else C.c_int8
         return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), (self.Y, self.X, ch))
 
+    def set_lightning(self, v):
+        """The lightning data texture replaced from outside (the counterpart of wx_lightning_set)."""
+        ptr = lib().wxo_field(self._h, 12)
+        np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), (4,))[:] = np.asarray(v, np.float32)
+
     def field(self, name: str) -> np.ndarray:
         if name == "LIGHTNING":
             ptr = lib().wxo_field(self._h, 12)

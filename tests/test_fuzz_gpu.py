@@ -1,6 +1,7 @@
-"""The differential fuzzer (tools/fuzz_parity.py) as a bounded test: a fixed seed's first cases in both modes -- one handle against the CPU
-oracle, N slabs against one handle, bit for bit -- and the recipes of what the fuzzer found in round 6 (tests/golden/fuzz_group_regressions.json:
-data, i.e. the drawn parameters of those cases)."""
+"""The differential fuzzer (tools/fuzz_parity.py) as a bounded test: a fixed seed's first cases in its modes -- one handle against the CPU
+oracle, N slabs against one handle, one handle against the oracle through a drawn HOST SCRIPT (reads in any order, options / parameters /
+iteration counter changed mid-run, placement searches and device-side writes between steps), bit for bit -- and the recipes of what the
+fuzzer found (tests/golden/fuzz_group_regressions.json, fuzz_script_regressions.json: data, i.e. the drawn parameters of those cases)."""
 import json
 import os
 import sys
@@ -11,6 +12,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+SCRIPT_CASES = 200
 
 
 @pytest.fixture(scope="module")
@@ -56,3 +60,35 @@ def test_fuzz_regressions_of_round_6(pkg, fuzz):
         bad, info = fuzz.run_group_case(pkg, pkg.engine, r["recipe"])
         assert not info.get("error"), info
         assert not bad, json.dumps({"recipe": r["recipe"], "mismatches": bad})
+
+
+@pytest.mark.parametrize("seed", [13, 14])
+def test_fuzz_host_scripts_against_the_oracle(pkg, oracle, fuzz, seed):
+    """--mode script: the scenes of the seed's oracle mode, each driven through a host script drawn from a generator of its own. Every
+    kind of host action occurs at least ten times over the run (the runner counts what it performed)."""
+    rng, rng_script = np.random.default_rng(seed), np.random.default_rng(seed + 2000003)
+    compared, reads, actions = 0, 0, {k: 0 for k in fuzz.SCRIPT_ACTIONS}
+    for k in range(SCRIPT_CASES):
+        c = fuzz.draw_script(rng_script, fuzz.draw_case(rng, 250000))
+        bad, info = fuzz.run_script_case(pkg, pkg.engine, oracle, c)
+        for kind, n in info["actions"].items():
+            actions[kind] += n
+        if info.get("error") or info.get("blown_up"):
+            continue
+        compared += 1
+        reads += info["reads"]
+        assert not bad, json.dumps({"mode": "script", "seed": seed, "case": k, "recipe": c, "mismatches": bad})
+    assert compared >= SCRIPT_CASES * 4 // 5, compared
+    assert reads >= 20 * compared, (reads, compared)
+    assert min(actions.values()) >= 10, actions
+
+
+def test_fuzz_script_regressions(pkg, oracle, fuzz):
+    """What --mode script found: BASE_DISP after a device-side write to BASE_CUR, the feedback texture's alpha after the particles
+    were switched off."""
+    recs = json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_script_regressions.json")))
+    assert len(recs) >= 2
+    for r in recs:
+        bad, info = fuzz.run_script_case(pkg, pkg.engine, oracle, r["recipe"])
+        assert not info.get("error") and not info.get("blown_up"), info
+        assert not bad, json.dumps({"why": r["why"], "mismatches": bad})

@@ -5,13 +5,31 @@ flow speed (up to several cells per iteration: the exact paths), humidity / clou
 the reference's GUI offers), pass mask (all passes / the dry stencil), brush tool and airplane inputs, droplets in deterministic splat
 order, the way a host cuts its iterations into steps, dry pairs on / off, row bands, waterTexture_0 on demand / stored. --mode group: the same
 scenes cut into 2 .. 8 column slabs on this one GPU (the library's own halo exchange, random halo widths, overlapped / split / in-order
-protocol, droplet pool in exact mode) against the undecomposed handle, bit for bit.
+protocol, droplet pool in exact mode) against the undecomposed handle, bit for bit. --mode script: the scenes of oracle mode, but the HOST'S
+CALL SEQUENCE is drawn as well (draw_script, from a generator of its own) -- 2 .. 5 steps, some cut into a WX_OVERLAP_MORE_TO_COME piece and
+the rest, and between them any of SCRIPT_ACTIONS:
+    read        a random subset (possibly empty) of all readable fields in random order, whole or a sub-rectangle, some twice in a row
+                (both wall dtypes, EMITTED as binary16, VORT while the per-pass set ran, PRECIP_FB / PRECIP_DEP / LIGHTNING on every grid)
+    particles   a range of the droplet pool                     stream      wx_stream_frame of a viewport == wx_read_rect of its fields
+    option      KERNEL_SET, DRY_KERNEL, DRY_PAIRS, ROW_BANDS, WATER0_ON_DEMAND, CHECK_LAUNCHES, SPLAT_ORDER (stays 1) at any point
+    params      sliders / sun angle / another initial_T row / brush / airplane / pass mask dry <-> all / precipitation / wrap
+    iter        wx_set_iter on and next to multiples of 20, 100, 600      step0       a step of no iterations
+    tune        wx_tune_placement(1-2 tries, 1-3 iterations): counter, every field, droplets, lightning and wx_pair_stats unchanged
+    devwrite    devtools.seed_flow / seed_vortices / a torch write through wx_device_ptr(BASE_CUR), mirrored into the oracle's state;
+                every field is compared afterwards (BASE_DISP and WATER_0 belong to the last display iteration, not to the edit)
+    reupload    the current state uploaded again (droplets too)          lightning   wx_lightning_set, mirrored
+    pair_stats, fastest, water_free, sync, profile (on / off + read)      calls with side effects, interleaved
+After the last step everything is read. Fields are compared where both sides define them alike (CURL / VORT / EMITTED after a step that
+ran the passes that store them). The recipe, script included, is printed and flushed BEFORE the case runs and reproduces the case alone.
+A WxError other than the exact path's reported overflow is not expected: the run ends there (exit 2). This is not a tool to provoke
+faults with: run it under `timeout`, and find the cause of a fault or hang from the recipe before starting the case again.
 
-    python tools/fuzz_parity.py [--seed S] [--cases N] [--seconds T] [--max-cells C]
+    python tools/fuzz_parity.py [--mode M] [--seed S] [--cases N] [--seconds T] [--max-cells C] [--only K] [--override JSON] [--check-launches]
 
 Every case prints one line; a mismatch prints the case's recipe (the seed reproduces it: --seed S --only K) and the run exits 1 at the
 end. The oracle is the checker (test infrastructure); nothing here is a product path."""
 import argparse
+import importlib
 import json
 import os
 import sys
@@ -233,6 +251,307 @@ def case_steps(pkg, E, wx_oracle, c):
     return bad, info
 
 
+# ---- --mode script: the HOST's call sequence is drawn too (everything above draws the scene and runs one fixed script) ----
+SCRIPT_FIELDS = ["BASE_CUR", "BASE_DISP", "WATER_0", "WATER_CUR", "WALL_CUR", "WALL_DISP", "WALL_CUR:i32", "WALL_DISP:i32", "LIGHT_0", "LIGHT_1", "CURL", "VORT",
+                 "PRECIP_FB", "PRECIP_DEP", "LIGHTNING", "EMITTED"]
+SCRIPT_OPTIONS = ["KERNEL_SET", "DRY_KERNEL", "DRY_PAIRS", "ROW_BANDS", "WATER0_ON_DEMAND", "CHECK_LAUNCHES", "SPLAT_ORDER"]
+# the action kinds a script is made of (run_script_case counts every one it performs, under these names)
+SCRIPT_ACTIONS = ["read", "particles", "stream", "option", "params", "iter", "tune", "devwrite", "reupload", "pair_stats", "fastest", "water_free", "sync",
+                  "profile", "lightning", "step0", "pieces"]
+EXPECTED_ERROR = "the exact path holds"  # the one WxError a drawn scene may run into (a blown-up flow overflows the exact path's list): reported, nothing to compare
+
+
+def _draw_rect(rng, X, Y):
+    x0, y0 = int(rng.integers(0, X)), int(rng.integers(0, Y))
+    return [x0, y0, int(rng.integers(1, X - x0 + 1)), int(rng.integers(1, Y - y0 + 1))]
+
+
+def _draw_reads(rng, c):
+    """A random subset (possibly empty) of the readable fields in random order; each whole or a sub-rectangle, some twice in a row."""
+    names = [SCRIPT_FIELDS[i] for i in rng.permutation(len(SCRIPT_FIELDS))[:int(rng.integers(0, len(SCRIPT_FIELDS) + 1))]]
+    return [{"field": f, "rect": _draw_rect(rng, c["X"], c["Y"]) if rng.random() < 0.3 else None, "twice": bool(rng.random() < 0.15)} for f in names]
+
+
+def _draw_action(rng, c, kind):
+    a = {"op": kind}
+    if kind == "read":
+        a["reads"] = _draw_reads(rng, c)
+    elif kind == "particles":
+        first = int(rng.integers(0, max(1, c["drops"])))
+        a.update(first=first, count=int(rng.integers(0, max(1, c["drops"] - first + 1))))
+    elif kind == "stream":
+        a["rect"] = _draw_rect(rng, c["X"], c["Y"])
+    elif kind == "option":
+        o = str(rng.choice(SCRIPT_OPTIONS))
+        a.update(opt=o, value=int(rng.integers(0, 3)) if o == "ROW_BANDS" else (1 if o == "SPLAT_ORDER" else int(rng.integers(0, 2))))
+    elif kind == "params":  # the changes are applied, in this order, to the parameters in force (see _script_uniforms)
+        ch = {}
+        what = rng.choice(["sliders", "sun", "lapse", "brush", "airplane", "mask", "precip", "wrap"], size=int(rng.integers(1, 4)), replace=False)
+        for w in what:
+            if w == "sliders":
+                ch["sliders"] = {k: float(rng.uniform(*SLIDERS[k])) for k in SLIDERS if rng.random() < 0.25}
+            elif w == "sun":
+                ch["sun"] = float(rng.uniform(-30.0, 210.0))
+            elif w == "lapse":  # another initial_T row
+                ch["lapse"] = float(rng.uniform(6.0, 11.0))
+            elif w == "brush":
+                ch["brush"] = None if rng.random() < 0.5 else {"type": int(rng.integers(0, 24)), "values": [float(rng.random()), float(rng.random()), float(rng.uniform(-1, 1)), float(rng.uniform(1, 30))],
+                                                                "move": [float(rng.uniform(-0.02, 0.02)), float(rng.uniform(-0.02, 0.02))]}
+            elif w == "airplane":
+                ch["airplane"] = None if rng.random() < 0.5 else [float(rng.random()), float(rng.random()), float(rng.random()), float(rng.choice([-1.0, 0.0, 1.0]))]
+            elif w == "mask":
+                ch["dry"] = bool(rng.random() < 0.5)
+            elif w == "precip":
+                ch["precip"] = int(rng.random() < 0.5)
+            else:
+                ch["wrap"] = bool(rng.random() < 0.7)
+        a["change"] = ch
+    elif kind == "iter":  # on and next to the boundary pass's % 20 / % 100 schedules and the % 600 of the droplets, odd and even
+        a["value"] = int(rng.choice([20, 100, 600, 1200, 12340]) * int(rng.integers(1, 4)) + int(rng.integers(-2, 3)))
+    elif kind == "tune":
+        a.update(tries=int(rng.integers(1, 3)), iters=int(rng.integers(1, 4)))
+    elif kind == "devwrite":
+        a.update(how=str(rng.choice(["eddies", "noise", "vortices", "scale"])), sigma=float(rng.choice([0.05, 0.2, 0.5])), seed=int(rng.integers(1, 1000)))
+    elif kind == "profile":
+        a["on"] = bool(rng.random() < 0.6)
+    elif kind == "lightning":
+        a["v"] = [float(rng.random()), float(rng.random()), float(rng.integers(0, 2000)), float(rng.random())]
+    return a
+
+
+def draw_script(rng, c):
+    """The host script of --mode script for the case ``c`` of draw_case: 2 .. 5 steps and, in front of each and after the last, a random
+    list of host actions (SCRIPT_ACTIONS). ``rng`` is a generator of ITS OWN, not draw_case's: the scene sequence of a seed is the same
+    in every mode. The script becomes part of the recipe (c["script"]); run_script_case reads everything after the last step by itself."""
+    kinds = [k for k in SCRIPT_ACTIONS if k != "pieces" and (c["drops"] or k != "particles")]
+    weight = {"read": 6.0, "option": 3.0, "params": 3.0, "stream": 1.5, "iter": 1.5, "tune": 0.7, "devwrite": 1.0, "reupload": 0.7, "particles": 4.0}
+    p = np.array([weight.get(k, 1.0) for k in kinds])
+    script = []
+    n_steps = int(rng.integers(2, 6))
+    for k in range(n_steps + 1):
+        for kind in rng.choice(kinds, size=int(rng.integers(0, 5)), p=p / p.sum()):
+            script.append(_draw_action(rng, c, str(kind)))
+        if k < n_steps:
+            n = int(rng.integers(1, 9))
+            script.append({"op": "step", "n": n, "first_piece": int(rng.integers(1, n)) if n > 1 and rng.random() < 0.3 else 0})
+    c["script"] = script
+    c["steps"] = [a["n"] for a in script if a["op"] == "step"]
+    return c
+
+
+def _script_uniforms(pkg, c, st):
+    """The uniforms of the parameters in force: build_case's, with what the script's "params" actions changed since (``st``)."""
+    P = pkg.params
+    gui = P.merge_settings(None)
+    gui.update(st["sliders"])
+    gui["sunAngle"] = st["sun"]
+    gui["wrapHorizontally"] = st["wrap"]
+    if st["lapse"] is not None:
+        gui["dryLapseRate"] = st["lapse"]
+    u = P.uniforms_from_gui(gui, c["Y"], quad_scale=c["quad_scale"], pass_mask=P.PASS_DRY if st["dry"] else P.PASS_ALL)
+    u["enablePrecipitation"] = 1 if (c["drops"] and st["precip"]) else 0
+    if st["brush"]:
+        u["userInputType"] = st["brush"]["type"]
+        u["userInputValues"] = tuple(st["brush"]["values"])
+        u["userInputMove"] = tuple(st["brush"]["move"])
+    if st["airplane"]:
+        u["airplaneValues"] = tuple(st["airplane"])
+    if c["drops"]:
+        u["splat_order"] = 1
+        u["spawnChanceMult"] = 0.01
+    return u
+
+
+def _diff(field, a, b, it):
+    ne = (a != b) & ~(np.isnan(a.astype(np.float64)) & np.isnan(b.astype(np.float64)))
+    idx = np.argwhere(ne)
+    return {"field": field, "after_iterations": it, "values": int(ne.sum()), "first": [int(v) for v in idx[0][::-1]] if len(idx) else None}
+
+
+def run_script_case(pkg, E, wx_oracle, c):
+    """--mode script: one handle against the oracle through the host script c["script"] (draw_script). Returns (mismatches, info);
+    info["actions"] counts the actions performed per kind, info["reads"] the field comparisons made. A WxError other than the exact
+    path's reported overflow is NOT expected: it propagates (the caller stops the run there)."""
+    X, Y = c["X"], c["Y"]
+    base, water, wall, u, drops = build_case(pkg, c)
+    nd = 0 if drops is None else len(drops)
+    st = {"sliders": dict(c["sliders"]), "sun": c["sun"], "wrap": c["wrap"], "lapse": None, "dry": c["dry"], "precip": 1, "brush": c["brush"], "airplane": c["airplane"]}
+    u = _script_uniforms(pkg, c, st)
+    h = E.Handle(X, Y, nd)
+    o = wx_oracle.OracleSim(X, Y, nd)
+    bad, count, n_reads = [], {k: 0 for k in SCRIPT_ACTIONS}, 0
+    # what the LAST step ran decides which display-side fields mean the same on both sides: curl / vorticity are stored by the
+    # iterations that run those passes (vorticity by the per-pass kernels only), the emitted-light image is made from what the last
+    # lighting pass sampled (include/wxsim.h: zero once an iteration without that pass has run)
+    last = {"stepped": False, "all": False, "per_pass": False, "lit_ever": False}
+    kernel_set = c["kernel_set"]
+
+    iters_done = 0
+
+    def done():
+        return iters_done
+
+    def expect(field, rect):
+        """(handle's array, oracle's array) of a read, or None where the two sides are not defined alike right now."""
+        name, _, dt = field.partition(":")
+        if name == "VORT" and not (last["stepped"] and last["all"] and last["per_pass"]):
+            return None
+        if name == "CURL" and last["stepped"] and not last["all"]:
+            return None
+        if name == "EMITTED" and last["lit_ever"] and not last["all"]:
+            return None
+        if name == "LIGHTNING":
+            return h.read_rect("LIGHTNING"), o.field("LIGHTNING")
+        x0, y0, w, hh = rect if rect else (0, 0, X, Y)
+        b = o.field(name)[y0:y0 + hh, x0:x0 + w]
+        if name == "EMITTED":
+            b = b.astype(np.float16)
+        if dt:
+            return h.read_rect(name, x0, y0, w, hh, int32=True), b.astype(np.int32)
+        return h.read_rect(name, x0, y0, w, hh), b
+
+    def compare(field, rect=None, why="read"):
+        nonlocal n_reads
+        ab = expect(field, rect)
+        if ab is None:
+            return
+        n_reads += 1
+        if ab[0].dtype != ab[1].dtype or not np.array_equal(ab[0], ab[1], equal_nan=True):
+            bad.append(dict(_diff(field, ab[0], ab[1], done()), rect=rect, during=why))
+
+    def compare_everything(why):
+        for f in SCRIPT_FIELDS:
+            compare(f, None, why)
+        if nd and not np.array_equal(h.read_particles(), o.field("DROPS"), equal_nan=True):
+            bad.append({"field": "DROPS", "after_iterations": done(), "during": why})
+
+    def set_params():
+        nonlocal u
+        u = _script_uniforms(pkg, c, st)
+        h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"])
+        o.set_params(u)
+
+    try:
+        h.upload(base, water, wall, drops)
+        o.upload(base, water, wall, drops)
+        set_params()
+        h.iter = o.iter = c["iter0"]
+        for k, v in (("DRY_PAIRS", c["pairs"]), ("ROW_BANDS", c["bands"]), ("KERNEL_SET", c["kernel_set"]), ("DRY_KERNEL", c["dry_kernel"]), ("WATER0_ON_DEMAND", c["water0_on_demand"])):
+            h.set_option(getattr(h, "OPT_" + k), v)
+        if nd:
+            h.set_option(h.OPT_SPLAT_ORDER, 1)
+        for a in c["script"]:
+            op = a["op"]
+            if op == "step":
+                n, k1 = a["n"], a.get("first_piece", 0)
+                if k1:  # the step cut into two pieces, the first with WX_OVERLAP_MORE_TO_COME (its last iteration stores no display-side field)
+                    h.step(k1, 4)
+                    h.step(n - k1)
+                    count["pieces"] += 1
+                else:
+                    h.step(n)
+                o.step(n)
+                iters_done += n
+                last.update(stepped=True, all=not st["dry"], per_pass=not kernel_set)
+                last["lit_ever"] = last["lit_ever"] or not st["dry"]
+                if c.get("verify_steps"):  # (--override '{"verify_steps": true}': everything after every step -- narrows a mismatch down to the step it begins in)
+                    compare_everything("step")
+                    if bad:
+                        break
+                continue
+            if op == "particles" and not nd:
+                continue
+            count[op] += 1
+            if op == "read":
+                for r in a["reads"]:
+                    for _ in range(2 if r["twice"] else 1):
+                        compare(r["field"], r["rect"])
+            elif op == "particles":
+                d, d_ref = h.read_particles(a["first"], a["count"]), o.field("DROPS")[a["first"]:a["first"] + a["count"]]
+                if not np.array_equal(d, d_ref, equal_nan=True):
+                    k = int(np.argwhere((d != d_ref) & ~(np.isnan(d) & np.isnan(d_ref)))[0][0])
+                    bad.append({"field": "DROPS", "range": [a["first"], a["count"]], "after_iterations": done(), "first": a["first"] + k, "handle": d[k].tolist(), "oracle": d_ref[k].tolist(),
+                                "whole_pool_equal": bool(np.array_equal(h.read_particles(), o.field("DROPS"), equal_nan=True))})
+            elif op == "stream":  # the streamed frame of a viewport == wx_read_rect of the same fields (those are compared with the oracle elsewhere)
+                x0, y0, w, hh = a["rect"]
+                h.stream_frame(x0, y0, w, hh)
+                fr = {k: v.copy() for k, v in h.stream_wait().items()}
+                for f, v in fr.items():
+                    if not np.array_equal(v, h.read_rect(f, x0, y0, w, hh), equal_nan=True):
+                        bad.append({"field": f + " streamed", "rect": a["rect"], "after_iterations": done()})
+            elif op == "option":
+                if a["opt"] == "SPLAT_ORDER" and not nd:
+                    continue
+                h.set_option(getattr(h, "OPT_" + a["opt"]), a["value"])
+                if a["opt"] == "KERNEL_SET":
+                    kernel_set = a["value"]
+            elif op == "params":
+                st.update({k: (dict(st["sliders"], **v) if k == "sliders" else v) for k, v in a["change"].items()})
+                set_params()
+            elif op == "iter":
+                h.iter = o.iter = a["value"]
+            elif op == "tune":  # state, iteration counter, every field and the pair counters are what they were (the oracle never moved)
+                h.pair_stats()
+                it = h.iter
+                h.tune_placement(a["tries"], a["iters"])
+                if h.iter != it:
+                    bad.append({"field": "iter", "during": "tune", "before": it, "after": h.iter})
+                ps = h.pair_stats()
+                if ps != (0, 0):
+                    bad.append({"field": "pair_stats", "during": "tune", "after": list(ps)})
+                if not np.array_equal(h.lightning(), o.field("LIGHTNING")):
+                    bad.append({"field": "lightning()", "during": "tune"})
+                compare_everything("tune")
+            elif op == "devwrite":  # the host edits velocities in place on the device (wx_device_ptr); the oracle gets the same BASE_CUR
+                D = importlib.import_module(pkg.__name__ + ".devtools")
+                if a["how"] == "vortices" and X >= 48 and Y >= 48:
+                    D.seed_vortices(h, 2, peak=1.0 + a["sigma"], radius=2.5, seed=a["seed"])
+                elif a["how"] == "scale":
+                    h.sync()
+                    D.field_tensor(h, "BASE_CUR")[1:, :, :2] *= 0.5
+                    D.torch.cuda.synchronize()
+                else:
+                    D.seed_flow(h, a["sigma"], seed=a["seed"], kind="noise" if a["how"] == "noise" else "eddies")
+                o.view("BASE_CUR")[...] = h.read_rect("BASE_CUR")
+                compare_everything("devwrite")
+            elif op == "reupload":
+                state = [o.field(f) for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR")] + ([o.field("DROPS")] if nd else [])
+                h.upload(*state)
+                o.upload(*state)
+                last.update(stepped=False, all=False, per_pass=False, lit_ever=False)
+            elif op == "pair_stats":
+                h.pair_stats()
+            elif op == "fastest":
+                h.fastest_velocity()
+            elif op == "water_free":
+                h.water_free()
+            elif op == "sync":
+                h.sync()
+            elif op == "profile":
+                h.profile(a["on"])
+                h.profile_read()
+            elif op == "lightning":
+                h.set_lightning(a["v"])
+                o.set_lightning(a["v"])
+            elif op == "step0":  # (a step of no iterations still prepares the kernel set's layout of the light textures)
+                h.step(0)
+            if bad:
+                break
+        if not bad:
+            compare_everything("end")
+        ob = o.field("BASE_CUR")
+        info = {"blown_up": not bool(np.isfinite(ob).all() and np.isfinite(o.field("WATER_CUR")).all() and np.abs(ob[..., :2]).max() < 1e4), "fastest": float(h.fastest_velocity()),
+                "actions": count, "reads": n_reads}
+    except E.WxError as e:
+        if EXPECTED_ERROR not in str(e):
+            raise
+        return [], {"error": str(e), "actions": count, "reads": n_reads}
+    finally:
+        h.close()
+        o.close()
+    return bad, info
+
+
 def draw_group(rng, c):
     """Extra draws of --mode group (after draw_case, so the scene sequence of a seed is the same in both modes)."""
     n = int(rng.choice([2, 2, 3, 4, 4, 5, 6, 8]))
@@ -373,7 +692,8 @@ def main():
     ap.add_argument("--max-cells", type=int, default=600000)
     ap.add_argument("--interleave", action="store_true", help="oracle mode: half of the cases run with a second handle alive, steps in turn")
     ap.add_argument("--big", action="store_true", help="grids of 1000-9000 x 512-2100 cells (use with --max-cells 8000000)")
-    ap.add_argument("--mode", choices=["oracle", "group", "setup"], default="oracle", help="oracle: one handle against the CPU oracle; group: N slabs against one handle")
+    ap.add_argument("--mode", choices=["oracle", "group", "setup", "script"], default="oracle",
+                    help="oracle: one handle against the CPU oracle; group: N slabs against one handle; script: one handle against the oracle through a drawn host script")
     ap.add_argument("--only", type=int, default=-1, help="run only case K of the seed's sequence")
     ap.add_argument("--first", type=int, default=0, help="skip the cases before this one (they are still drawn: same sequence)")
     ap.add_argument("--last", type=int, default=1 << 30)
@@ -389,12 +709,16 @@ def main():
     wx_oracle.build()
     rng = np.random.default_rng(a.seed)
     rng_il = np.random.default_rng(a.seed + 1000003)  # (companions come from a sequence of their own: --seed S --only K still reproduces case K alone)
+    rng_script = np.random.default_rng(a.seed + 2000003)  # (host scripts too: the scenes of --mode script are those of --mode oracle)
+    totals = {k: 0 for k in SCRIPT_ACTIONS}
     t0 = time.time()
-    failures, ran, reported = [], 0, 0
+    failures, ran, reported, compared = [], 0, 0, 0
     for k in range(a.cases):
         c = draw_case(rng, a.max_cells, a.big)
         if a.mode == "group":
             c = draw_group(rng, c)
+        if a.mode == "script":
+            c = draw_script(rng_script, c)
         if (a.only >= 0 and k != a.only) or k < a.first:
             continue
         if k > a.last:
@@ -410,10 +734,20 @@ def main():
             if bad2 and not info2.get("blown_up"):
                 failures.append({"case": k, "interleaved_with": c, "recipe": c2, "mismatches": bad2})
                 print("MISMATCH in the interleaved companion:", json.dumps(failures[-1]), flush=True)
+        elif a.mode == "script":
+            print(f"case {k} recipe: {json.dumps(c)}", flush=True)  # BEFORE it runs: a case that faults or hangs leaves its recipe behind
+            try:
+                bad, info = run_script_case(pkg, E, wx_oracle, c)
+            except E.WxError as e:  # not the reported overflow of a blown-up scene: the run ends here (no retry, nothing further on the GPU)
+                print(f"case {k}: UNEXPECTED ERROR {e}", flush=True)
+                sys.exit(2)
+            for kind, n in info["actions"].items():
+                totals[kind] += n
         else:
             bad, info = run_case(pkg, E, wx_oracle, c) if a.mode == "oracle" else (run_group_case(pkg, E, c) if a.mode == "group" else run_setup_case(pkg, E, c))
         ran += 1
         reported += 1 if info.get("error") else 0
+        compared += 0 if (info.get("error") or info.get("blown_up")) else 1
         if bad and info.get("blown_up"):  # NaN / inf / |v| > 1e4 cells per iteration (the reference blows up the same way): float -> int conversions out of range differ between CPU and GPU
             print(f"case {k}: state not finite, {len(bad)} fields differ -- not counted", flush=True)
             bad = []
@@ -423,8 +757,8 @@ def main():
         if bad:
             failures.append({"case": k, "recipe": c, "mismatches": bad})
             print(json.dumps(failures[-1]), flush=True)
-    print(json.dumps({"mode": a.mode, "seed": a.seed, "cases_run": ran, "mismatching_cases": len(failures), "cases_ending_in_a_reported_error": reported,
-                      "seconds": round(time.time() - t0, 1)}))
+    print(json.dumps(dict({"mode": a.mode, "seed": a.seed, "cases_run": ran, "cases_compared": compared, "mismatching_cases": len(failures),
+                           "cases_ending_in_a_reported_error": reported, "seconds": round(time.time() - t0, 1)}, **({"actions": totals} if a.mode == "script" else {}))))
     sys.exit(1 if failures else 0)
 
 
