@@ -823,3 +823,22 @@ int wx_group_sync(wx_group *g)
   }
   return WX_OK;
 }
+
+// every slab's passes are enqueued on its own device and stream first, then collected: the slabs run next to each other
+int wx_group_diagnostics(wx_group *g, wx_diag *out)
+{
+  if (!g || !out) return WX_E_INVALID;
+  for (wx_sim *s : g->slab) {
+    DeviceScope ds(s);
+    if (int rc = gpass(g, s, diag_enqueue(s))) return rc;
+  }
+  wx_diag_raw all;
+  memset(&all, 0, sizeof(all));
+  for (wx_sim *s : g->slab) {
+    DeviceScope ds(s);
+    wx_diag_raw part;
+    if (int rc = gpass(g, s, diag_complete(s, &part))) return rc;
+    if (wxd::diag_merge(&all, &part) != WX_OK) return gfail(g, WX_E_STATE, "wx_group_diagnostics: the slabs disagree about geometry or iteration (slab at x0 = %d: iteration %lld)", s->x0, (long long)s->run.iter);
+  }
+  return wxd::diag_finish(&all, out);
+}

@@ -11,6 +11,7 @@
 #include "wx_march.h"
 #include "wx_march2.h"
 #include "wx_kernels.h"
+#include "wx_diag.h"
 
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -324,6 +325,9 @@ struct wx_sim {
   float3 *fb = nullptr;      // precipitationFeedbackTexture stored with its three used channels (12-byte texels); RGBA on demand: fb_rgba
   float4 *fb_rgba = nullptr; // (not in the placement blocks: allocated by the first reader of WX_FIELD_PRECIP_FB)
   half4 *emitted = nullptr;  // RGBA16F, allocated by the first read
+  // diagnostics (wx_diag.h): the device table and its pinned host copy, allocated by the first wx_diag_collect (not in the placement
+  // blocks: nothing an iteration touches)
+  unsigned long long *diag_table = nullptr, *diag_host = nullptr;
   float *drops[2] = {nullptr, nullptr};
   float *initial_T = nullptr, *snd_T = nullptr, *snd_W = nullptr, *snd_Vel = nullptr;
   DevState *state = nullptr;
@@ -1323,6 +1327,8 @@ void wx_destroy(wx_sim *s)
   hipFree(s->split.sync_words);
   hipFree(s->emitted);
   hipFree(s->fb_rgba);
+  hipFree(s->diag_table);
+  if (s->diag_host) hipHostFree(s->diag_host);
   water0_scratch_free(s);
   hipFree(s->w0.initT);
   hipFree(s->det_tmp);
@@ -2469,6 +2475,77 @@ int wx_read_particles(wx_sim *s, int first, int count, float *dst)
   HIPCHK(s, hipMemcpyAsync(dst, s->drops[s->run.drop_cur] + 5 * (size_t)first, (size_t)count * 20, hipMemcpyDeviceToHost, s->stream));
   HIPCHK(s, hipStreamSynchronize(s->stream));
   return WX_OK;
+}
+
+// ---- diagnostics (include/wxsim.h: wx_diag; kernels and the pure host functions: wx_diag.h) ----
+// the device passes + the copy of the table, enqueued on the compute stream behind the pending iterations; reads base[0], water[1],
+// wall[0] and the current droplet buffer as they stand (no field_info: nothing that is made on demand is made or dropped here)
+static int diag_enqueue(wx_sim *s)
+{
+  if (!s->uploaded) return fail(s, WX_E_STATE, "wx_diag_collect before wx_upload");
+  if ((unsigned long long)s->Xg * (unsigned long long)s->Y >= 0xFFFFFFFFull)
+    return fail(s, WX_E_INVALID, "wx_diag_collect: %d x %d cells: global cell indices are 32 bits wide", s->Xg, s->Y);
+  settle_edges(s);
+  wait_unpacked(s); // (ghost columns are not read, but the droplet pool and a split iteration's edge strips are)
+  if (int rc = validate_ghost_flag(s)) return rc;
+  const size_t bytes = (size_t)wxd::SHARDS * wxd::T_WORDS * sizeof(unsigned long long);
+  if (!s->diag_table) {
+    if (hipMalloc((void **)&s->diag_table, bytes) != hipSuccess) {
+      s->diag_table = nullptr;
+      return fail(s, WX_E_NOMEM, "wx_diag_collect: the device table");
+    }
+    if (hipHostMalloc((void **)&s->diag_host, bytes) != hipSuccess) {
+      s->diag_host = nullptr;
+      hipFree(s->diag_table);
+      s->diag_table = nullptr;
+      return fail(s, WX_E_NOMEM, "wx_diag_collect: the pinned copy of the table");
+    }
+  }
+  HIPCHK(s, hipMemsetAsync(s->diag_table, 0, bytes, s->stream));
+  const int Xo = s->X - 2 * s->halo;
+  const unsigned chunks = (unsigned)((Xo + wxd::WG - 1) / wxd::WG) * (unsigned)s->Y;
+  hipLaunchKernelGGL(wxd::k_diag_cells, dim3(std::min<unsigned>(chunks, wxd::MAX_WGS)), dim3(wxd::WG), 0, s->stream, s->X, s->Y, s->halo, Xo, s->Xg, s->x0, s->base[0], s->water[1],
+                     s->wall[0], s->diag_table);
+  if (s->n_drops > 0) {
+    const unsigned wgs = std::min<unsigned>((unsigned)((s->n_drops + wxd::WG - 1) / wxd::WG), wxd::MAX_WGS);
+    hipLaunchKernelGGL(wxd::k_diag_drops, dim3(wgs), dim3(wxd::WG), 0, s->stream, s->geo, s->n_drops, s->halo, s->X - s->halo, s->drops[s->run.drop_cur], s->pool.remote,
+                       s->diag_table);
+  }
+  HIPCHK(s, hipGetLastError());
+  HIPCHK(s, hipMemcpyAsync(s->diag_host, s->diag_table, bytes, hipMemcpyDeviceToHost, s->stream));
+  return WX_OK;
+}
+static int diag_complete(wx_sim *s, wx_diag_raw *out)
+{
+  HIPCHK(s, hipStreamSynchronize(s->stream));
+  wxd::raw_from_table(s->diag_host, out);
+  out->x_global = s->Xg;
+  out->y_rows = s->Y;
+  out->iter = s->run.iter;
+  out->count[wxd::C_CELLS] = (int64_t)(s->X - 2 * s->halo) * s->Y;
+  return WX_OK;
+}
+
+int wx_diag_collect(wx_sim *s, wx_diag_raw *out)
+{
+  if (!s || !out) return WX_E_INVALID;
+  DeviceScope dev_scope(s);
+  if (int rc = diag_enqueue(s)) return rc;
+  return diag_complete(s, out);
+}
+int wx_diag_merge(wx_diag_raw *into, const wx_diag_raw *other) { return wxd::diag_merge(into, other); }
+int wx_diag_finish(const wx_diag_raw *raw, wx_diag *out) { return wxd::diag_finish(raw, out); }
+int wx_diag_accumulate(wx_diag_raw *into, int quantity, const float *values, size_t n) { return wxd::diag_accumulate(into, quantity, values, n); }
+int wx_diag_accumulate_cells(wx_diag_raw *into, int x_global, int y_rows, int x, int y, int n, const float *base, const float *water, const int8_t *wall)
+{
+  return wxd::diag_accumulate_cells(into, x_global, y_rows, x, y, n, base, water, wall);
+}
+int wx_diagnostics(wx_sim *s, wx_diag *out)
+{
+  if (!s || !out) return WX_E_INVALID;
+  wx_diag_raw raw;
+  if (int rc = wx_diag_collect(s, &raw)) return rc;
+  return wxd::diag_finish(&raw, out);
 }
 
 // ---- field streaming for display consumers ----

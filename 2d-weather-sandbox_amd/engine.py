@@ -40,7 +40,116 @@ EXPORTS = [
     "wx_comm_unique_id", "wx_comm_init", "wx_exchange", "wx_slab_step", "wx_group_create", "wx_group_destroy", "wx_group_last_error",
     "wx_group_count", "wx_group_transport", "wx_group_slab", "wx_group_agree", "wx_group_step", "wx_group_sync", "wx_group_set_option",
     "wx_group_exchange", "wx_slab_vx_take", "wx_slab_set_vx_bound", "wx_slab_cone", "wx_slab_period", "wx_pair_stats", "wx_placement_info", "wx_arith",
+    "wx_diag_collect", "wx_diag_merge", "wx_diag_finish", "wx_diag_accumulate", "wx_diag_accumulate_cells", "wx_diagnostics", "wx_group_diagnostics",
 ]
+
+
+class WxDiag(C.Structure):
+    """``wx_diag`` of include/wxsim.h, field for field (tests/test_diag_cpu.py compares the two)."""
+    _fields_ = [
+        ("iter", C.c_int64), ("n_air", C.c_int64), ("n_wall", C.c_int64), ("n_marker_mismatch", C.c_int64), ("n_negative_water", C.c_int64),
+        ("n_nonfinite_base", C.c_int64), ("n_nonfinite_water", C.c_int64),
+        ("first_nonfinite_base_x", C.c_int64), ("first_nonfinite_base_y", C.c_int64),
+        ("first_nonfinite_water_x", C.c_int64), ("first_nonfinite_water_y", C.c_int64),
+        ("sum_base", C.c_double * 4), ("sum_water", C.c_double * 4), ("sum_soil_moisture", C.c_double), ("sum_snow", C.c_double),
+        ("sum_vegetation", C.c_int64),
+        ("min_base", C.c_double * 4), ("max_base", C.c_double * 4), ("min_water", C.c_double * 4), ("max_water", C.c_double * 4),
+        ("min_base_x", C.c_int64 * 4), ("min_base_y", C.c_int64 * 4), ("max_base_x", C.c_int64 * 4), ("max_base_y", C.c_int64 * 4),
+        ("min_water_x", C.c_int64 * 4), ("min_water_y", C.c_int64 * 4), ("max_water_x", C.c_int64 * 4), ("max_water_y", C.c_int64 * 4),
+        ("n_droplets_active", C.c_int64), ("n_droplets_nonfinite", C.c_int64),
+        ("sum_droplet_mass_x", C.c_double), ("sum_droplet_mass_y", C.c_double),
+    ]
+
+
+DIAG_QUANTITIES, DIAG_BINS = 12, 16
+# quantity numbers of wx_diag_accumulate (WX_DIAG_QUANTITIES): base and water channels over the air cells, the two wall-cell sums, the droplets
+DIAG_Q = {"vx": 0, "vy": 1, "pressure": 2, "temperature": 3, "water": 4, "cloud": 5, "precipitation": 6, "smoke": 7,
+          "soil_moisture": 8, "snow": 9, "droplet_mass_x": 10, "droplet_mass_y": 11}
+
+
+class WxDiagRaw(C.Structure):
+    """``wx_diag_raw``: what leaves the device (integers only); ``bytes(raw)`` is what the hosts exchange and merge."""
+    _fields_ = [
+        ("x_global", C.c_int64), ("y_rows", C.c_int64), ("iter", C.c_int64), ("count", C.c_int64 * 10),
+        ("first_nonfinite", C.c_uint64 * 2), ("key_max", C.c_uint64 * 8), ("key_min", C.c_uint64 * 8),
+        ("bin_hi", (C.c_int64 * DIAG_BINS) * DIAG_QUANTITIES), ("bin_lo", (C.c_uint64 * DIAG_BINS) * DIAG_QUANTITIES),
+    ]
+
+
+DIAG_RAW_BYTES = C.sizeof(WxDiagRaw)
+
+
+def _diag_dict(d: WxDiag) -> dict:
+    """wx_diag as a dict under the same names; every ``*_x`` / ``*_y`` pair becomes one ``*_at`` = (x, y) or None, an absent extreme is None."""
+    def at(x, y):
+        return (int(x), int(y)) if x >= 0 else None
+    out = {}
+    for name, _ in WxDiag._fields_:
+        if name.endswith(("_x", "_y")) and not name.startswith("sum_"):
+            continue
+        v = getattr(d, name)
+        out[name] = list(v) if hasattr(v, "__len__") else v
+    out["first_nonfinite_base"] = at(d.first_nonfinite_base_x, d.first_nonfinite_base_y)
+    out["first_nonfinite_water"] = at(d.first_nonfinite_water_x, d.first_nonfinite_water_y)
+    for k in ("min_base", "max_base", "min_water", "max_water"):
+        xs, ys = getattr(d, k + "_x"), getattr(d, k + "_y")
+        out[k + "_at"] = [at(xs[c], ys[c]) for c in range(4)]
+        out[k] = [out[k][c] if xs[c] >= 0 or out[k][c] == out[k][c] else None for c in range(4)]
+    return out
+
+
+def _raw_of(b) -> WxDiagRaw:
+    if isinstance(b, WxDiagRaw):
+        return b
+    if len(b) != DIAG_RAW_BYTES:
+        raise ValueError(f"a wx_diag_raw has {DIAG_RAW_BYTES} bytes, got {len(b)}")
+    return WxDiagRaw.from_buffer_copy(bytes(b))
+
+
+def diag_empty() -> bytes:
+    """The empty set: a zero-filled wx_diag_raw."""
+    return bytes(DIAG_RAW_BYTES)
+
+
+def diag_merge(a, b) -> bytes:
+    """wx_diag_merge over ``bytes``: the union of two disjoint sets of cells of one domain (associative and commutative, bit for bit)."""
+    ra, rb = _raw_of(a), _raw_of(b)
+    rc = lib().wx_diag_merge(C.byref(ra), C.byref(rb))
+    if rc != 0:
+        raise WxError(rc, "wx_diag_merge: the two parts disagree about geometry or iteration")
+    return bytes(ra)
+
+
+def diag_finish(raw) -> dict:
+    """wx_diag_finish over ``bytes``: every sum rounded once (== math.fsum of the values that went in)."""
+    r, d = _raw_of(raw), WxDiag()
+    rc = lib().wx_diag_finish(C.byref(r), C.byref(d))
+    if rc != 0:
+        raise WxError(rc, "wx_diag_finish")
+    return _diag_dict(d)
+
+
+def diag_accumulate(raw, quantity, values) -> bytes:
+    """wx_diag_accumulate over ``bytes``: float32 ``values`` added to the bins of ``quantity`` (a number or a DIAG_Q name) on the CPU."""
+    r = _raw_of(raw)
+    v = np.ascontiguousarray(values, np.float32).ravel()
+    rc = lib().wx_diag_accumulate(C.byref(r), int(DIAG_Q.get(quantity, quantity)), v.ctypes.data, v.size)
+    if rc != 0:
+        raise WxError(rc, f"wx_diag_accumulate: quantity {quantity}")
+    return bytes(r)
+
+
+def diag_accumulate_cells(raw, X_global: int, Y: int, x: int, y: int, base, water, wall) -> bytes:
+    """wx_diag_accumulate_cells over ``bytes``: the kernel's per-cell function on the CPU over a run of cells (n, 4) of row ``y`` from column ``x``."""
+    r = _raw_of(raw)
+    b, w = np.ascontiguousarray(base, np.float32).reshape(-1, 4), np.ascontiguousarray(water, np.float32).reshape(-1, 4)
+    wl = np.ascontiguousarray(wall, np.int8).reshape(-1, 4)
+    if not (len(b) == len(w) == len(wl)):
+        raise ValueError("base, water and wall must hold the same number of cells")
+    rc = lib().wx_diag_accumulate_cells(C.byref(r), int(X_global), int(Y), int(x), int(y), len(b), b.ctypes.data, w.ctypes.data, wl.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_diag_accumulate_cells: bad geometry or range")
+    return bytes(r)
 
 
 def build(force: bool = False, fast: bool = False) -> str:
@@ -166,6 +275,13 @@ def lib() -> C.CDLL:
     L.wx_group_sync.argtypes = [vp]
     L.wx_group_set_option.argtypes = [vp, i32, i32]
     L.wx_group_exchange.argtypes = [vp]
+    L.wx_diag_collect.argtypes = [vp, vp]
+    L.wx_diag_merge.argtypes = [vp, vp]
+    L.wx_diag_finish.argtypes = [vp, vp]
+    L.wx_diag_accumulate.argtypes = [vp, i32, vp, C.c_size_t]
+    L.wx_diag_accumulate_cells.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.wx_diagnostics.argtypes = [vp, vp]
+    L.wx_group_diagnostics.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -351,6 +467,20 @@ class Handle:
         out = np.zeros((max(count, 0), 5), np.float32)
         self._chk(lib().wx_read_particles(self._h, first, count, out.ctypes.data))
         return out
+
+    # ---- diagnostics (wx_diag: replaces the reference's commented-out conservation block app.js:6736-6762) ----
+    def diagnostics(self) -> dict:
+        """Exact sums, extremes, census and non-finite report of the owned columns, computed on the device (wx_diagnostics): the members
+        of ``wx_diag`` by name, locations as global (x, y) or None. Changes nothing in the handle."""
+        d = WxDiag()
+        self._chk(lib().wx_diagnostics(self._h, C.byref(d)))
+        return _diag_dict(d)
+
+    def diagnostics_raw(self) -> bytes:
+        """wx_diag_collect: the unrounded integers of this handle's owned columns, to be merged with other slabs' (diag_merge, diag_finish)."""
+        r = WxDiagRaw()
+        self._chk(lib().wx_diag_collect(self._h, C.byref(r)))
+        return bytes(r)
 
     # ---- plumbing ----
     def set_stream(self, stream_ptr: int):
@@ -636,6 +766,14 @@ class Group:
 
     def sync(self):
         self._chk(lib().wx_group_sync(self._g))
+
+    def diagnostics(self) -> dict:
+        """wx_group_diagnostics: every slab's pass on its own device, merged: bit for bit the numbers of the undecomposed domain. With
+        droplets: call it where an exchange has just been applied (after ``exchange()``, or after a ``step`` whose iteration count ends
+        on a multiple of the slabs' period) -- in between a droplet that crossed a slab edge may be counted by neither or both slabs."""
+        d = WxDiag()
+        self._chk(lib().wx_group_diagnostics(self._g, C.byref(d)))
+        return _diag_dict(d)
 
     def read(self, field: str) -> np.ndarray:
         """The whole domain's field assembled from the slabs' owned columns."""

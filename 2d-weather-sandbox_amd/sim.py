@@ -171,6 +171,10 @@ class WeatherSim:
     def read_particles(self, first=0, count=None):
         return self._h.read_particles(first, count)
 
+    def diagnostics(self) -> dict:
+        """Conservation sums (exact), extremes and the non-finite census of the current state, from one device pass (Handle.diagnostics)."""
+        return self._h.diagnostics()
+
     def measure_station(self, x: int, y: int):
         """Weatherstation.measure (app.js:1084-1092): FB0 base 1x3 and water 1x2 starting at (x, y-1)."""
         return self.read_rect("BASE_CUR", x, y - 1, 1, 3), self.read_rect("WATER_0", x, y - 1, 1, 2)

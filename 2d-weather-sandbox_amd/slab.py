@@ -456,6 +456,38 @@ class SlabSim:
     def sync(self):
         self.engine.sync()
 
+    def diagnostics(self) -> Dict[str, Any]:
+        """COLLECTIVE: the exact conservation sums, extremes and census of the WHOLE domain on every rank (``Handle.diagnostics`` of the
+        undecomposed run, bit for bit). Each rank's device pass over its owned columns (wx_diag_collect), one all-gather of the raw
+        integers as bytes, merged in rank order and rounded locally. Every rank enqueues the same one collective whatever its own
+        pass returned: a rank whose pass failed contributes the empty set and a flag, and all ranks raise after the all-gather.
+        With droplets: call it right after an exchange (a droplet that crossed a slab edge since is counted by neither or both ranks)."""
+        from . import engine as _engine
+        n = _engine.DIAG_RAW_BYTES
+        err = None
+        try:
+            raw = self.handle.diagnostics_raw()
+        except Exception as ex:  # (reported after the collective: the other ranks are already waiting in it)
+            raw, err = _engine.diag_empty(), ex
+        mine = torch.frombuffer(bytearray(raw + (b"\1" if err is not None else b"\0")), dtype=torch.uint8)
+        if self.world == 1:
+            parts = [mine]
+        else:
+            on_dev = self.send[0].is_cuda and not self._stage
+            dev = self.send[0].device if on_dev else torch.device("cpu")
+            parts = [torch.empty(n + 1, dtype=torch.uint8, device=dev) for _ in range(self.world)]
+            dist.all_gather(parts, mine.to(dev))
+            parts = [p.cpu() for p in parts]
+        failed = [r for r, p in enumerate(parts) if int(p[n])]
+        if err is not None:
+            raise err
+        if failed:
+            raise RuntimeError(f"SlabSim.diagnostics: the device pass failed on rank(s) {failed}")
+        merged = _engine.diag_empty()
+        for p in parts:
+            merged = _engine.diag_merge(merged, bytes(p[:n].numpy().tobytes()))
+        return _engine.diag_finish(merged)
+
     def upload(self, base, water, wall, drops=None):
         """Re-upload this rank's slab (local arrays incl. ghost columns): the ghost columns are fresh again, so the exchange
         period starts over and the next step does not run the interior-first split against an exchange that never happened."""

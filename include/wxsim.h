@@ -480,6 +480,80 @@ int wx_fastest_velocity(wx_sim *s, float *cells_per_iteration);
  * reference has no velocity clamp (advectionShader.frag:85-99); results are bit-identical to one iteration per launch whatever these say. */
 int wx_pair_stats(wx_sim *s, int64_t *cells_recomputed, int64_t *pairs_repeated);
 
+/* ---- Conservation and health diagnostics, computed on the device in one pass over the state ----
+ * Replaces the reference's commented-out block app.js:6736-6762 (readPixels of the whole water texture, then a JavaScript loop that sums
+ * vapour, cloud and smoke over the non-wall cells). Covers the handle's OWNED columns (the ghost columns of a slab are excluded), all
+ * rows, of the CURRENT state: WX_FIELD_BASE_CUR, WX_FIELD_WATER_CUR, WX_FIELD_WALL_CUR and the droplet buffer wx_read_particles returns.
+ * A cell is a WALL cell iff channel 1 (distance) of its WX_FIELD_WALL_CUR texel is 0 -- the engine's own test in bilerpWall
+ * (common.glsl:216-254) --, otherwise an AIR cell.
+ *
+ * Every floating-point sum is EXACT: the correctly rounded (round-to-nearest-even, to double) value of the mathematically exact sum of
+ * the float values it covers -- what Python's math.fsum returns. It therefore does not depend on the order of summation, the launch
+ * shape or the decomposition: N slabs merged give the bits of the undecomposed handle. A non-finite VALUE (NaN, +-Inf) is never added
+ * into a sum (the other channels of its cell are); such cells are counted. A sum over no values is +0.0.
+ * Extremes: NaNs are skipped; -0.0 and 0.0 compare equal (a zero extreme is reported as +0.0); among equal values the cell with the
+ * smallest global index y * X_global + x is reported. Locations are GLOBAL (x, y), y = 0 at the bottom; -1, -1 means "none".
+ * A diagnostics call changes nothing: not the state, not the fields that are made on demand, not the iteration counter. */
+#define WX_HAVE_DIAGNOSTICS 1
+typedef struct wx_diag {
+  int64_t iter;               /* the iteration counter the numbers belong to */
+  int64_t n_air, n_wall;      /* census of the covered cells */
+  int64_t n_marker_mismatch;  /* cells where (water.x > 1000) differs from "is a wall cell": the reference's diagnostic tests the marker, the engine the wall texture */
+  int64_t n_negative_water;   /* air cells with water.x < 0 */
+  int64_t n_nonfinite_base, n_nonfinite_water;  /* cells (air and wall) with a NaN or +-Inf in any channel */
+  int64_t first_nonfinite_base_x, first_nonfinite_base_y;   /* the first such cell in order of the global index; -1, -1: none */
+  int64_t first_nonfinite_water_x, first_nonfinite_water_y;
+  double sum_base[4];         /* over the air cells: vx, vy, pressure, temperature */
+  double sum_water[4];        /* over the air cells: total water, cloud water, precipitation (visual), smoke */
+  double sum_soil_moisture;   /* over the wall cells: water.z */
+  double sum_snow;            /* over the wall cells: water.w */
+  int64_t sum_vegetation;     /* over the wall cells: wall channel 3 */
+  double min_base[4], max_base[4], min_water[4], max_water[4]; /* over the air cells, NaNs skipped; NaN if there is no such value */
+  int64_t min_base_x[4], min_base_y[4], max_base_x[4], max_base_y[4];     /* where each extreme FIRST occurs; -1, -1: none */
+  int64_t min_water_x[4], min_water_y[4], max_water_x[4], max_water_y[4];
+  int64_t n_droplets_active;    /* droplets with mass.x >= 0 (a slab counts the ones inside its owned columns that it tracks itself) */
+  int64_t n_droplets_nonfinite; /* active droplets whose mass.x or mass.y is not finite */
+  double sum_droplet_mass_x, sum_droplet_mass_y; /* over the active droplets: mass.x (water), mass.y (ice) */
+} wx_diag;
+
+/* What leaves the device: integers only, nothing rounded yet. A zero-filled wx_diag_raw is the empty set. Sums: a finite float is
+ * m * 2^(e - 150) with an integer |m| < 2^24 and a biased exponent e in 1..254 (subnormals: e = 1, no hidden bit); quantity q keeps 16 integer
+ * bins, bin e >> 4 receives m << (e & 15). A bin's value is hi * 2^32 + lo with 0 <= lo < 2^32 (one representation per value, so a merge
+ * is associative and commutative bit for bit). Extremes: one 64-bit key per channel, order-preserving float bits above the inverted
+ * global index, combined with max (the keys of the minima hold the inverted float order). */
+#define WX_DIAG_QUANTITIES 12  /* 0-3 base, 4-7 water (air cells); 8 soil moisture, 9 snow (wall cells); 10 droplet mass.x, 11 droplet mass.y */
+#define WX_DIAG_BINS 16
+typedef struct wx_diag_raw {
+  int64_t x_global, y_rows;   /* geometry the global indices refer to; 0: no device pass went into this yet */
+  int64_t iter;
+  int64_t count[10];          /* n_air, n_wall, n_marker_mismatch, n_negative_water, n_nonfinite_base, n_nonfinite_water, sum_vegetation,
+                                 n_droplets_active, n_droplets_nonfinite, cells covered */
+  uint64_t first_nonfinite[2]; /* base, water: ~global index, combined with max; 0: none */
+  uint64_t key_max[8], key_min[8];
+  int64_t bin_hi[WX_DIAG_QUANTITIES][WX_DIAG_BINS];
+  uint64_t bin_lo[WX_DIAG_QUANTITIES][WX_DIAG_BINS];
+} wx_diag_raw;
+
+/* Device pass over this handle's owned columns, enqueued on the handle's stream behind the pending iterations; synchronous like
+ * wx_read_rect, and like it the place where the iterations report WX_E_STATE. WX_E_STATE before wx_upload. */
+int wx_diag_collect(wx_sim *s, wx_diag_raw *out);
+/* Host only, pure: `into` becomes the union of two disjoint sets of cells of ONE domain (WX_E_INVALID if geometry or iteration differ). */
+int wx_diag_merge(wx_diag_raw *into, const wx_diag_raw *other);
+/* Host only, pure: combines the bins of every quantity in a 320-bit integer and rounds ONCE to double. */
+int wx_diag_finish(const wx_diag_raw *raw, wx_diag *out);
+/* Host only: adds n floats to the bins of `quantity` with the binning function the kernel uses (non-finite values are skipped). */
+int wx_diag_accumulate(wx_diag_raw *into, int quantity, const float *values, size_t n);
+/* Host only: the kernel's per-cell function over n cells of row y starting at global column x (base, water: 4 floats per cell, wall: 4
+ * bytes per cell), for hosts that hold cells themselves and for tests without a GPU. Sets the geometry of an empty `into`. */
+int wx_diag_accumulate_cells(wx_diag_raw *into, int x_global, int y_rows, int x, int y, int n, const float *base, const float *water, const int8_t *wall);
+/* wx_diag_collect + wx_diag_finish. */
+int wx_diagnostics(wx_sim *s, wx_diag *out);
+/* Every slab of the group collects on its own device and stream; merged and finished: the numbers of the undecomposed domain (with
+ * droplets: the pool protocol makes one slab THE owner of an active droplet at the iterations that end with an exchange -- every
+ * wx_slab_period iterations of wx_group_step, or after wx_group_exchange; in between a droplet that crossed a slab edge may be counted by
+ * neither or both). A failed slab reports through wx_group_last_error. */
+int wx_group_diagnostics(wx_group *g, wx_diag *out);
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */
