@@ -130,9 +130,7 @@ __global__ __launch_bounds__(NTD, WX_D_MINWAVES) void k_fused_dry(Geo g, Uni u, 
   } sm;
   const int X = g.X, Y = g.Y;
   const int tid = threadIdx.x;
-  int tbx, tby;
-  tile_of_block(tiles_x(X), tbx, tby);
-  const int tx0 = tbx * TX, ty0 = tby * TY;
+  const int tx0 = (int)blockIdx.x * TX, ty0 = (int)blockIdx.y * TY; // (tile_grid)
   const bool small = (X < TX + 8) || (Y < TY + 8);
 #define WX_WRAPX(v) (small ? wrapmod((v), X) : wrapfast((v), X))
 #define WX_WRAPY(v) (small ? wrapmod((v), Y) : wrapfast((v), Y))

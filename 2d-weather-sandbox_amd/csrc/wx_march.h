@@ -19,9 +19,6 @@
 #include "wx_wet.h"
 #include <vector> // ld_row / st_row (scalar-base addressing), wave_from_left (DPP shift)
 
-#ifndef WX_MARCH_BANDS
-#define WX_MARCH_BANDS 1
-#endif
 #ifndef WX_MARCH_BAND_SEG
 #define WX_MARCH_BAND_SEG 24 // (32768x4096, interleaved: 24-row band segments + tail 0.941-0.943 ms, 32-row 0.953, equal 32-row segments 0.954)
 #endif
@@ -29,12 +26,6 @@ namespace wx {
 
 #ifndef WX_MARCH_MAXSEG
 #define WX_MARCH_MAXSEG 32 // upper bound of the rows one wave marches (3 warm-up rows per segment are redundant work; measured at 32768x4096: 32 rows 143.7, 64 rows 140.6, 128 rows 135.7 Gcell-steps/s)
-#endif
-#ifndef WX_MARCH_UNI_MEM
-#define WX_MARCH_UNI_MEM 1 // measured: SGPR spills 12 -> 0, 0.31 -> 0.29 ms at 16384x2048
-#endif
-#ifndef WX_MARCH_XCD
-#define WX_MARCH_XCD 1
 #endif
 #ifndef WX_MARCH_MINWAVES
 #define WX_MARCH_MINWAVES 8
@@ -83,23 +74,8 @@ __device__ __forceinline__ MDryFp make_fp(const MDryAcc &a, int dx0, int dy0) { 
 // WRITE_WALL = false: the host has established that advection cannot change the wall texture in this launch (no brush,
 // no airplane crash, no negative vegetation left to clamp -- the only three ways, advectionShader.frag:189-227, 229-457),
 // so the pass-through store is dropped and the wall buffers are not swapped: 36 B/cell, SURVEY's A_dry.
-#ifndef WX_MARCH_FENCE
-#define WX_MARCH_FENCE 0 // 1: wavefront-scope fence instead of __syncthreads() between the stages (the workgroup is one wave)
-#endif
-__device__ __forceinline__ void march_fence()
-{
-#if WX_MARCH_FENCE
-  wave_fence();
-#else
-  __syncthreads();
-#endif
-}
-#ifndef WX_MARCH_AIR
-#define WX_MARCH_AIR 1 // wave-uniform free-air instantiation of the advection stage (rows without wall cells)
-#endif
-#ifndef WX_MARCH_UNROLL
-#define WX_MARCH_UNROLL 1 // row steps per loop iteration. 2: 1.08 instead of 0.95 ms at 32768x4096 (more registers, fewer waves per SIMD), unlike k_march_wet
-#endif
+// between the stages of a row step; the workgroup is one wave, so the barrier orders the wave's own LDS traffic and waits for nobody
+__device__ __forceinline__ void march_fence() { __syncthreads(); }
 // QUIET: no brush input, no airplane event in this iteration (see advection_cell)
 template <bool WRITE_DISP, bool WRITE_WALL, bool QUIET>
 __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni u_arg, const FullCtx *__restrict__ ctx, DryIn in, DryOut out, int n_strips, int seg_rows,
@@ -113,18 +89,14 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
   const unsigned long long t_begin = __builtin_readcyclecounter();
 #endif
   __shared__ MarchRing rg;
-#if WX_MARCH_UNI_MEM
   // uniforms and the per-row profiles through the constant address space: scalar loads the compiler may re-issue anywhere
   // (through a generic pointer every load behind the first store of the kernel turns into a vector load, and waiting for it
-  // means waiting for the row prefetch issued just before). The dry passes do not use iterNum.
+  // means waiting for the row prefetch issued just before). The dry passes do not use iterNum. Against the by-value argument
+  // (u_arg, unused): SGPR spills 12 -> 0, 0.31 -> 0.29 ms at 16384x2048.
   CUni &u = as_constant(ctx->u);
-#else
-  const Uni &u = u_arg;
-#endif
   const CFloatP initial_T = as_constant(ctx->initial_T), snd_T = as_constant(ctx->snd_T), snd_W = as_constant(ctx->snd_W), snd_Vel = as_constant(ctx->snd_Vel);
   const int X = g.X, Y = g.Y;
   const int lane = threadIdx.x;
-#if WX_MARCH_XCD
   // XCD-aware placement: workgroup id lands on XCD id % 8 (MI355X_MICROARCH.md). The (segment, strip) items are numbered
   // segment-major and XCD k takes the contiguous range [k*T/8, (k+1)*T/8): neighbouring strips run on the same XCD, so the
   // 128-byte lines they share (2 halo columns each side; 60-column strips are not line aligned) are fetched into ONE L2
@@ -150,10 +122,6 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
     strip = pk.strip;
     is_edge = pk.is_edge;
   }
-#else
-  const int sidx = blockIdx.x % n_strips, seg = blockIdx.x / n_strips;
-  const int strip = sidx < split_at ? strip_lo + sidx : strip_lo2 + (sidx - split_at);
-#endif
   const int c_out = strip * MOUT + lane - 2;         // output column of this lane (may be >= X in the last strip)
   const int col = wrapmod(c_out, X);                 // column this lane loads / computes
   const bool lane_out = lane >= 2 && lane <= 61 && c_out < X;
@@ -211,9 +179,7 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
     int w_raw = w_new;
     asm volatile("" : "+v"(w_raw)); // keeps the byte unpacking on this side of the prefetch
     const char4 w_cur = make_char4((signed char)(w_raw & 0xff), (signed char)((w_raw >> 8) & 0xff), (signed char)((w_raw >> 16) & 0xff), (signed char)(w_raw >> 24));
-#if WX_MARCH_AIR
     const int nw0 = __all(w_cur.y != 0);
-#endif
     // software prefetch: next row's loads are in flight while this row is processed
     if (r < y_hi + 1) {
       const size_t e = (size_t)yw_p1 * X;
@@ -261,11 +227,9 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
         }
         if (fast) {
           MDryAcc a{rg, l1, yc};
-#if WX_MARCH_AIR
           if (nw1 & nw2 & nw3) // (wave-uniform) no wall cell in the three rows the footprints reach: plain interpolation, no wall branch
             advection_cell<true, true, false, QUIET>(u, g, initial_T, snd_T, snd_W, snd_Vel, col, y, a, ab, aw, awl);
           else
-#endif
             advection_cell<true, false, false, QUIET>(u, g, initial_T, snd_T, snd_W, snd_Vel, col, y, a, ab, aw, awl);
         } else { // exact out-of-line path (velocity recomputed from global memory)
           const AdvOut o = advection_cell_dry_global(ctx, in, false, col, y);
@@ -289,30 +253,14 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
     w_prev = w_cur;
     big3 = big2;
     big2 = big1;
-#if WX_MARCH_AIR
     nw3 = nw2;
     nw2 = nw1;
     nw1 = nw0;
-#endif
     yw_p1 = yw_p1 + 1 == Y ? 0 : yw_p1 + 1;
     yw_m2 = yw_m2 + 1 == Y ? 0 : yw_m2 + 1;
   };
-#if WX_MARCH_UNROLL >= 2
-  // several row steps per loop iteration: the values carried from step to step (prefetched row, previous rows, deferred stores)
-  // change registers between the copies instead of being moved (cf. WX_WET_UNROLL2)
-  for (; r <= y_hi + 1;) {
-    step();
-    r++;
-#pragma unroll
-    for (int k = 1; k < WX_MARCH_UNROLL; k++) {
-      if (r > y_hi + 1) break;
-      step();
-      r++;
-    }
-  }
-#else
+  // one row step per loop iteration (two, as in k_march_wet: 1.08 instead of 0.95 ms at 32768x4096 -- more registers, fewer waves per SIMD)
   for (; r <= y_hi + 1; r++) step();
-#endif
   if (st_valid && lane_out) { // the last row
     const size_t e = (size_t)(y_hi - 1) * X;
     st_row_v(out.base + e, so16, st_p);
@@ -348,7 +296,6 @@ inline int march_capacity()
 inline int march_seg_rows(int n_strips, int Y)
 {
   const int capacity = march_capacity();
-  if (const char *e = wx_tune_env("WX_MARCH_SEG")) return atoi(e) < Y ? atoi(e) : Y;
   int maxseg = WX_MARCH_MAXSEG;
   if (const char *e = wx_tune_env("WX_MARCH_MAXSEG")) maxseg = atoi(e) > 0 ? atoi(e) : maxseg;
   for (int k = 1; k < 64; k++) {
@@ -377,7 +324,7 @@ inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, cons
   if (n_strips <= 0) return 0;
   int seg_rows = march_seg_rows(n_strips_all, g.Y);
   int n_seg = (g.Y + seg_rows - 1) / seg_rows, n_full = n_seg, n_half = 0, band_h = 0;
-  if (WX_MARCH_XCD && WX_MARCH_BANDS && !wx_tune_env("WX_MARCH_NOTAIL") && !wx_tune_env("WX_MARCH_SEG") && g.Y % 8 == 0) {
+  if (g.Y % 8 == 0) {
     int R = WX_MARCH_BAND_SEG;
     const int bh = g.Y / 8;
     // (Round 5, measured: on grids whose 24-row band segments do not fill the chip -- 4096 x 1024, BASELINE configs[1], is 69 strips x 56
@@ -397,7 +344,7 @@ inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, cons
   StripOrder ord{};
   if (order && order->mode != 0) {
     ord = *order;
-    if (!(band_h > 0 && WX_MARCH_XCD)) ord.mode = 3;
+    if (band_h == 0) ord.mode = 3;
   }
   const int edge_items = ord.mode != 0 ? (ord.nl + (n_strips_all - ord.nr0)) * n_seg : 0;
   VxTrack vt = vx ? *vx : VxTrack{nullptr, nullptr, 0.0f, 0, 0};
@@ -406,7 +353,7 @@ inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, cons
     vt.zone_r = vx->zone_r / MOUT;
   }
   // (an ordered launch groups edge and interior strips separately: with one wave per workgroup the count is the same)
-  const dim3 grid(WX_MARCH_XCD ? 8 * ((n_strips * n_seg + 7) / 8) : n_strips * n_seg);
+  const dim3 grid(8 * ((n_strips * n_seg + 7) / 8));
   static bool dbg = wx_tune_env("WX_MARCH_DEBUG") != nullptr;
   if (dbg) {
     fprintf(stderr, "[wx_march] strips=%d seg_rows=%d segs=%d (bands of %d rows: %d full + 2 x %d short each) waves=%d\n", n_strips, seg_rows, n_seg, band_h, n_full, n_half, n_strips * n_seg);

@@ -634,13 +634,14 @@ __device__ __forceinline__ void dry2_grid_barrier(int *cnt, int *rel, int epoch,
 
 // ---- k_dry2_post: everything that may have to follow a pair, in ONE launch (round 6: the fix pass and the two predicated repeat launches ----
 // ---- were three dependent launches of ~5 us each behind every pair -- a quarter of a 4096 x 1024 pair) ----
-// A small co-resident grid (D2_POST_GRID workgroups of one wave). Quiet pair -- list empty, epoch word not this pair's --: one scalar load
-// per workgroup, and out. Entries on the list (the host's hint word was stale: a flow that has just produced its first fast cells; with a
+// A small grid (D2_POST_GRID workgroups of one wave; the first D2_POST_ACTIVE of them do whatever follows the quiet check). Quiet pair
+// -- list empty, epoch word not this pair's --: one scalar load per workgroup, and out. Entries on the list (the host's hint word was stale: a flow that has just produced its first fast cells; with a
 // non-zero hint the wide k_dry2_fix runs in front and leaves the list empty): fixed here, grid-stride. The pair has to be repeated whole
 // (decided by either fix pass): iteration 1 from the pair's inputs into the scratch buffer -> grid barrier -> iteration 2 into the pair's
 // output (+ display field).
-// (128: the barrier needs every workgroup of the launch resident at once, and up to eight slab handles may share one device in the group
-// tests -- 8 x 128 workgroups of 32 KB of LDS fit the chip's 1 280 slots together, so no two such launches can starve each other)
+// (D2_POST_ACTIVE = 128: the barrier needs every workgroup that takes part resident at once, and up to eight slab handles may share one
+// device in the group tests -- 8 x 128 workgroups of 32 KB of LDS fit the chip's 1 280 slots together, so no two such launches can starve
+// each other. The other workgroups of the D2_POST_GRID = 512 launched leave behind the quiet check and never wait at a barrier.)
 #ifndef WX_POST_GRID
 #define WX_POST_GRID 512
 #endif
@@ -729,10 +730,9 @@ inline void launch_march_dry2(const Geo &g, const Uni &u, const FullCtx *ctx, co
   const bool quiet = !(u.userInputType >= 1) && !(u.airplaneValues[3] < 0.0f || u.airplaneValues[3] > 0.9f);
   // The host's (stale) hint word -- the length of the last exact-path list it has heard of -- picks the instantiation: clean flows run the plain
   // one (first-iteration fast cells, should one appear, take the inline path through global memory), flows with fast cells the TAINT one
-  // (no inline path: those cells go to the list with what depends on them). Identical results; an A/B switch in the debug build.
+  // (no inline path: those cells go to the list with what depends on them). Identical results.
   const int last = fix.hint_host ? *(volatile const int *)fix.hint_host : -1;
-  bool taint = last > 0;
-  if (const char *e = wx_tune_env("WX_MARCH2_TAINT")) taint = atoi(e) != 0;
+  const bool taint = last > 0;
 #define WX_LAUNCH_M2(Q, D, T) hipLaunchKernelGGL((k_march_dry2<Q, D, T>), grid, dim3(64), 0, stream, g, ctx, in, out, n_strips, seg_rows, n_full, n_half, band_h, n_seg, vt, fix)
 #define WX_LAUNCH_M2T(Q, D) \
   do { if (taint) WX_LAUNCH_M2(Q, D, true); else WX_LAUNCH_M2(Q, D, false); } while (0)
@@ -743,7 +743,6 @@ inline void launch_march_dry2(const Geo &g, const Uni &u, const FullCtx *ctx, co
   }
 #undef WX_LAUNCH_M2T
 #undef WX_LAUNCH_M2
-  if (wx_tune_env("WX_MARCH2_NOREDO")) return; // (timing experiments)
   // While the host's (stale) hint word says that the lists hold entries: the wide fix pass -- one wavefront per recorded cell, room for four
   // times the last list, at most 4096 workgroups of one wave (the list is walked grid-stride: any size is correct).
   if (last != 0) {

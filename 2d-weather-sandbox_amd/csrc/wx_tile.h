@@ -34,45 +34,10 @@ __device__ __forceinline__ size_t fidx(int x, int y, int X) { return (size_t)y *
 // wrap for i in [-n, 2n): tile halos of grids at least as large as the halo
 __device__ __forceinline__ int wrapfast(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
 
-// XCD-aware tile order. The dispatcher places workgroup `id` on XCD id % 8 (observed, MI355X_MICROARCH.md); every XCD has
-// its own L2. With the natural order horizontally adjacent tiles land on different XCDs and the 128-byte lines of
-// their shared halo columns are fetched once per XCD. Here XCD k walks the column block [k*GX/8, (k+1)*GX/8) row band by
-// row band, so that left/right (and, one band later, upper/lower) neighbours hit the same L2. Placement only affects
-// speed, never results. MEASURED (16384x2048): FETCH_SIZE of kernel B drops from 1.18x to 1.05x of the algorithmic
-// bytes, but the kernel gets 2 % SLOWER (the re-fetched halo lines were served by the Infinity Cache, and the
-// column-block order concentrates each XCD on fewer HBM channels), so the natural order stays the default.
-#ifndef WX_XCD_TILES
-#define WX_XCD_TILES 0
-#endif
-#ifndef WX_GRID2D
-#define WX_GRID2D 1
-#endif
-__device__ __forceinline__ void tile_of_block(int GX, int &bx, int &by)
-{
-#if WX_GRID2D
-  bx = blockIdx.x;
-  by = blockIdx.y;
-#else
-  const int id = blockIdx.x;
-  if (WX_XCD_TILES && (GX & 7) == 0) {
-    const int k = id & 7, j = id >> 3, w = GX >> 3;
-    by = j / w;
-    bx = k * w + (j - by * w);
-  } else {
-    by = id / GX;
-    bx = id - by * GX;
-  }
-#endif
-}
-inline dim3 tile_grid(int X, int Y)
-{
-#if WX_GRID2D
-  return dim3((X + 63) / 64, (Y + 15) / 16);
-#else
-  return dim3(((X + 63) / 64) * ((Y + 15) / 16));
-#endif
-}
-__device__ __forceinline__ int tiles_x(int X) { return (X + 63) / 64; }
+// One workgroup per tile, 2-D grid in the natural order. (An XCD-aware order -- XCD k walks its own column block, so that neighbouring
+// tiles share an L2 -- dropped the tiled dry kernel's FETCH_SIZE from 1.18x to 1.05x of the algorithmic bytes at 16384x2048 and made it
+// 2 % SLOWER: the re-fetched halo lines came from the Infinity Cache, and the column blocks concentrate each XCD on fewer HBM channels.)
+inline dim3 tile_grid(int X, int Y) { return dim3((X + 63) / 64, (Y + 15) / 16); }
 
 // fp32 plane set of a float4 field
 template <int H, int W> struct Planes4 {
@@ -87,19 +52,16 @@ template <int H, int W> struct Planes4 {
   __device__ __forceinline__ float4 get(int r, int c) const { return make_float4(x[r][c], y[r][c], z[r][c], w[r][c]); }
 };
 
-#ifndef WX_REACH
-#define WX_REACH 1
-#endif
 namespace fb_ {
 // advection is evaluated on x,y in [-1,0] (pressure needs the left and lower neighbour); its 7-point velocity
 // stencil reaches 1 further, and so does the back-traced bilinear footprint as long as |v| < 1 cell/iteration
 // (REACH = 1; the shaders document velocities as "-1.0 to 1.0", common.glsl:40-41): inputs on [-2,+1].
-// Cells with a longer back-trace take the exact out-of-line path. REACH = 2 stages [-3,+2] and covers |v| < 2.
-constexpr int REACH = WX_REACH;
+// Cells with a longer back-trace take the exact out-of-line path.
+constexpr int REACH = 1;
 constexpr int HL = 1 + REACH, HR = REACH, HD = 1 + REACH, HU = REACH;
 constexpr int IW = TX + HL + HR, IH = TY + HD + HU;
 constexpr int AW = TX + 1, AH = TY + 1;             // advection results on [-1,0]
-constexpr float VMAX = REACH == 1 ? 0.9f : 1.9f;    // back-traces shorter than this stay inside the staged tile
+constexpr float VMAX = 0.9f;                        // back-traces shorter than this stay inside the staged tile
 struct SmemOut { // advection output needed by neighbours (aliases the input tiles after a barrier)
   float vx[AH][AW], vy[AH][AW], T[AH][AW];
   char4 w[AH][AW + 1];
@@ -132,7 +94,6 @@ struct StripOrder {
   int edge_list;         // wet kernel: edge waves append their exact-path cells to the second list (consumed on the comm stream)
   int prio;              // s_setprio level of the edge waves (0: none): all waves of a slab's launch are resident at once, so the DISPATCH order
                          // alone does not make the edge strips finish first -- the SIMD's issue priority does
-  int nofence;           // (timing experiments only: no release fence in front of the arrival -- WRONG results)
 };
 // position `sloc`-th of the n_part strips of one part (edge / interior) of the strip range [a, b) -> strip; returns false past the end
 struct StripPick {
@@ -196,7 +157,7 @@ __device__ __forceinline__ void strip_order_wait(const StripOrder &o)
 __device__ __forceinline__ void strip_order_arrive(const StripOrder &o, int lane, bool stored)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (stored && !o.nofence) {
+  if (stored) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // writes the XCD's dirty lines back: the pack kernel may run on any XCD
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the compiler may drop the wait behind buffer_wbl2: restated where it cannot)
   }

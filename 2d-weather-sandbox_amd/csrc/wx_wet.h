@@ -45,54 +45,12 @@ namespace wx {
 #ifndef WX_WET_MINWAVES
 #define WX_WET_MINWAVES 4
 #endif
-#ifndef WX_WET_UNI_COPY
-#define WX_WET_UNI_COPY 0
-#endif
 #ifndef WX_WET_WPB
 #define WX_WET_WPB 4 // wavefronts per workgroup: independent strips (no barrier between them); the dispatcher spreads the waves of
                      // ONE workgroup evenly over the four SIMDs of a CU, which it does not guarantee for single-wave workgroups
 #endif
 #ifndef WX_ABL_FORCE_AIR
 #define WX_ABL_FORCE_AIR 0 // (instruction-budget builds: every row takes the free-air instantiations; wrong near terrain)
-#endif
-#ifndef WX_WET_ARGS_MEM
-#define WX_WET_ARGS_MEM 1
-#endif
-#ifndef WX_WET_BANDS
-#define WX_WET_BANDS 1
-#endif
-#ifndef WX_WET_FB_COND
-#define WX_WET_FB_COND 0 // 1: load feedback rows only where a tile holds feedback (measured: 1.012-1.021 vs 0.974-0.977 ms with the always-issued loads from a row of zeros)
-#endif
-#ifndef WX_WET_TAIL
-#define WX_WET_TAIL 1
-#endif
-#ifndef WX_WET_ALPHA_DEFAULT
-#define WX_WET_ALPHA_DEFAULT 1.0 // cost of a row below air_from_row relative to a free-air row when the segment borders are placed
-#endif
-#ifndef WX_WET_PRIO_ROTATE
-#define WX_WET_PRIO_ROTATE 0
-#endif
-#ifndef WX_WET_SKIP_LOADS
-#define WX_WET_SKIP_LOADS 1 // 1: no water / light loads in the first two warm-up steps; light_0.x only near walls. 2: only the latter. 0: neither
-#endif
-#ifndef WX_WET_NT_STORES
-#define WX_WET_NT_STORES 0
-#endif
-#ifndef WX_WET_ZW0
-#define WX_WET_ZW0 1 // wave-uniform skip of the precipitation-visual / smoke interpolations where those channels are zero (advection_cell NO_ZW)
-#endif
-#ifndef WX_WET_DEP_NEAR
-#define WX_WET_DEP_NEAR 1 // deposition rows are only loaded where a surface wall cell can read them
-#endif
-#ifndef WX_WET_PRIO_MEM
-#define WX_WET_PRIO_MEM 0 // s_setprio level while a step issues its prefetch and its deferred stores (0: none)
-#endif
-#ifndef WX_WET_UNROLL2
-#define WX_WET_UNROLL2 1 // two row steps per loop iteration (measured -1.2 .. -1.6 % at 16384x2048: fewer register moves for the carried values)
-#endif
-#ifndef WX_WET_AIR
-#define WX_WET_AIR 1 // wave-uniform free-air instantiations of the boundary / advection / lighting stages
 #endif
 
 struct FullCtx { // static per wx_set_params; the per-launch items (buffer pointers, iterNum) travel as arguments
@@ -425,24 +383,14 @@ template <class T> __device__ __forceinline__ T ld_row(const T *row, unsigned &b
   asm("" : "+v"(byte_off));
   return *(GPtr)((GBytes)uniform_addr(row) + byte_off);
 }
-template <int N> struct NativeVec;
-template <> struct NativeVec<4> { typedef unsigned type; };
-template <> struct NativeVec<8> { typedef unsigned type __attribute__((ext_vector_type(2))); };
-template <> struct NativeVec<16> { typedef unsigned type __attribute__((ext_vector_type(4))); };
 template <class T> __device__ __forceinline__ void st_row(T *row, unsigned &byte_off, T v)
 {
   typedef __attribute__((address_space(1))) char *GBytes;
   asm("" : "+v"(byte_off));
-#if WX_WET_NT_STORES
-  // streamed once, read again only by the next launch: keep the output rows from evicting the input lines that neighbouring
-  // strips still share (halo columns) out of the 4 MB L2
-  typedef typename NativeVec<sizeof(T)>::type NV;
-  typedef __attribute__((address_space(1))) NV *GPtr;
-  __builtin_nontemporal_store(__builtin_bit_cast(NV, v), (GPtr)((GBytes)uniform_addr(row) + byte_off));
-#else
+  // (plain stores: nontemporal ones bring the re-read halo and warm-up lines from 1.25x back to 1.19x of the algorithmic bytes without
+  // moving the time, and cost a cache-sized grid 17 %)
   typedef __attribute__((address_space(1))) T *GPtr;
   *(GPtr)((GBytes)uniform_addr(row) + byte_off) = v;
-#endif
 }
 #else // host pass of the single-source compile: same meaning, never executed
 template <class T> __device__ __forceinline__ T ld_row(const T *row, unsigned &byte_off) { return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(row) + byte_off); }
@@ -468,7 +416,7 @@ __device__ __forceinline__ int ring_back(int s, int k, int n) // slot of the row
 constexpr int WMAXSEG = 128;
 struct WetSegs {
   int n_seg;
-  int bands;              // experimental (WX_WET_BANDS=1): XCD k takes the row band [k*Y/8, (k+1)*Y/8) of ALL strips; start[] is relative to it
+  int bands;              // != 0: XCD k takes the row band [k*Y/8, (k+1)*Y/8) of ALL strips; start[] is relative to it
   int start[WMAXSEG + 1];
 };
 // QUIET: no brush input and no airplane event in this iteration (the host looks at the uniforms): advection_cell without those sections.
@@ -489,33 +437,28 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
     StripOrder order;
     VxTrack vx;
   };
-#if WX_WET_ARGS_MEM && defined(__HIP_DEVICE_COMPILE__)
   // The ~22 plane pointers are read from the kernel-argument segment (constant address space) where they are used: separate
   // two-dword scalar loads that the register allocator can re-issue, instead of 44 SGPRs preloaded in wide loads that it can only
-  // spill -- and an SGPR spill / restore is a v_writelane / v_readlane, i.e. a VECTOR instruction in a VALU-bound loop.
+  // spill -- and an SGPR spill / restore is a v_writelane / v_readlane, i.e. a VECTOR instruction in a VALU-bound loop. The struct
+  // parameters (in_arg ... vx_arg) are therefore never named below: they give the segment its layout.
   typedef const __attribute__((address_space(4))) char *KBytes;
+#if defined(__HIP_DEVICE_COMPILE__)
   const KBytes ka_c = (KBytes)__builtin_amdgcn_kernarg_segment_ptr();
+#else // host pass of the single-source compile: the body is parsed, never emitted
+  const KBytes ka_c = nullptr;
+#endif
   const __attribute__((address_space(4))) WetIn &in = *(const __attribute__((address_space(4))) WetIn *)(ka_c + offsetof(KArgs, in));
   const __attribute__((address_space(4))) WetOut &out = *(const __attribute__((address_space(4))) WetOut *)(ka_c + offsetof(KArgs, out));
   // (the split-iteration order likewise: read where it is used -- prologue and epilogue --, nothing of it lives in the row loop)
   const __attribute__((address_space(4))) StripOrder &order_c = *(const __attribute__((address_space(4))) StripOrder *)(ka_c + offsetof(KArgs, order));
-#define WX_ORDER() (StripOrder{order_c.mode, order_c.nl, order_c.nr0, order_c.arrive, order_c.epoch, order_c.epoch_want, order_c.edge_list, order_c.prio, order_c.nofence})
-#else
-  const WetIn &in = in_arg;
-  const WetOut &out = out_arg;
-#define WX_ORDER() (order_arg)
-#endif
+#define WX_ORDER() (StripOrder{order_c.mode, order_c.nl, order_c.nr0, order_c.arrive, order_c.epoch, order_c.epoch_want, order_c.edge_list, order_c.prio})
   __shared__ WetRing rings[WX_WET_WPB];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   WetRing &rg = rings[wave];
   // Everything the wave reads from the context goes through the constant address space: scalar loads that the compiler may
   // issue (and re-issue) anywhere. Through a generic pointer every such load behind the kernel's first store becomes a VECTOR
   // load with a uniform address, and waiting for it means waiting for the row prefetch issued just before (one in-order counter).
-#if WX_WET_UNI_COPY
-  const Uni u = ctx->u; // read before the first store of the kernel: scalar loads, kept in SGPRs
-#else
   CUni &u = as_constant(ctx->u);
-#endif
   const Geo g = ctx->g;
   const CFloatP initial_T = as_constant(ctx->initial_T), snd_T = as_constant(ctx->snd_T), snd_W = as_constant(ctx->snd_W), snd_Vel = as_constant(ctx->snd_Vel);
   const int X = g.X, Y = g.Y;
@@ -625,10 +568,6 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
   int sq3 = (r - 3 + 12) % WQ; // ring slot of row r-3 (base / wall / water planes)
   // wrapped (REPEAT) row indices of rows r+1, r-1 .. r-4, advanced by one per step (a general modulo costs ~20 scalar instructions)
   int yw_p1 = wrapmod(r + 1, Y), yw_m1 = wrapmod(r - 1, Y), yw_m2 = wrapmod(r - 2, Y), yw_m3 = wrapmod(r - 3, Y), yw_m4 = wrapmod(r - 4, Y);
-#if WX_WET_PRIO_ROTATE
-  // wave slot within the SIMD (HW_ID.WAVE_ID): the waves that share a SIMD have different ones
-  const int prio_phase = (int)__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);
-#endif
   int t = 0;
   // WARM: one of the first eight steps of the segment, in which the stages come alive one after the other (t >= ...); the steady-state
   // instantiation has none of those wave-uniform branches -- every one of them is a control-flow merge at which the carried values of
@@ -636,14 +575,6 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 #define WX_T_GE(n) (!WARM || t >= (n))
   auto step = [&](auto warm_tag) __attribute__((always_inline)) {
     constexpr bool WARM = decltype(warm_tag)::value;
-#if WX_WET_PRIO_ROTATE
-    { // the SIMD issues the OLDEST ready wave first: without this the first-dispatched waves run ~30 % faster than the last ones
-      const int pr = (t + prio_phase) % 3;
-      if (pr == 0) __builtin_amdgcn_s_setprio(0);
-      else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(2);
-    }
-#endif
     const float4 b_cur = pf_b, q_up = pf_q;       // base row r, water row r-2
     int w_raw = pf_w;
     const float lx_cur = pf_lx, l0x_cur = pf_l0x, l0y_cur = pf_l0y; // light row r-2
@@ -672,9 +603,6 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 #ifdef WX_STAGE_MARKS
     asm volatile("; @@prefetch");
 #endif
-#if WX_WET_PRIO_MEM
-    __builtin_amdgcn_s_setprio(WX_WET_PRIO_MEM); // the step's loads and stores go out ahead of the other waves' arithmetic
-#endif
     // ---- software prefetch: the loads of the next step are in flight while this one computes ----
     if (r < y_hi + 3) {
       {
@@ -682,7 +610,7 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
         pf_b = ld_row(in.base + e, lo16);
         pf_w = ld_row(WX_WALL_RAW + e, lo4);
       }
-      if (WX_WET_SKIP_LOADS != 1 || WX_T_GE(2)) { // (the first warm-up steps of a segment only feed velocity / curl: no water, no light yet)
+      if (WX_T_GE(2)) { // (the first warm-up steps of a segment only feed velocity / curl: no water, no light yet)
         const int rl = r - 1;
         const size_t ew = (size_t)yw_m1 * X;
         pf_q = ld_row(in.water + ew, lo16);
@@ -694,8 +622,8 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
         pf_l0y = ld_row(in.l0.y + ew, lo4);
         // light_0's sunlight is only read by cells next to a wall and by surface wall cells, of rows r-1 and r-2: skipped while
         // none of the wall rows loaded so far (r-3 .. r) has such a cell (in even iterations the load coincides with pf_lx anyway)
-        if (WX_WET_SKIP_LOADS) WX_H_SET(h_near, __any(w_cur.y <= 1));
-        if (!WX_WET_SKIP_LOADS || (h_near & 15u)) pf_l0x = ld_row(in.l0.x + ew, lo4);
+        WX_H_SET(h_near, __any(w_cur.y <= 1));
+        if (h_near & 15u) pf_l0x = ld_row(in.l0.x + ew, lo4);
       }
       if (HAS_FB) {
         // does any of the (up to three) 64x16 tiles under this strip hold feedback in row r-2? The flag byte was loaded one step
@@ -712,21 +640,12 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
         {
           // always the same two loads -- from the textures' row, or from a row of zeros (L2 resident) where the tiles are known
           // to be zero: a conditional load would make the number of loads per step, which the waits are built on, vary
+          // (0.974-0.977 ms with the always-issued loads, 1.012-1.021 with loads only where a tile holds feedback)
           const size_t e = (size_t)yw_m2 * X;
-#if WX_WET_FB_COND
-          if (fb_have) {
-            pf_fb = ld_row(in.fb + e, lo12);
-            pf_dep = ld_row((dep_have && (!WX_WET_DEP_NEAR || (h_near & 4u))) ? in.dep + e : reinterpret_cast<const float2 *>(in.zero_row), lo8);
-          } else {
-            pf_fb = make_float3(0.f, 0.f, 0.f);
-            pf_dep = make_float2(0.f, 0.f);
-          }
-#else
           pf_fb = ld_row(fb_have ? in.fb + e : reinterpret_cast<const float3 *>(in.zero_row), lo12);
           // (the deposition texture is only read by surface wall cells, boundaryShader.frag:390-475: rows without a cell at or next to
           // a wall take it from the row of zeros too)
-          pf_dep = ld_row((dep_have && (!WX_WET_DEP_NEAR || (h_near & 4u))) ? in.dep + e : reinterpret_cast<const float2 *>(in.zero_row), lo8);
-#endif
+          pf_dep = ld_row((dep_have && (h_near & 4u)) ? in.dep + e : reinterpret_cast<const float2 *>(in.zero_row), lo8);
         }
 #endif
 #if !defined(WX_ABL_FB_NOFLAG) && !defined(WX_ABL_FB_NOLOAD)
@@ -754,9 +673,6 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 #endif
     }
     st_valid = false;
-#if WX_WET_PRIO_MEM
-    __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef WX_STAGE_MARKS
     asm volatile("; @@velocity");
 #endif
@@ -814,7 +730,7 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 #else
         // free air (no wall within one cell, terrain at least 8 rows below) in every lane that feeds something: the
         // branch-free instantiation. Most rows of most strips; the general one handles everything else.
-        if (WX_ABL_FORCE_AIR || (WX_WET_AIR && __all(lane < 2 || lane > 60 || air_cell(w00, a.wall(-1, 0), wD, a.wall(1, 0), a.wall(0, 1)))))
+        if (WX_ABL_FORCE_AIR || __all(lane < 2 || lane > 60 || air_cell(w00, a.wall(-1, 0), wD, a.wall(1, 0), a.wall(0, 1))))
           boundary_cell<true>(u, iterNum, iterI, g, initial_T, col, yb, a, bb, bq, bwl);
         else
           boundary_cell<false>(u, iterNum, iterI, g, initial_T, col, yb, a, bb, bq, bwl);
@@ -879,12 +795,8 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 #endif
           // (the list: read from the kernel-argument segment HERE, in the rare branch -- nothing of it is live in the loop; the edge strips
           // of a split iteration have a list of their own, consumed on the comm stream before the halo is packed)
-#if WX_WET_ARGS_MEM && defined(__HIP_DEVICE_COMPILE__)
           const __attribute__((address_space(4))) WetFixList &fix =
               *(const __attribute__((address_space(4))) WetFixList *)(ka_c + offsetof(KArgs, fix) + (edge_list ? sizeof(WetFixList) : 0));
-#else
-          const WetFixList &fix = edge_list ? fix_edge_arg : fix_arg;
-#endif
           if (fix.fastest) atomicMax(fix.fastest, __float_as_int(m)); // (m >= 0.9 or NaN: the bit patterns of positive floats order like ints)
           if (n_add) {
             int at = atomicAdd(fix.count, n_add);
@@ -900,8 +812,8 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
       fast = false;
 #endif
       if (fast) {
-        if (WX_ABL_FORCE_AIR || (WX_WET_AIR && (h_nowall & 7u) == 7u)) { // (wave-uniform) plain instead of wall-aware interpolation, no wall branch
-          if (WX_WET_ZW0 && (h_zw0 & 7u) == 7u) // ... and nothing to interpolate in the precipitation-visual / smoke channels
+        if (WX_ABL_FORCE_AIR || (h_nowall & 7u) == 7u) { // (wave-uniform) plain instead of wall-aware interpolation, no wall branch
+          if ((h_zw0 & 7u) == 7u) // ... and nothing to interpolate in the precipitation-visual / smoke channels
           {
 #ifdef WX_STAGE_MARKS
             asm volatile("; @@advair");
@@ -933,7 +845,7 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 #ifdef WX_ABL_NOLIGHT
         st_l = make_float4(la.sun_at(0, r - 4), la.ir_up_at(r - 5), lz1, ab.w);
 #else
-        if (WX_ABL_FORCE_AIR || (WX_WET_AIR && __all(lane < WLO || lane >= WLO + WOUT || (awl.y != 0 && awl.z != 1))))
+        if (WX_ABL_FORCE_AIR || __all(lane < WLO || lane >= WLO + WOUT || (awl.y != 0 && awl.z != 1)))
           st_l = lighting_cell<true>(u, g, col, r - 4, la);
         else
           st_l = lighting_cell<false>(u, g, col, r - 4, la);
@@ -983,9 +895,9 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
   };
   // (a segment has at least one row: at least nine steps)
   for (; t < 8; r++, t++) step(std::true_type{});
-  if (WX_WET_UNROLL2 && !HAS_FB && !OPT_OUT) { // (doubling the other instantiations re-measured at four waves per SIMD: neutral, profiles/r04_unroll_variants_four_waves.txt)
+  if (!HAS_FB && !OPT_OUT) { // (doubling the other instantiations re-measured at four waves per SIMD: neutral, profiles/r04_unroll_variants_four_waves.txt)
     // two steps per loop iteration: the values carried from step to step (prefetched rows, the previous rows' registers, the deferred
-    // stores) change registers between the two copies instead of being moved: -1.4 % without feedback loads; WITH them (particles on)
+    // stores) change registers between the two copies instead of being moved: -1.2 .. -1.6 % at 16384x2048 without feedback loads; WITH them (particles on)
     // the doubled loop is 4-6 % slower, and the display-writing one (every tenth iteration) loses 2-8 %: only the plain instantiation
     // is doubled (profiles/r03_unroll_variants.txt)
     for (; r <= y_hi + 3;) {
@@ -994,11 +906,6 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
       if (r > y_hi + 3) break;
       step(std::false_type{});
       r++;
-#if WX_WET_UNROLL2 >= 3
-      if (r > y_hi + 3) break;
-      step(std::false_type{});
-      r++;
-#endif
     }
   } else {
     for (; r <= y_hi + 3; r++) step(std::false_type{});
@@ -1017,12 +924,8 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
     if (out.t_disp && st_td) st_row(out.t_disp + e, so4, st_ab.w);
   }
   {
-#if WX_WET_ARGS_MEM && defined(__HIP_DEVICE_COMPILE__)
     const __attribute__((address_space(4))) VxTrack &vc = *(const __attribute__((address_space(4))) VxTrack *)(ka_c + offsetof(KArgs, vx));
     vx_track_commit(VxTrack{vc.max_bits, vc.violation, vc.limit, vc.zone_l, vc.zone_r, vc.limit_in}, vx_seen, lane, strip);
-#else
-    vx_track_commit(vx_arg, vx_seen, lane, strip);
-#endif
   }
   if (sig_edge) strip_order_arrive(WX_ORDER(), lane, true); // the halo exchange may pack this strip's columns
 #undef WX_ORDER
@@ -1270,8 +1173,8 @@ __global__ __launch_bounds__(256) void k_wet_fix(const FullCtx *__restrict__ ctx
 // OLDEST ready wave first. With one round of 9 long segments the first-dispatched waves run at 6000 cycles / row and the last at 8100;
 // when the old ones retire nothing refills their slots and the young ones finish at 1-2 waves per SIMD, which cannot hide their own
 // memory latency: 77 % of the SIMD-time is used, against 89 % with four rounds, and that costs more than the warm-up rows saved
-// (0.87-0.90 ms against 0.835-0.845). Rotating s_setprio per step (WX_WET_PRIO_ROTATE=1) equalises the rates but marches the waves
-// of a SIMD in lock-step into their memory waits (-5 %); giving older segments more rows (WX_WET_SKEW) shifts the rates with it.
+// (0.87-0.90 ms against 0.835-0.845). Rotating s_setprio per step equalises the rates but marches the waves of a SIMD in lock-step
+// into their memory waits (-5 %); giving older segments more rows shifts the rates with it.
 // Halo columns are not the problem: an s_barrier per row step, which keeps the four strips of a workgroup on the same rows, lowers
 // FETCH_SIZE by 2 % and costs 6 % of time -- the neighbouring strips' lines already hit in L2; what the counters show above the
 // algorithmic bytes (reads 1.15x) is the 8 warm-up rows per segment.
@@ -1310,7 +1213,7 @@ inline int wet_capacity()
 }
 inline double wet_alpha()
 {
-  double alpha = WX_WET_ALPHA_DEFAULT;
+  double alpha = 1.0; // cost of a row below air_from_row relative to a free-air row when the segment borders are placed
   if (const char *e = wx_tune_env("WX_WET_ALPHA")) alpha = atof(e) >= 1.0 ? atof(e) : alpha;
   return alpha;
 }
@@ -1329,7 +1232,7 @@ inline WetLaunch wet_launch_shape(const Geo &g, int air_from_row, int bands_mode
   // (129 strips) -15 / -8 % with bands, 8000 x 300 ... 500 (143 strips) -5 % (x 350: +2.5 %), 10000 x 480 (179) +9 %, 12000 and 16000
   // columns even or worse: fewer than 146 strips. The minimum segment height below is at its optimum for every reference size.
   const int strips_all = (g.X + WOUT - 1) / WOUT;
-  bool bands = bands_mode >= 2 ? g.Y >= 16 : (bands_mode != 0 && WX_WET_BANDS && (g.Y >= 8 * 64 || (strips_all < 146 && g.Y >= 128)));
+  bool bands = bands_mode >= 2 ? g.Y >= 16 : (bands_mode != 0 && (g.Y >= 8 * 64 || (strips_all < 146 && g.Y >= 128)));
   if (const char *e = wx_tune_env("WX_WET_BANDS")) bands = atoi(e) >= 2 ? g.Y >= 16 : (atoi(e) != 0 && g.Y >= 8 * 64); // (2: tests force it on small grids)
   const int Y = bands ? (g.Y + 7) / 8 : g.Y; // (bands: the shape of ONE band; the kernel clips it to the band's own height)
   w.segs.bands = bands ? 1 : 0;
@@ -1353,19 +1256,16 @@ inline WetLaunch wet_launch_shape(const Geo &g, int air_from_row, int bands_mode
   // workgroups per segment: 8 XCD column blocks x ceil(strips of the block / waves per workgroup); the device holds capacity / WPB
   const int wg_per_seg = bands ? 8 * ((w.n_strips + WX_WET_WPB - 1) / WX_WET_WPB) : 8 * (((w.n_strips + 7) / 8 + WX_WET_WPB - 1) / WX_WET_WPB);
   int n_seg = (int)((long long)rounds * (wet_capacity() / WX_WET_WPB) / wg_per_seg);
-  double skew = 0.0; // > 0: earlier-dispatched (lower) segments get more rows: the SIMD issues its OLDEST ready wave first
-  if (const char *e = wx_tune_env("WX_WET_SKEW")) skew = atof(e);
-  if (const char *e = wx_tune_env("WX_WET_SEG")) n_seg = atoi(e) > 0 ? (Y + atoi(e) - 1) / atoi(e) : n_seg;
   n_seg = n_seg < 1 ? 1 : (n_seg > WMAXSEG ? WMAXSEG : n_seg);
   if (n_seg > (Y + minrows - 1) / minrows) n_seg = (Y + minrows - 1) / minrows; // (8 warm-up rows per segment are redundant work)
   const int A = (air_from_row < 0 || air_from_row > Y) ? 0 : air_from_row;           // unknown: uniform segments
   const double total = alpha * A + (Y - A);
-  // weights of the segments in dispatch order (bottom first): 1 + skew/2 .. 1 - skew/2, or an explicit list
+  // weights of the segments in dispatch order (bottom first): equal, the tail shape below, or an explicit list
   // WX_WET_SPEC="29x1,5x0.5,5x0.25" (count x weight, ...; the counts give the number of segments): short segments LAST shorten the
   // drain phase of the launch, in which finished waves are not replaced
   double wt[WMAXSEG];
-  for (int sg = 0; sg < n_seg; sg++) wt[sg] = 1.0 + skew * (0.5 - (n_seg > 1 ? (double)sg / (n_seg - 1) : 0.5));
-  if (WX_WET_TAIL && skew == 0.0 && !wx_tune_env("WX_WET_SEG") && !wx_tune_env("WX_WET_NOTAIL")) {
+  for (int sg = 0; sg < n_seg; sg++) wt[sg] = 1.0;
+  if (!wx_tune_env("WX_WET_NOTAIL")) {
     // default shape: (rounds - 1) rounds of full segments, then about half a round each of segments of weight 1/2, 1/4 and 1/8.
     // The launch ends with a drain phase in which finished waves are not replaced; short segments at the end of the dispatch order
     // make it short: -5 % kernel time against equal segments (interleaved A/B, profiles/r02_wet_tail_shape.txt)
@@ -1505,8 +1405,7 @@ inline void launch_wet_fix(float iterNum, const FullCtx *ctx, const WetIn &in, c
   // four entries per workgroup with room for four times the last list (its length varies from iteration to iteration: room for twice
   // cost the particle flow 6 us, 21 -> 27), 32 .. 512 workgroups (wgs: the edge group of a slab -- a few strips -- asks for 64); the
   // list is walked grid-stride, so any size is correct
-  int want = last < 0 ? 512 : (last > 0 ? std::min(512, std::max(32, last)) : 32);
-  if (const char *e = wx_tune_env("WX_FIX_WGS")) want = atoi(e) > 0 ? atoi(e) : want; // (tuning)
+  const int want = last < 0 ? 512 : (last > 0 ? std::min(512, std::max(32, last)) : 32);
   const dim3 grid(wgs > 0 ? wgs : want), block(256);
   if (opt_out)
     hipLaunchKernelGGL((k_wet_fix<true>), grid, block, 0, stream, ctx, iterNum, in, out, fix.count, fix.cells, fix.cap, overflow, fix.hint);

@@ -784,15 +784,6 @@ static int split_launch_ready(wx_sim *s, bool need_fix_list)
   }
   if (need_fix_list && !s->split.edge_fix.cells) {
     if (int rc = edge_list_create(s, "strips'")) return rc;
-    if (wx_tune_env("WX_SPLIT_PREWARM") && s->comm_stream && s->full_ctx) {
-      // (experiment) the fix kernel needs 652 bytes of scratch per lane: let the comm stream's hardware queue get its scratch ring now,
-      // while nothing on the chip is polling for the exchange this kernel is part of
-      hipStreamSynchronize(s->stream);
-      WetIn in{};
-      WetOut out{};
-      launch_wet_fix(0.f, s->full_ctx, in, out, s->split.edge_fix.wet(&s->state->fastest_bits), &s->state->fix_overflow, false, s->comm_stream, 64);
-      hipStreamSynchronize(s->comm_stream);
-    }
   }
   return WX_OK;
 }
@@ -887,7 +878,6 @@ template <class Launch> int split_iteration(wx_sim *s, int edge_mode, int nl, in
     }
     ord.prio = WX_SPLIT_PRIO;
     if (const char *e = wx_tune_env("WX_SPLIT_PRIO")) ord.prio = atoi(e);
-    if (const char *e = wx_tune_env("WX_SPLIT_NOFENCE")) ord.nofence = atoi(e);
     sp.check = true;
     const int items = launch(s->stream, 0, -1, 0, 0, &ord, false);
     if (edge_mode & 1) {
@@ -975,9 +965,8 @@ int iterate_march_wet(wx_sim *s, bool opt_out, bool precip, int edge_mode = 0)
   if (!s->fix.cells) { // (once per handle) room for a quarter of the grid's cells, at most 8 M entries
     size_t cap = std::min<size_t>(std::max<size_t>(ncell(s) / 4, 1u << 16), 1u << 23);
     if (s->opt.fix_cap_request > 0) cap = (size_t)s->opt.fix_cap_request; // (WX_OPT_FIX_CAP; tests: provoke the overflow report)
-    const bool hint = !(wx_tune_env("WX_FIX_HINT") && atoi(wx_tune_env("WX_FIX_HINT")) == 0); // (WX_FIX_HINT=0: tuning)
     // words: {entries, arrival ticket of the fix pass, what the hint word was last told, -}: the fix pass leaves the first two at 0
-    if (!s->fix.create(s->stream, cap, 4, 2, hint)) return fail(s, WX_E_NOMEM, "wx_step: %zu bytes for the exact-path cell list", cap * sizeof(int2));
+    if (!s->fix.create(s->stream, cap, 4, 2, true)) return fail(s, WX_E_NOMEM, "wx_step: %zu bytes for the exact-path cell list", cap * sizeof(int2));
   }
   {
     ProfScope ps(s, K_MARCH_WET);
@@ -2712,7 +2701,7 @@ static int halo_pack_impl(wx_sim *s, void *const dev_buf[2])
   HaloPtrs f{s->base[0], s->water[1], s->light[0], s->light[1], s->run.light_planar ? s->lp[0] : none, s->run.light_planar ? s->lp[1] : none, s->wall[0],
              s->pool.remote ? s->fb : nullptr, s->pool.remote ? s->dep : nullptr};
   hipStream_t st = exchange_stream(s);
-  if (st != s->stream && s->split.gate_pending && s->split.gate_wet && !wx_tune_env("WX_SPLIT_FIX_ON_COMM")) {
+  if (st != s->stream && s->split.gate_pending && s->split.gate_wet) {
     // ONE ordered launch of the WET kernel: its edge strips left exact-path cells on their own list. Consuming it HERE, on the comm
     // stream, behind a gate kernel would let the pack start while the interior still marches -- built and measured in round 5, and
     // withdrawn: k_wet_fix needs 652 bytes of scratch per lane, which the runtime hands out per dispatch ("use once") only when the
@@ -2728,9 +2717,6 @@ static int halo_pack_impl(wx_sim *s, void *const dev_buf[2])
     // the latest iteration was ONE ordered launch whose edge strips report on a device word: a one-wave gate kernel waits for them (the
     // interior strips are still marching), then the pack may read (dry stencil: no exact-path list, every kernel here is scratch-free)
     hipLaunchKernelGGL(k_strip_gate, dim3(1), dim3(64), 0, st, s->split.sync_words, s->split.arrive_target);
-    if (s->split.gate_wet && !wx_tune_env("WX_SPLIT_NOFIX2")) {
-      launch_wet_fix(s->split.gate_iter, s->full_ctx, s->split.gate_in, s->split.gate_out, s->split.edge_fix.wet(&s->state->fastest_bits), &s->state->fix_overflow, s->split.gate_opt_out, st, 64);
-    }
     s->split.gate_pending = false;
     s->split.gate_passed = true;
   } else if (st != s->stream && s->split.gate_passed) {
