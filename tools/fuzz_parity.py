@@ -19,6 +19,8 @@ the rest, and between them any of SCRIPT_ACTIONS:
                 every field is compared afterwards (BASE_DISP and WATER_0 belong to the last display iteration, not to the edit)
     reupload    the current state uploaded again (droplets too)          lightning   wx_lightning_set, mirrored
     pair_stats, fastest, water_free, sync, profile (on / off + read)      calls with side effects, interleaved
+--mode impulse: the impulse-lattice scenes of tests/impulse_scenes.py (lone single-cell triggers; grid, kind, pitch, offset and configuration
+drawn by draw_impulse from a generator of its own), run by run_impulse_case.
 After the last step everything is read. Fields are compared where both sides define them alike (CURL / VORT / EMITTED after a step that
 ran the passes that store them). The recipe, script included, is printed and flushed BEFORE the case runs and reproduces the case alone.
 A WxError other than the exact path's reported overflow is not expected: the run ends there (exit 2). This is not a tool to provoke
@@ -684,6 +686,148 @@ def run_setup_case(pkg, E, c):
     return bad, info
 
 
+# ---- --mode impulse: the impulse-lattice scenes of tests/impulse_scenes.py (lone single-cell triggers at every kernel phase) ----
+# configuration name -> how the case is run: the dry stencil's pass mask, handle options, the iterations of each step, steps cut into
+# WX_OVERLAP_MORE_TO_COME pieces
+IMPULSE_CONFIGS = {
+    # steps (1, 1, 3): the planted trigger meets the DISPLAY iteration (the last one of a step); (3, 2): a plain iteration; pieces: every
+    # step is cut into a first iteration with WX_OVERLAP_MORE_TO_COME and the rest, so the trigger meets a piece that skips the display stores
+    "wet": {}, "wet_plain": {"steps": (3, 2)}, "wet_stored": {"water0_on_demand": 0}, "wet_pieces": {"steps": (3, 2), "pieces": True}, "perpass": {"kernel_set": 0},
+    "wet_bands0": {"bands": 0}, "wet_bands1": {"bands": 1}, "wet_bands2": {"bands": 2},
+    "dry_single": {"dry": True, "pairs": 0}, "dry_single_plain": {"dry": True, "pairs": 0, "steps": (3, 2)}, "dry_perpass": {"dry": True, "kernel_set": 0},
+    # pairs: iterations 1-2 and 3-4 are pairs, 5 runs the one-iteration kernel. A fresh handle's hint word starts at 1, so its first
+    # pair runs the TAINT instantiation (launch_march_dry2), and so does the second while the first left entries. "prime": a quiet pair
+    # on the background first -- its empty post pass sets the hint to 0 -- then the scene is uploaded into the SAME handle: the trigger
+    # meets the PLAIN instantiation (first-iteration fast cells inline through global memory, second-iteration ones recorded lane by lane)
+    "dry_pairs": {"dry": True, "pairs": 1, "steps": (2, 2, 1)}, "dry_pairs_plain": {"dry": True, "pairs": 1, "steps": (2, 2, 1), "prime": True},
+    "dry_pairs_bands0": {"dry": True, "pairs": 1, "steps": (2, 2, 1), "bands": 0}, "dry_pairs_bands1": {"dry": True, "pairs": 1, "steps": (2, 2, 1), "bands": 1},
+    "dry_pairs_bands2": {"dry": True, "pairs": 1, "steps": (2, 2, 1), "bands": 2},
+    # droplets in the DEFAULT splat order (fp32 atomics): with lone sprites every texel receives one deposit -- order-free, so bit for bit
+    "splat_atomic": {"splat_order": 0}, "splat_atomic_perpass": {"splat_order": 0, "kernel_set": 0},
+}
+
+
+def impulse_module():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    return importlib.import_module("impulse_scenes")
+
+
+def draw_impulse(rng, I):
+    """A generator of its own (draw_case and the pinned digests of its sequences are untouched): grid, kind, pitch, offset, configuration."""
+    X = int(rng.choice([56, 60, 64, 112, 120, 448]) * int(rng.integers(2, 12)) + int(rng.integers(-2, 3))) if rng.random() < 0.5 else int(rng.integers(150, 3000))
+    Y = int(rng.integers(24, 400))
+    dry = bool(rng.random() < 0.4)
+    kind = str(rng.choice(I.DRY_KINDS if dry else I.KINDS))
+    pitch = list(I.DROPLET_PITCH) if kind == "droplet" else [int(rng.integers(I.MIN_DX + 1, 140)), int(rng.integers(I.MIN_DY + 1, 24))]
+    cfgs = [k for k, v in IMPULSE_CONFIGS.items() if bool(v.get("dry")) == dry and (("splat_order" in v) == (kind == "droplet"))]
+    return {"sweep": "drawn", "X": X, "Y": Y, "kind": kind, "pitch": pitch, "offset": [int(rng.integers(0, X)), int(rng.integers(0, pitch[1]))],
+            "background": "air" if dry or rng.random() < 0.5 else "terrain", "config": str(rng.choice(cfgs))}
+
+
+def run_impulse_case(pkg, E, wx_oracle, c, I=None):
+    """One impulse-lattice case: the handle, configured as c["config"] says, against the oracle after every step -- every field both
+    define, bit for bit; a mismatch names the nearest site and its phases. info: the sites, wx_fastest_velocity after the first step
+    and what the oracle says it must be (wet marching kernel), wx_pair_stats, the launches of the pair kernel (profile counter) and the oracle's
+    largest velocity in the first / second iterations of the pairs (the second always records tiles, the first while the TAINT instantiation runs), the iteration up to which the droplets' sprites stayed disjoint."""
+    I = I or impulse_module()
+    cfg = IMPULSE_CONFIGS[c["config"]]
+    X, Y, kind, dry = c["X"], c["Y"], c["kind"], bool(cfg.get("dry"))
+    base, water, wall, drops, sites = I.build_case(c)
+    nd = 0 if drops is None else len(drops)
+    u = I.scene_uniforms(kind, Y, dry=dry)
+    p = pkg.params.fill_struct(pkg.params.WxParams(), u)
+    h = E.Handle(X, Y, nd)
+    o = wx_oracle.OracleSim(X, Y, nd)
+    bad, info = [], {"sites": len(sites), "blown_up": False}
+    try:
+        marching = cfg.get("kernel_set", 1) == 1
+        pairs = dry and marching and cfg.get("pairs", 1) == 1
+
+        def options():
+            h.set_option(h.OPT_KERNEL_SET, cfg.get("kernel_set", 1))
+            h.set_option(h.OPT_DRY_KERNEL, 1)
+            h.set_option(h.OPT_DRY_PAIRS, cfg.get("pairs", 1))
+            h.set_option(h.OPT_ROW_BANDS, cfg.get("bands", 1))
+            h.set_option(h.OPT_WATER0_ON_DEMAND, cfg.get("water0_on_demand", 1))
+            if nd:
+                h.set_option(h.OPT_SPLAT_ORDER, cfg["splat_order"])
+
+        if cfg.get("prime"):  # a quiet pair first: the handle hears of an empty exact-path list
+            quiet = I.build_case(c, plant=False)
+            h.upload(*quiet[:3])
+            h.set_params(p, u["initial_T"])
+            options()
+            h.step(2)
+            info["prime_pair_stats"] = h.pair_stats()  # (synchronises: the hint word is the host's to read at the next launch)
+        h.upload(base, water, wall, drops)
+        o.upload(base, water, wall, drops)
+        h.set_params(p, u["initial_T"])
+        o.set_params(u)
+        h.iter = o.iter = 0
+        options()
+        if dry:
+            info["water_free"] = h.water_free()
+        if pairs:
+            h.profile(True)
+        if not dry and marching:  # what the exact path of the wet kernel must report after the first iteration: the largest post-boundary component
+            t = wx_oracle.OracleSim(X, Y, 0)
+            t.upload(base, water, wall)
+            t.set_params(dict(u, pass_mask=7, enablePrecipitation=0))
+            t.step(1)
+            v = np.abs(t.field("BASE_CUR")[..., :2]).max()
+            t.close()
+            info["fastest_expected"] = float(v) if v >= np.float32(0.9) else 0.0
+        fields = ["BASE_CUR", "BASE_DISP", "WATER_CUR", "WATER_0", "WALL_CUR"] if dry else list(GRID_FIELDS)
+        done, v1, v2, exact = 0, 0.0, 0.0, True
+        steps = cfg.get("steps", (1, 1, 3))
+        for n in steps:
+            if cfg.get("pieces") and n > 1:
+                h.step(1, 4)
+                h.step(n - 1)
+            else:
+                h.step(n)
+            for k in range(n):
+                before = o.field("DROPS") if nd else None
+                in_pair = (k % 2 == 1) or (k + 1 < n)  # the host pairs iterations (0, 1), (2, 3) ... of a step; an odd one out runs alone
+                if pairs and in_pair:  # the velocities the two iterations of a pair advect with
+                    t = wx_oracle.OracleSim(X, Y, 0)
+                    t.upload(o.field("BASE_CUR"), o.field("WATER_CUR"), o.field("WALL_CUR"))
+                    t.set_params(dict(u, pass_mask=1))
+                    t.step(1)
+                    v = float(np.abs(t.field("BASE_CUR")[..., :2]).max())
+                    v1, v2 = max(v1, v if k % 2 == 0 else 0.0), max(v2, v if k % 2 == 1 else 0.0)
+                    t.close()
+                o.step(1)
+                if nd and exact and I.deposits_per_texel(before, o.field("DROPS"), X, Y) > 1:
+                    exact = False
+                    info["sprites_disjoint_until"] = done + k
+            done += n
+            if nd and not exact:  # two deposits in one texel: the atomic order decides the last bit from here on
+                break
+            for f in fields + (["PRECIP_FB", "PRECIP_DEP", "LIGHTNING"] if nd else []):
+                a, b = h.read_rect(f), o.field(f)
+                if not np.array_equal(a, b):
+                    bad.append({"field": f, "after_iterations": done, "what": I.describe_difference(f, a, b, sites, X) if a.ndim == 3 else "differs"})
+            if nd and not np.array_equal(h.read_particles(), o.field("DROPS")):
+                bad.append({"field": "DROPS", "after_iterations": done})
+            if done == steps[0] and not dry and marching:
+                info["fastest"] = h.fastest_velocity()
+            if bad:
+                break
+        if nd and exact:
+            info["sprites_disjoint_until"] = done
+        if pairs:
+            info["pair_stats"], info["first_iteration_fastest"], info["second_iteration_fastest"] = h.pair_stats(), v1, v2
+            info["first_iteration_fast"], info["second_iteration_fast"] = v1 >= 0.9, v2 >= 0.9
+            info["pair_launches"] = h.profile_read().get("march_dry2_two_iterations_per_launch", (0.0, 0))[1]
+        ob = o.field("BASE_CUR")
+        info["blown_up"] = not bool(np.isfinite(ob).all() and np.abs(ob[..., :2]).max() < 1e4)
+    finally:
+        h.close()
+        o.close()
+    return bad, info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=1)
@@ -692,7 +836,7 @@ def main():
     ap.add_argument("--max-cells", type=int, default=600000)
     ap.add_argument("--interleave", action="store_true", help="oracle mode: half of the cases run with a second handle alive, steps in turn")
     ap.add_argument("--big", action="store_true", help="grids of 1000-9000 x 512-2100 cells (use with --max-cells 8000000)")
-    ap.add_argument("--mode", choices=["oracle", "group", "setup", "script"], default="oracle",
+    ap.add_argument("--mode", choices=["oracle", "group", "setup", "script", "impulse"], default="oracle",
                     help="oracle: one handle against the CPU oracle; group: N slabs against one handle; script: one handle against the oracle through a drawn host script")
     ap.add_argument("--only", type=int, default=-1, help="run only case K of the seed's sequence")
     ap.add_argument("--first", type=int, default=0, help="skip the cases before this one (they are still drawn: same sequence)")
@@ -713,6 +857,22 @@ def main():
     totals = {k: 0 for k in SCRIPT_ACTIONS}
     t0 = time.time()
     failures, ran, reported, compared = [], 0, 0, 0
+    if a.mode == "impulse":  # a generator, a loop and a summary of its own: draw_case's sequences are untouched
+        I = impulse_module()
+        n_bad = ran = 0
+        for k in range(a.cases):
+            c = draw_impulse(rng, I)
+            if (a.only >= 0 and k != a.only) or k < a.first or c["X"] * c["Y"] > a.max_cells:
+                continue
+            if k > a.last or time.time() - t0 > a.seconds:
+                break
+            print(f"case {k} recipe: {json.dumps(c)}", flush=True)  # BEFORE it runs
+            bad, info = run_impulse_case(pkg, E, wx_oracle, c, I)
+            ran += 1
+            n_bad += 1 if bad and not info["blown_up"] else 0
+            print(f"case {k:4d} {c['X']:5d}x{c['Y']:<5d} {c['kind']:14s} {c['config']:20s} {json.dumps(info)}  {'MISMATCH ' + json.dumps(bad) if bad else 'ok'}", flush=True)
+        print(json.dumps({"mode": a.mode, "seed": a.seed, "cases_run": ran, "mismatching_cases": n_bad, "seconds": round(time.time() - t0, 1)}))
+        sys.exit(1 if n_bad else 0)
     for k in range(a.cases):
         c = draw_case(rng, a.max_cells, a.big)
         if a.mode == "group":
