@@ -80,6 +80,26 @@ GUI_DEFAULTS: Dict[str, Any] = {
     "windUnit": "SPEED_UNIT_KMH",
 }
 
+# (min, max) of every control of the reference's GUI that the simulation step reads (app.js:3481-3745, the `.add(guiControls, ...)`
+# calls of setupDatGui), keyed like GUI_DEFAULTS. The ONE table of those ranges: tools/fuzz_parity.py draws its slider settings
+# from it and oracle/golden/gen_golden.py the sliders64 fixtures. Order matters to the fuzzer's pinned draws: append only.
+GUI_RANGES: Dict[str, Any] = {
+    "vorticity": (0.0, 0.010), "dragMultiplier": (0.0, 1.0), "wind": (-1.0, 1.0), "globalDrying": (0.0, 0.0001), "globalHeating": (-0.001, 0.001),
+    "sunIntensity": (0.0, 2.0), "waterTemperature": (0.0, 40.0), "landEvaporation": (0.0, 0.0002), "waterEvaporation": (0.0, 0.0004),
+    "evapHeat": (0.0, 5.0), "meltingHeat": (0.0, 5.0), "condensationRate": (0.001, 0.020), "waterWeight": (0.0, 2.0),
+    "greenhouseGases": (0.0, 0.01), "waterGreenHouseEffect": (0.0, 0.01), "IR_rate": (0.0, 10.0), "soundingForcing": (0.0, 1.0),
+    # the precipitation folder (app.js:3679-3745)
+    "aboveZeroThreshold": (0.1, 2.0), "subZeroThreshold": (0.0, 1.0), "spawnChance": (0.00001, 0.0001), "snowDensity": (0.1, 0.9),
+    "fallSpeed": (0.0001, 0.001), "growthRate0C": (0.0001, 0.005), "growthRate_30C": (0.0001, 0.005), "freezingRate": (0.0005, 0.01),
+    "meltingRate": (0.0005, 0.01), "evapRate": (0.0001, 0.005),
+    # the window of globalDrying / globalHeating, in metres (app.js:3524, 3536: 0 .. simHeight; given here as fractions of simHeight)
+    "globalEffectsStartAlt": (0.0, 1.0), "globalEffectsEndAlt": (0.0, 1.0),
+    "sunAngle": (-10.0, 190.0),  # app.js:3586, degrees
+    # not a dat.GUI control: the start dialog's height slider (index.html:345); with dryLapseRate (no control at all) it makes the
+    # dryLapse uniform and initial_T (app.js:5439, 5467-5474)
+    "simHeight": (5000.0, 15000.0),
+}
+
 DEG2RAD = 0.0174533  # app.js:340 (the reference's own rounded constant)
 RAD2DEG = 57.2957795
 

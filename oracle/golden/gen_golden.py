@@ -96,7 +96,7 @@ def js_uniforms(u: dict) -> dict:
 
 def run_fixture(name, X, Y, base, water, wall, drops, u, *, niter, dump_iters, perpass_iter=None, precip=False,
                 iter0=0, keep=("base_cur", "water_cur", "wall_cur", "light_0", "light_1", "water_0", "base_disp"), points=False,
-                dump_emitted=False, keep_particles=("drops", "lightning", "precip_fb", "precip_dep"), timeout=600.0):
+                dump_emitted=False, keep_particles=("drops", "lightning", "precip_fb", "precip_dep"), timeout=600.0, keep_perpass=None):
     tmp = tempfile.mkdtemp(prefix="wxgold_")
     np.ascontiguousarray(base, np.float32).tofile(os.path.join(tmp, "base.f32"))
     np.ascontiguousarray(water, np.float32).tofile(os.path.join(tmp, "water.f32"))
@@ -141,6 +141,8 @@ def run_fixture(name, X, Y, base, water, wall, drops, u, *, niter, dump_iters, p
             dt = np.int8 if "wall" in k else np.float32
             out[f"it{it}_{k}"] = _dec(v, dt).reshape(shapes.get(k, (Y, X, 4)))
     for k, v in res.get("perpass", {}).items():
+        if keep_perpass is not None and k not in keep_perpass:
+            continue
         dt = np.int8 if "wall" in k else np.float32
         out[f"pp_{k}"] = _dec(v, dt).reshape(shapes.get(k, (Y, X, 4)))
     if "inactiveDroplets" in res:
@@ -183,10 +185,12 @@ def fx_save100(precip: bool):
                        keep=("base_cur", "water_cur", "wall_cur", "light_0", "light_1"))
 
 
-def synth_terrain(X, Y, rng):
-    """Quad-aligned terrain with every wall type, snow, vegetation, moist warm air and cloud."""
-    gui = dict(pkg.params.GUI_DEFAULTS)
-    gui["sunAngle"] = 60.0
+def synth_terrain(X, Y, rng, gui=None):
+    """Quad-aligned terrain with every wall type, snow, vegetation, moist warm air and cloud. ``gui``: settings other than the
+    defaults with the sun at 60 degrees (the air is then built on THEIR initial_T and dryLapse)."""
+    if gui is None:
+        gui = dict(pkg.params.GUI_DEFAULTS)
+        gui["sunAngle"] = 60.0
     u = pkg.params.uniforms_from_gui(gui, Y)
     T0 = u["initial_T"]
     base = np.zeros((Y, X, 4), np.float32)
@@ -546,6 +550,160 @@ def fx_setup256():
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# sliders64: the same physics at OTHER VALUES of the uniforms. Every earlier fixture runs at (nearly) the GUI's defaults, several of
+# which are multiplicative identities (IR_rate = aboveZeroThreshold = 1); these scenes draw every control the simulation reads from
+# the range the reference's GUI offers (params.GUI_RANGES), stratified over the family.
+# ------------------------------------------------------------------------------------------------
+SLIDERS64_N = 8
+SLIDERS64_PRECIP = (1, 4, 7)       # precipitation on, hand-built droplets
+SLIDERS64_NOWRAP = (0, 2, 4, 6)    # wrapHorizontally off, with an input at the x edge that the non-wrapping distance decides
+SLIDERS64_SUN = (90.0, 60.0, 4.0, -8.0, 135.0, 176.5, 30.0, 188.0)  # noon exactly (the ray leaves through the top row), day, low sun, below the horizon (it enters from under row 0)
+SLIDERS64_PRECIP_ONLY = ("aboveZeroThreshold", "subZeroThreshold", "spawnChance", "snowDensity", "fallSpeed", "growthRate0C", "growthRate_30C",
+                         "freezingRate", "meltingRate", "evapRate", "meltingHeat")
+# (tool, (x, y), intensity) held for the whole run in the scenes without wrap: brush64's encoding of userInputType / userInputValues
+SLIDERS64_BRUSH = {0: (1, (0.02, 0.30), 0.04), 2: (12, (0.985, 0.12), 0.01), 4: (2, (0.01, 0.45), 0.02), 6: (4, (0.99, 0.50), 0.8)}
+
+
+def sliders64_gui(k):
+    """Settings of scene k: a Latin hypercube with a fixed seed over params.GUI_RANGES. Each control's range is cut into SLIDERS64_N
+    strata -- the lowest 6 %, the highest 6 %, and equal parts of what lies between -- and every scene gets another one, so that over
+    the family each control sits at its low end, at its high end and at interior values, never at its default. Controls only the
+    particle pass reads get their low / high / one interior stratum in the three scenes that run it."""
+    rng = np.random.default_rng(640048)
+    R, D = pkg.params.GUI_RANGES, pkg.params.GUI_DEFAULTS
+    n = SLIDERS64_N
+    strata = [(0.0, 0.06)] + [(0.06 + 0.88 * i / (n - 2), 0.06 + 0.88 * (i + 1) / (n - 2)) for i in range(n - 2)] + [(0.94, 1.0)]
+    guis = [dict(D) for _ in range(n)]
+    for name, (lo, hi) in R.items():
+        order = [int(i) for i in rng.permutation(n)]  # order[scene] = stratum
+        if name in SLIDERS64_PRECIP_ONLY:  # low, high and an interior stratum inside the scenes with droplets
+            want = [0, n - 1, 1 + int(rng.integers(0, n - 2))]
+            rest = [i for i in range(n) if i not in want]
+            order = [None] * n
+            for sc, st in zip(SLIDERS64_PRECIP, [want[int(i)] for i in rng.permutation(3)]):
+                order[sc] = st
+            for sc, st in zip([i for i in range(n) if i not in SLIDERS64_PRECIP], [rest[int(i)] for i in rng.permutation(len(rest))]):
+                order[sc] = st
+        pos = rng.random(n)
+        for sc in range(n):
+            a, b = strata[order[sc]]
+            f = a + (b - a) * float(pos[sc])
+            v = lo + (hi - lo) * f
+            if name in D and abs(v - float(D[name])) < 0.02 * (hi - lo):  # never the default itself
+                v = float(D[name]) + (0.03 if f < 0.9 else -0.03) * (hi - lo)
+            guis[sc][name] = float(v)
+    g = guis[k]
+    s, e = sorted((g["globalEffectsStartAlt"], g["globalEffectsEndAlt"]))  # the GUI keeps start <= end (app.js:3524-3544)
+    g["globalEffectsStartAlt"], g["globalEffectsEndAlt"] = s * g["simHeight"], max(e, s + 0.25) * g["simHeight"] if e < s + 0.25 else e * g["simHeight"]
+    g["globalEffectsEndAlt"] = min(g["globalEffectsEndAlt"], g["simHeight"])
+    g["sunAngle"] = SLIDERS64_SUN[k]
+    g["wrapHorizontally"] = k not in SLIDERS64_NOWRAP
+    g["dynamicWaterTemperature"] = bool(k % 3)
+    g["enablePrecipitation"] = k in SLIDERS64_PRECIP
+    return g
+
+
+def _sliders64_sounding(u, Y, seed):
+    """Synthetic realWorldSounding_* rows (as fx_sounding64): soundingForcing acts in every scene."""
+    y = np.arange(Y + 1, dtype=np.float64)
+    real_t = 290.0 + seed - (70.0 - 2.0 * seed) * y / Y + 3.0 * np.sin(y * 0.4 + seed)
+    u["sounding_T"] = (real_t + (y / Y) * u["dryLapse"]).astype(np.float32)
+    u["sounding_W"] = (((real_t - 4.0 - 6.0 * (y / Y)) / 250.0) ** 17).astype(np.float32)
+    u["sounding_Vel"] = ((0.05 + 0.25 * y / Y) * (1.0 if seed % 2 else -1.0)).astype(np.float32)
+
+
+def _sliders64_drops(rng, n=256, k=96):
+    """fx_precip64's hand-built droplet set, plus one heavy droplet already below the bottom edge (precipitationShader.vert's
+    `newPos.y < -1.0` side of the deposit test) and a few right above the ground."""
+    drops = np.zeros((n, 5), np.float32)
+    drops[:, 0] = rng.random(n)
+    drops[:, 1] = rng.random(n)
+    drops[:, 2] = -10.0 + rng.random(n)
+    drops[:, 3] = rng.random(n)
+    drops[:, 4] = rng.random(n)
+    drops[:k, 0] = rng.uniform(-0.98, 0.98, k)
+    drops[:k, 1] = rng.uniform(-0.9, 0.9, k)
+    drops[:k, 2] = rng.uniform(0.0, 0.6, k)
+    drops[:k, 3] = np.where(rng.random(k) < 0.5, rng.uniform(0.0, 0.8, k), 0.0)
+    drops[:k, 4] = np.where(drops[:k, 3] > 0, rng.uniform(0.2, 1.0, k), 1.0)
+    drops[:8, 2] = 0.01
+    drops[:8, 3] = 0.01
+    drops[8:16, 1] = -0.97
+    drops[16:20, 1] = -0.999
+    drops[20] = (0.31, -1.0005, 0.3, 0.2, 0.7)  # left the domain through the bottom
+    drops[21:28, 1] = rng.uniform(-0.8, -0.6, 7)  # rain / snow a few cells above the ground: falls in, deposits
+    return drops
+
+
+# Seeds of the scenes' random fields. The scenes with droplets run freely for 20 iterations, and an inactive droplet spawns when
+# spawnChance > fract(pow(cloud * 10, 2)) (precipitationShader.vert:113) -- of values around 1000, so one ulp of the driver's pow()
+# moves that threshold by 1e-4 and now and then a droplet decides differently (tests/test_oracle_golden.py, lightning64). These
+# seeds are the first of 6400 + k, + 10, + 20 ... for which no decision of the run sits that close to its threshold.
+SLIDERS64_SEED = {1: 6481, 4: 6414, 7: 6437}
+
+
+def fx_sliders64(k, seed=None):
+    rng = np.random.default_rng(SLIDERS64_SEED.get(k, 6400 + k) if seed is None else seed)
+    X, Y = 64, 48
+    gui = sliders64_gui(k)
+    _, u, base, water, wall = synth_terrain(X, Y, rng, gui)
+    _sliders64_sounding(u, Y, k)
+    precip = k in SLIDERS64_PRECIP
+    drops = None
+    if precip:
+        yy = np.arange(Y)[:, None]
+        air = wall[..., 1] != 0
+        deck = air & (yy >= 3) & (yy < 40)  # cloud deck from the warm rows (above 0 C up to row 8 or so) into the cold ones, denser than both thresholds' whole range
+        water[..., 1] = np.where(deck, 2.2 + 2.5 * rng.random((Y, X)), water[..., 1]).astype(np.float32)
+        water[..., 0] = np.where(deck, water[..., 0] + water[..., 1], water[..., 0]).astype(np.float32)
+        drops = _sliders64_drops(rng)
+        u["inactiveDroplets"] = float(20 * k)  # what the host counts every 600 iterations (app.js:5957-5966); 0 until then
+    if k in SLIDERS64_BRUSH:
+        tool, (bx, by), inten = SLIDERS64_BRUSH[k]
+        u.update(userInputType=tool, userInputValues=(bx, by, inten, 6.0), userInputMove=(0.004, -0.002))
+    if k == 2:
+        u["airplaneValues"] = (0.995, 0.5, 0.7, -1.0)  # water dump in the last column: with wrap it would reach column 0
+    # iterations 90..109 / 585..604: across iterNum % 100 == 0 and % 20 == 0
+    return run_fixture(f"sliders64_{k:02d}", X, Y, base, water, wall, drops, u, niter=20, dump_iters=[1, 5, 20], perpass_iter=0,
+                       precip=precip, iter0=585 if k % 2 else 90, keep=("base_cur", "water_cur", "wall_cur", "light_1"), points=True,
+                       keep_particles=("drops", "precip_fb", "precip_dep"), keep_perpass=SLIDERS64_PERPASS)
+
+
+SLIDERS64_PERPASS = ("velocity_base", "vort", "boundary_base", "boundary_water", "boundary_wall", "advection_base", "advection_water",
+                     "advection_wall", "pressure_base", "lighting_light", "precip_fb", "precip_dep", "precip_drops")
+
+
+def fx_sliders64_lightning():
+    """fx_lightning64's cold dense deck and droplet pool under off-default settings, every iteration dumped: lightning requests
+    (the 1-px sprite on texel (1,0)) with snowDensity / meltingHeat / subZeroThreshold / spawnChance away from their defaults."""
+    rng = np.random.default_rng(6499)
+    X, Y = 64, 48
+    gui = sliders64_gui(SLIDERS64_PRECIP[1])
+    gui.update(wrapHorizontally=True, sunAngle=60.0)
+    _, u, base, water, wall = synth_terrain(X, Y, rng, gui)
+    yy = np.arange(Y)[:, None]
+    air = wall[..., 1] != 0
+    realT = base[..., 3] - ((yy + 0.5) / Y) * u["dryLapse"]
+    deck = air & (realT < 268.0) & (yy < Y - 4)
+    water[..., 1] = np.where(deck, 4.0 + 5.0 * rng.random((Y, X)), water[..., 1]).astype(np.float32)
+    water[..., 0] = np.where(deck, water[..., 0] + water[..., 1], water[..., 0]).astype(np.float32)
+    water[..., 2] = np.where(deck, 1.0 * rng.random((Y, X)), water[..., 2]).astype(np.float32)
+    u["spawnChanceMult"] = 0.02  # (as lightning64: far above the GUI's range, so that a pool of 1024 requests strikes within a few iterations)
+    u["enablePrecipitation"] = 1
+    n = 1024
+    drops = np.zeros((n, 5), np.float32)
+    drops[:, 0] = rng.random(n)
+    drops[:, 1] = rng.random(n)
+    drops[:, 2] = -10.0 + rng.random(n)
+    drops[:, 3] = rng.random(n)
+    drops[:, 4] = rng.random(n)
+    u["inactiveDroplets"] = float(n)
+    niter = 6
+    return run_fixture("sliders64_lightning", X, Y, base, water, wall, drops, u, niter=niter, dump_iters=list(range(1, niter + 1)), precip=True,
+                       iter0=40, keep=("base_disp", "water_cur"), points=True)
+
+
 FIXTURES = {
     "randwalls64": fx_randwalls64,
     "brush64": fx_brush64,
@@ -560,6 +718,8 @@ FIXTURES = {
     "emitted64": fx_emitted64,
     "airplane64": fx_airplane64,
     "setup256": fx_setup256,
+    **{f"sliders64_{k:02d}": (lambda k=k: fx_sliders64(k)) for k in range(SLIDERS64_N)},
+    "sliders64_lightning": fx_sliders64_lightning,
 }
 
 if __name__ == "__main__":

@@ -39,6 +39,30 @@ def test_existing_seeds_draw_the_cases_they_drew(mode, seed):
     assert hashlib.sha256(json.dumps(_recipes(mode, seed), sort_keys=True).encode()).hexdigest() == DIGESTS[(mode, seed)]
 
 
+def test_the_added_sliders_come_from_the_shared_table_and_cover_it():
+    """One table of GUI ranges (params.GUI_RANGES): the fuzzer's 17 first sliders are its first 17 entries (four with the fuzzer's own,
+    stated interval), the added ones (draw_more_sliders: a function of the case, no draw from its generator, so the digests above
+    hold) lie inside the GUI's range, every one of them within 300 cases, and a recipe without the key -- the committed regressions --
+    draws none."""
+    R = fuzz_parity._GUI_RANGES
+    assert list(fuzz_parity.SLIDERS) == list(R)[:17] and set(fuzz_parity.SLIDERS_MORE) <= set(R)
+    assert {k for k in fuzz_parity.SLIDERS if fuzz_parity.SLIDERS[k] != R[k]} == set(fuzz_parity.FUZZ_INTERVALS)
+    assert not (set(fuzz_parity.SLIDERS) | set(fuzz_parity.SLIDERS_MORE)) - set(fuzz_parity.wxpkg.load_package().params.GUI_DEFAULTS)
+    seen = {}
+    more = lambda n: [fuzz_parity.draw_more_sliders(c)["sliders_more"] for c in _recipes("oracle", 11, n)]
+    for sm in more(300):
+        for k, v in sm.items():
+            lo, hi = R[k]
+            assert lo <= v <= hi
+            seen.setdefault(k, []).append((v - lo) / (hi - lo))
+    assert set(seen) == set(fuzz_parity.SLIDERS_MORE)
+    assert all(min(v) < 0.1 and max(v) > 0.9 for v in seen.values())
+    assert more(20) == more(20) and all("sliders_more" not in c for c in _recipes("oracle", 11, 20))
+    for f in ("fuzz_group_regressions.json", "fuzz_script_regressions.json"):
+        with open(os.path.join(ROOT, "tests", "golden", f)) as fh:
+            assert all("sliders_more" not in r["recipe"] for r in json.load(fh))
+
+
 def test_scripts_are_a_function_of_the_seed_and_leave_the_scenes_alone():
     a, b = _recipes("script", 13), _recipes("script", 13)
     assert json.dumps(a) == json.dumps(b) and json.dumps(a) != json.dumps(_recipes("script", 14))

@@ -27,7 +27,7 @@ def _run(fuzz, pkg, oracle, mode, seed, n_cases, max_cells=250000):
     rng = np.random.default_rng(seed)
     ran = compared = 0
     for k in range(n_cases):
-        c = fuzz.draw_case(rng, max_cells)
+        c = fuzz.draw_more_sliders(fuzz.draw_case(rng, max_cells))
         if mode == "group":
             c = fuzz.draw_group(rng, c)
             bad, info = fuzz.run_group_case(pkg, pkg.engine, c)
@@ -69,7 +69,7 @@ def test_fuzz_host_scripts_against_the_oracle(pkg, oracle, fuzz, seed):
     rng, rng_script = np.random.default_rng(seed), np.random.default_rng(seed + 2000003)
     compared, reads, actions = 0, 0, {k: 0 for k in fuzz.SCRIPT_ACTIONS}
     for k in range(SCRIPT_CASES):
-        c = fuzz.draw_script(rng_script, fuzz.draw_case(rng, 250000))
+        c = fuzz.draw_script(rng_script, fuzz.draw_more_sliders(fuzz.draw_case(rng, 250000)))
         bad, info = fuzz.run_script_case(pkg, pkg.engine, oracle, c)
         for kind, n in info["actions"].items():
             actions[kind] += n

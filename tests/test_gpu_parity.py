@@ -60,7 +60,10 @@ def _assert_grid_equal(h, o, fields=GRID_FIELDS, emitted=True):
         assert a.dtype == np.float16 and np.array_equal(a, b), f"EMITTED: {np.count_nonzero(a != b)} of {a.size} values differ"
 
 
-@pytest.mark.parametrize("name", ["save100qa", "synth64", "randwalls64", "sounding64", "save100raw", "randwalls64p", "emitted64_day", "emitted64_night"])
+SLIDERS64 = [f"sliders64_{k:02d}" for k in range(8)]  # every control off default over the GUI's ranges (tests/test_oracle_sliders.py)
+
+
+@pytest.mark.parametrize("name", ["save100qa", "synth64", "randwalls64", "sounding64", "save100raw", "randwalls64p", "emitted64_day", "emitted64_night"] + SLIDERS64)
 @pytest.mark.parametrize("quad_scale", [0, 1])
 def test_bit_exact_vs_oracle_on_golden_inputs(pkg, oracle, golden, E, name, quad_scale, fused):
     g, u = golden(name)
@@ -96,6 +99,61 @@ def test_vs_swiftshader_goldens(pkg, golden, E, fused):
         assert np.abs(b[..., :3] - rb[..., :3]).max() <= tv
         assert np.abs(b[..., 3] - rb[..., 3]).max() <= tT
         assert np.abs(h.read_rect("WATER_CUR") - g[f"it{it}_water_cur"]).max() <= tw
+
+
+@pytest.mark.parametrize("name", SLIDERS64)
+def test_vs_reference_off_default_settings(pkg, golden, E, fused, name):
+    """HIP (quad_scale = 1) straight against the reference's own output on the sliders64 scenes -- every control away from its
+    default, wrap off with an input at the x edge -- at iterations 1, 5 and 20 with the tolerances tests/test_oracle_sliders.py
+    states for the CPU oracle (the scenes are drawn as GL_POINTS, whose varyings are the exact analytic ones: no
+    fragCoord-interpolation allowance is needed); masks bit-exact. The three scenes with droplets are compared at iteration 1
+    only, grid and droplet state: the reference's rasteriser snaps the 12 x 12 sprites to 1/16 px (the oracle's subpixel_bits),
+    the engine does not, so from the second iteration on the feedback differs by whole texels of a sprite's rim. Their
+    particle pass reaches the reference through test_sliders64_particles_bit_exact_vs_oracle."""
+    import test_oracle_sliders as S
+    g, u = golden(name)
+    u = dict(u, quad_scale=1)
+    X, Y, precip = int(g["X"]), int(g["Y"]), int(g["precip"])
+    drops = g["in_drops"] if precip else None
+    h = E.Handle(X, Y, len(drops) if precip else 0)
+    if precip:
+        h.set_option(h.OPT_SPLAT_ORDER, 1)
+    h.upload(g["in_base"], g["in_water"], g["in_wall"], drops)
+    h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"], u["sounding_T"], u["sounding_W"], u["sounding_Vel"])
+    h.iter = int(g["iter0"])
+    out, done = {}, 0
+    for it in ((1,) if precip else S.ITS):
+        h.step(it - done)
+        done = it
+        b, w, l = h.read_rect("BASE_CUR"), h.read_rect("WATER_CUR"), h.read_rect("LIGHT_1")
+        out.update({f"it{it}:wall": h.read_rect("WALL_CUR"), f"it{it}:v": b[..., :2], f"it{it}:P": b[..., 2], f"it{it}:T": b[..., 3],
+                    f"it{it}:vapour_cloud": w[..., :2], f"it{it}:precip_smoke": w[..., 2:], f"it{it}:sunlight": l[..., 0],
+                    f"it{it}:net_heating": l[..., 1], f"it{it}:IR": l[..., 2:]})
+        if precip:
+            out[f"it{it}:drops"] = h.read_particles()
+            assert round(float(h.read_rect("PRECIP_FB")[0, 0, 0])) == round(float(g[f"it{it}_precip_fb"][0, 0, 0]))  # the inactive-droplet count
+    assert len(out) >= 9 and S.check_against_reference(out, g, u) == []
+
+
+@pytest.mark.parametrize("name", ["sliders64_01", "sliders64_04", "sliders64_07"])
+def test_sliders64_particles_bit_exact_vs_oracle(pkg, oracle, golden, E, fused, name):
+    """The scenes with droplets and every precipitation control off default, 20 iterations with the particle pass on, against the
+    oracle in the engine's summation order (splat_order 1) and with the reference's sprite snapping (subpixel_bits 4) off on both
+    sides: grid, droplets, feedback and deposition bit for bit. The oracle with snapping on is what tests/test_oracle_sliders.py
+    holds against the reference."""
+    g, u = golden(name)
+    u = dict(u, quad_scale=1, splat_order=1)
+    h, o = _make_pair(pkg, oracle, E, int(g["X"]), int(g["Y"]), g["in_base"], g["in_water"], g["in_wall"], u, drops=g["in_drops"], iter0=int(g["iter0"]))
+    h.set_option(h.OPT_SPLAT_ORDER, 1)
+    done = 0
+    for it in (1, 5, 20):
+        h.step(it - done)
+        o.step(it - done)
+        done = it
+        _assert_grid_equal(h, o)
+        assert np.array_equal(h.read_particles(), o.field("DROPS")), it
+        assert np.array_equal(h.read_rect("PRECIP_FB"), o.field("PRECIP_FB")) and np.array_equal(h.read_rect("PRECIP_DEP"), o.field("PRECIP_DEP")), it
+    assert (o.field("DROPS")[:, 2] >= 0).sum() >= 30  # droplets are in flight
 
 
 def test_reference_raw_save_1000_iterations(pkg, golden, E, fused):

@@ -45,11 +45,32 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import wxpkg  # noqa: E402
 
 GRID_FIELDS = ["BASE_CUR", "BASE_DISP", "WATER_0", "WATER_CUR", "WALL_CUR", "WALL_DISP", "LIGHT_0", "LIGHT_1"]
-# sliders of the reference's GUI (app.js:3402-3560: min / max of the controls the simulation reads)
-SLIDERS = {"vorticity": (0.0, 0.010), "dragMultiplier": (0.0, 1.0), "wind": (-1.0, 1.0), "globalDrying": (0.0, 0.001), "globalHeating": (-0.002, 0.002),
-           "sunIntensity": (0.0, 2.0), "waterTemperature": (0.0, 40.0), "landEvaporation": (0.0, 0.0002), "waterEvaporation": (0.0, 0.0004),
-           "evapHeat": (0.0, 5.0), "meltingHeat": (0.0, 5.0), "condensationRate": (0.0, 0.01), "waterWeight": (0.0, 2.0),
-           "greenhouseGases": (0.0, 0.01), "waterGreenHouseEffect": (0.0, 0.01), "IR_rate": (0.0, 10.0), "soundingForcing": (0.0, 0.001)}
+# Sliders of the reference's GUI: the table is params.GUI_RANGES (checked against app.js:3481-3745), shared with oracle/golden/gen_golden.py.
+# SLIDERS are the 17 controls draw_case has always drawn from its main generator, in the table's order (the draws of existing seeds are
+# pinned, tests/test_fuzz_draw_cpu.py). Four of them keep the interval this fuzzer has always used instead of the GUI's, on purpose:
+# globalDrying / globalHeating ten / two times wider than the GUI (a superset), condensationRate from 0 (below the GUI's 0.001), and
+# soundingForcing up to 0.001 only -- these scenes carry no realWorldSounding_* arrays, so the term relaxes towards zero profiles.
+_GUI_RANGES = wxpkg.load_package().params.GUI_RANGES
+FUZZ_INTERVALS = {"globalDrying": (0.0, 0.001), "globalHeating": (-0.002, 0.002), "condensationRate": (0.0, 0.01), "soundingForcing": (0.0, 0.001)}
+SLIDERS = {k: FUZZ_INTERVALS.get(k, _GUI_RANGES[k]) for k in list(_GUI_RANGES)[:17]}
+# The rest of what the simulation reads -- the precipitation folder and the start dialog's simHeight (dryLapse and initial_T) -- is drawn
+# from a CHILD generator seeded by values the main one has already produced, so that adding it left every earlier draw where it was
+# (draw_more_sliders, recipe key "sliders_more": draw_case's own recipe is byte for byte what it was; recipes without the key, the
+# committed regressions, run as they always did). spawnChance is left out: the
+# scenes with droplets fix spawnChanceMult at 0.01, two orders above the GUI's range, or grids this small would hardly ever spawn.
+SLIDERS_MORE = {k: _GUI_RANGES[k] for k in ("aboveZeroThreshold", "subZeroThreshold", "snowDensity", "fallSpeed", "growthRate0C", "growthRate_30C",
+                                            "freezingRate", "meltingRate", "evapRate", "simHeight")}
+
+
+def _draw_more(seed_words, chance):
+    r = np.random.default_rng([int(w) & 0x7FFFFFFF for w in seed_words])
+    return {k: float(r.uniform(*SLIDERS_MORE[k])) for k in SLIDERS_MORE if r.random() < chance}
+
+
+def draw_more_sliders(c):
+    """Adds c["sliders_more"] to a case of draw_case (SLIDERS_MORE): a pure function of the case, no draw from its generator."""
+    c["sliders_more"] = _draw_more([c["data_seed"], 0x51D], 0.35)
+    return c
 
 
 def draw_case(rng, max_cells, big=False):
@@ -133,6 +154,7 @@ def build_case(pkg, c):
         water[..., 2] += np.where(air & (rng.random((Y, X)) < 0.1), rng.random((Y, X)) * 0.5, 0).astype(np.float32)
     gui = P.merge_settings(None)
     gui.update(c["sliders"])
+    gui.update(c.get("sliders_more", {}))
     gui["sunAngle"] = c["sun"]
     gui["wrapHorizontally"] = c["wrap"]
     u = P.uniforms_from_gui(gui, Y, quad_scale=c["quad_scale"], pass_mask=P.PASS_DRY if c["dry"] else P.PASS_ALL)
@@ -292,6 +314,7 @@ def _draw_action(rng, c, kind):
         for w in what:
             if w == "sliders":
                 ch["sliders"] = {k: float(rng.uniform(*SLIDERS[k])) for k in SLIDERS if rng.random() < 0.25}
+                ch["sliders"].update(_draw_more([c["data_seed"], 0x5C2, sum(ch["sliders"].values()) * 1e9], 0.25))
             elif w == "sun":
                 ch["sun"] = float(rng.uniform(-30.0, 210.0))
             elif w == "lapse":  # another initial_T row
@@ -377,7 +400,7 @@ def run_script_case(pkg, E, wx_oracle, c):
     X, Y = c["X"], c["Y"]
     base, water, wall, u, drops = build_case(pkg, c)
     nd = 0 if drops is None else len(drops)
-    st = {"sliders": dict(c["sliders"]), "sun": c["sun"], "wrap": c["wrap"], "lapse": None, "dry": c["dry"], "precip": 1, "brush": c["brush"], "airplane": c["airplane"]}
+    st = {"sliders": dict(c["sliders"], **c.get("sliders_more", {})), "sun": c["sun"], "wrap": c["wrap"], "lapse": None, "dry": c["dry"], "precip": 1, "brush": c["brush"], "airplane": c["airplane"]}
     u = _script_uniforms(pkg, c, st)
     h = E.Handle(X, Y, nd)
     o = wx_oracle.OracleSim(X, Y, nd)
@@ -874,7 +897,7 @@ def main():
         print(json.dumps({"mode": a.mode, "seed": a.seed, "cases_run": ran, "mismatching_cases": n_bad, "seconds": round(time.time() - t0, 1)}))
         sys.exit(1 if n_bad else 0)
     for k in range(a.cases):
-        c = draw_case(rng, a.max_cells, a.big)
+        c = draw_more_sliders(draw_case(rng, a.max_cells, a.big))
         if a.mode == "group":
             c = draw_group(rng, c)
         if a.mode == "script":
@@ -889,7 +912,7 @@ def main():
             c.update(json.loads(a.override))
         t1 = time.time()
         if a.mode == "oracle" and a.interleave and rng_il.random() < 0.5 and a.only < 0:  # this case and a second small one, handles alive together
-            c2 = draw_case(rng_il, min(a.max_cells, 60000))
+            c2 = draw_more_sliders(draw_case(rng_il, min(a.max_cells, 60000)))
             (bad, info), (bad2, info2) = run_interleaved(pkg, E, wx_oracle, [c, c2])
             if bad2 and not info2.get("blown_up"):
                 failures.append({"case": k, "interleaved_with": c, "recipe": c2, "mismatches": bad2})
