@@ -144,6 +144,9 @@ __device__ __forceinline__ char4 pack_wall(const int w[4])
   return make_char4((signed char)sat8(w[0]), (signed char)sat8(w[1]), (signed char)sat8(w[2]), (signed char)sat8(w[3]));
 }
 __host__ __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
+// x for every finite x (signed zeros kept) and for NaN, NaN for +-Inf -- one fma: what the reference's `x -= (x - s) * 0` lines leave of x
+// (advection_cell: the sounding forcing at forcing 0, which is skipped for everything finite)
+__device__ __forceinline__ float inf_to_nan(float x) { return __builtin_fmaf(x, 0.0f, x); }
 // mix(): lowered as a + t*(b-a), the form pinned by the golden vectors (see oracle/wx_oracle.c)
 __device__ __forceinline__ float mixf(float a, float b, float t) { return a + t * (b - a); }
 // common.glsl:99-101
@@ -586,7 +589,9 @@ __device__ __forceinline__ float smoothstepf(float e0, float e1, float x)
 
 // NO_WATER: the water texture is identically zero in air cells (BASELINE config 1, checked by the host) and no
 // sounding forcing is active: the water interpolation and the phase-change block then provably leave base unchanged
-// (condensation = max(negative * 0.2, -0) = -0, dT = -0) and water zero, so they are not evaluated.
+// (condensation = max(negative * 0.2, -0) = -0, dT = -0) and water zero, so they are not evaluated. FINITE states only: with a NaN or
+// Inf velocity the interpolation weights are NaN and the reference makes NaN water (and temperature) of the zeros -- a state the
+// water-free kernels cannot hold; their index arithmetic is defined and memory-safe on it all the same.
 // NO_WALL (wave-uniform, established by the caller): neither the cell nor any texel of its back-trace footprints is a wall
 // cell, so the wall-aware interpolation reduces to the plain one (same weights, same operations) and the wall branch is dead.
 // NO_ZW (wave-uniform, established by the caller; only with NO_WALL): the precipitation-visual channel (z) and the smoke channel (w)
@@ -732,6 +737,10 @@ __device__ __forceinline__ void advection_cell(const UT &u, const Geo &g, const 
         b.y *= u.snd_dragk;
         const float velDiff = b.x - sV;
         b.x -= velDiff * u.snd_velk;
+      } else { // ... and for finite fields ONLY: x - (x - s) * 0 is NaN for an infinite x, and a blown-up state has them
+        b.w = inf_to_nan(b.w);
+        w.x = inf_to_nan(w.x);
+        b.x = inf_to_nan(b.x);
       }
     }
     w.x = fmaxf(w.x, 0.0f);

@@ -101,8 +101,9 @@ template <bool WATER>
 __device__ __forceinline__ void advect_dry_cell(const Uni &u, const Geo &g, const FullCtx *ctx, const fd::Smem<WATER> &sm, const DryIn &in, int x,
                                                 int y, int lx, int ly, float4 &b, float4 &w, char4 &wl)
 {
-  const float m = fmaxf(fmaxf(fmaxf(fabsf(sm.b.x[ly][lx]), fabsf(sm.b.x[ly][lx - 1])), fmaxf(fabsf(sm.b.x[ly + 1][lx]), fabsf(sm.b.x[ly + 1][lx - 1]))),
-                        fmaxf(fmaxf(fabsf(sm.b.y[ly][lx]), fabsf(sm.b.y[ly - 1][lx])), fmaxf(fabsf(sm.b.y[ly][lx + 1]), fabsf(sm.b.y[ly - 1][lx + 1]))));
+  // (speed8: a NaN among the eight counts as +Inf -- fmaxf alone drops it, and a NaN back-trace has no footprint in the tile)
+  const float m = speed8(sm.b.x[ly][lx], sm.b.x[ly][lx - 1], sm.b.x[ly + 1][lx], sm.b.x[ly + 1][lx - 1],
+                         sm.b.y[ly][lx], sm.b.y[ly - 1][lx], sm.b.y[ly][lx + 1], sm.b.y[ly - 1][lx + 1]);
 #ifdef WX_ABL_NOADV
   b = sm.b.get(ly, lx);
   w = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -731,7 +731,9 @@ __device__ __forceinline__ bool precip_droplet(const int i, const Geo &g, const 
     q += sp.seam + 1; // low-x side of the domain edge: right of the seam, stored one column further right
   else
     q -= g.xoff;
-  if (q < 0 || q >= sg.AP) return false; // the sprite lies outside this slab
+  // (r needs no test of the data's making: the clip test above leaves yw in [0, Y] whatever the droplet holds -- a NaN fails it -- so r is
+  // in [0, Y] and the grid has AH >= Y + 1 rows; it is bounded here all the same: this is the one STORE address made from a float)
+  if (q < 0 || q >= sg.AP || r < 0 || r >= sg.AH) return false; // the sprite lies outside this slab
   const size_t ai = (size_t)r * sg.AP + q;
   if (det.key) {
     det.key[i] = (int)ai;

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
       MarchRing::put(rg.vx, s1, lane, v.x);
       MarchRing::put(rg.vy, s1, lane, v.y);
       vx_seen = fmaxf(vx_seen, fabsf(v.x));
-      big1 = __any(fmaxf(fabsf(v.x), fabsf(v.y)) >= 0.9f); // any back-trace of this row that may leave the 3x3 cells?
+      big1 = __any((!(fabsf(v.x) < 0.9f) || !(fabsf(v.y) < 0.9f))); // any back-trace of this row that may leave the 3x3 cells? (a compare per component, not fmaxf: that drops a NaN)
     }
     march_fence();
 
@@ -219,10 +219,9 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
         const int yc = rc - 2, l1 = lr;
         bool fast = true;
         if (big1 | big2 | big3) { // wave-uniform: some velocity of rows y-1 .. y+1 is large -> per-lane test
-          const float m = fmaxf(fmaxf(fmaxf(fabsf(rg.vx[yc & 3][l1]), fabsf(rg.vx[yc & 3][l1 - 1])),
-                                      fmaxf(fabsf(rg.vx[(yc + 1) & 3][l1]), fabsf(rg.vx[(yc + 1) & 3][l1 - 1]))),
-                                fmaxf(fmaxf(fabsf(rg.vy[yc & 3][l1]), fabsf(rg.vy[(yc - 1) & 3][l1])),
-                                      fmaxf(fabsf(rg.vy[yc & 3][l1 + 1]), fabsf(rg.vy[(yc - 1) & 3][l1 + 1]))));
+          const float m = speed8(rg.vx[yc & 3][l1], rg.vx[yc & 3][l1 - 1], rg.vx[(yc + 1) & 3][l1], rg.vx[(yc + 1) & 3][l1 - 1],
+                                 rg.vy[yc & 3][l1], rg.vy[(yc - 1) & 3][l1], rg.vy[yc & 3][l1 + 1], rg.vy[(yc - 1) & 3][l1 + 1]);
+          if (rg.vx[yc & 3][l1] != rg.vx[yc & 3][l1]) vx_seen = __builtin_inff(); // (the watch: fmaxf dropped a NaN vx in the row loop; it set the vote, so it is seen here and counts as +Inf)
           fast = m < 0.9f;
         }
         if (fast) {

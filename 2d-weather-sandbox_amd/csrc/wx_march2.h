@@ -189,7 +189,7 @@ __global__ __launch_bounds__(64, WX_MARCH2_MINWAVES) void k_march_dry2(Geo g, co
       rg.vx[0][s1][lane] = v.x;
       rg.vy[0][s1][lane] = v.y;
       vx_seen = fmaxf(vx_seen, fabsf(v.x));
-      h_big1 |= __any(fmaxf(fabsf(v.x), fabsf(v.y)) >= 0.9f) ? 1u : 0u;
+      h_big1 |= __any((!(fabsf(v.x) < 0.9f) || !(fabsf(v.y) < 0.9f))) ? 1u : 0u; // (a compare per component, not fmaxf: that drops a NaN, and a NaN back-trace has no footprint in the ring)
     }
     march_fence();
     float4 b2 = make_float4(0.f, 0.f, 0.f, 0.f); // pressure_1 of row r-2 = the second iteration's input row
@@ -201,9 +201,10 @@ __global__ __launch_bounds__(64, WX_MARCH2_MINWAVES) void k_march_dry2(Geo g, co
       bool fast = true;
       if (TAINT) h_bad1 <<= 1;
       if (h_big1 & 7u) {
+        if (rg.vx[0][yc & 3][lr] != rg.vx[0][yc & 3][lr]) vx_seen = __builtin_inff(); // (the watch: fmaxf dropped a NaN vx in the row loop; it set the vote, so it is seen here and counts as +Inf)
         if (!TAINT) {
-          const float m = fmaxf(fmaxf(fmaxf(fabsf(rg.vx[0][yc & 3][lr]), fabsf(rg.vx[0][yc & 3][lr - 1])), fmaxf(fabsf(rg.vx[0][(yc + 1) & 3][lr]), fabsf(rg.vx[0][(yc + 1) & 3][lr - 1]))),
-                                fmaxf(fmaxf(fabsf(rg.vy[0][yc & 3][lr]), fabsf(rg.vy[0][(yc - 1) & 3][lr])), fmaxf(fabsf(rg.vy[0][yc & 3][lr + 1]), fabsf(rg.vy[0][(yc - 1) & 3][lr + 1]))));
+          const float m = speed8(rg.vx[0][yc & 3][lr], rg.vx[0][yc & 3][lr - 1], rg.vx[0][(yc + 1) & 3][lr], rg.vx[0][(yc + 1) & 3][lr - 1],
+                                 rg.vy[0][yc & 3][lr], rg.vy[0][(yc - 1) & 3][lr], rg.vy[0][yc & 3][lr + 1], rg.vy[0][(yc - 1) & 3][lr + 1]);
           fast = m < 0.9f;
         } else {
           const float q0 = rg.vx[0][yc & 3][lr], q1 = rg.vx[0][yc & 3][lr - 1], q2 = rg.vx[0][(yc + 1) & 3][lr], q3 = rg.vx[0][(yc + 1) & 3][lr - 1];
@@ -250,8 +251,9 @@ __global__ __launch_bounds__(64, WX_MARCH2_MINWAVES) void k_march_dry2(Geo g, co
         if (lane == 63) v.x = v.y = 0.0f;
         rg.vx[1][s3][lane] = v.x;
         rg.vy[1][s3][lane] = v.y;
-        vx_seen = fmaxf(vx_seen, fabsf(v.x));
-        h_big2 |= __any(lane >= 2 && lane <= 61 && fmaxf(fabsf(v.x), fabsf(v.y)) >= 0.9f) ? 1u : 0u; // (fmaxf drops a NaN: tainted rows are covered by h_bad1 below)
+        vx_seen = fmaxf(vx_seen, fabsf(v.x)); // (fmaxf drops a NaN -- here it may be the taint marker; k_dry2_fix reports the velocities of the cells it recomputes)
+        // (NaN-aware: a GENUINE NaN of the uploaded state reaches the plain instantiation too, which has no h_bad1)
+        h_big2 |= __any(lane >= 2 && lane <= 61 && (!(fabsf(v.x) < 0.9f) || !(fabsf(v.y) < 0.9f))) ? 1u : 0u;
       }
     }
     march_fence();
@@ -262,8 +264,8 @@ __global__ __launch_bounds__(64, WX_MARCH2_MINWAVES) void k_march_dry2(Geo g, co
       bool fast2 = true;
       if ((h_big2 & 7u) | (TAINT ? (h_bad1 & 0xffu) : 0u)) { // (some velocity of rows y-1 .. y+1 is large, or a first-iteration cell of the last rows was tainted)
         if (!TAINT) {
-          const float m = fmaxf(fmaxf(fmaxf(fabsf(rg.vx[1][yc & 3][lr]), fabsf(rg.vx[1][yc & 3][lr - 1])), fmaxf(fabsf(rg.vx[1][(yc + 1) & 3][lr]), fabsf(rg.vx[1][(yc + 1) & 3][lr - 1]))),
-                                fmaxf(fmaxf(fabsf(rg.vy[1][yc & 3][lr]), fabsf(rg.vy[1][(yc - 1) & 3][lr])), fmaxf(fabsf(rg.vy[1][yc & 3][lr + 1]), fabsf(rg.vy[1][(yc - 1) & 3][lr + 1]))));
+          const float m = speed8(rg.vx[1][yc & 3][lr], rg.vx[1][yc & 3][lr - 1], rg.vx[1][(yc + 1) & 3][lr], rg.vx[1][(yc + 1) & 3][lr - 1],
+                                 rg.vy[1][yc & 3][lr], rg.vy[1][(yc - 1) & 3][lr], rg.vy[1][yc & 3][lr + 1], rg.vy[1][(yc - 1) & 3][lr + 1]);
           fast2 = m < 0.9f;
         } else {
           const float q0 = rg.vx[1][yc & 3][lr], q1 = rg.vx[1][yc & 3][lr - 1], q2 = rg.vx[1][(yc + 1) & 3][lr], q3 = rg.vx[1][(yc + 1) & 3][lr - 1];
@@ -450,7 +452,7 @@ __device__ __forceinline__ bool dry2_fix_entries(const Geo &g, const FullCtx *__
     wave_fence();
     // (slabs size their exchange periods by the largest |vx| they produce: the marching loop could not see the second iteration's velocity
     // where its input was tainted -- fmaxf drops NaN -- so the tile's own 64 cells report theirs here)
-    vx_track_commit(vx, fabsf(v2x[(F2C + (lane >> 3)) * F2W + F2C + (lane & 7)]), lane, c.x / M2OUT);
+    vx_track_commit(vx, vx_mag(v2x[(F2C + (lane >> 3)) * F2W + F2C + (lane & 7)]), lane, c.x / M2OUT);
     bool left2 = false;
     for (int k = lane; k < F2A * F2A; k += 64) { // advection_2 on [7, 16]^2
       const int oy = k / F2A, ox = k - oy * F2A, sy = F2C - 1 + oy, sx = F2C - 1 + ox;
@@ -566,7 +568,7 @@ __device__ __forceinline__ void march_dry_redo_items(const Geo &g, const FullCtx
         rg.vx[0][s1][lane] = v.x;
         rg.vy[0][s1][lane] = v.y;
         vx_seen = fmaxf(vx_seen, fabsf(v.x));
-        h_big |= __any(fmaxf(fabsf(v.x), fabsf(v.y)) >= 0.9f) ? 1u : 0u;
+        h_big |= __any((!(fabsf(v.x) < 0.9f) || !(fabsf(v.y) < 0.9f))) ? 1u : 0u;
       }
       march_fence();
       if (r >= y_lo + 1) {
@@ -575,8 +577,9 @@ __device__ __forceinline__ void march_dry_redo_items(const Geo &g, const FullCtx
         char4 awl;
         bool fast = true;
         if (h_big & 7u) {
-          const float m = fmaxf(fmaxf(fmaxf(fabsf(rg.vx[0][yc & 3][lr]), fabsf(rg.vx[0][yc & 3][lr - 1])), fmaxf(fabsf(rg.vx[0][(yc + 1) & 3][lr]), fabsf(rg.vx[0][(yc + 1) & 3][lr - 1]))),
-                                fmaxf(fmaxf(fabsf(rg.vy[0][yc & 3][lr]), fabsf(rg.vy[0][(yc - 1) & 3][lr])), fmaxf(fabsf(rg.vy[0][yc & 3][lr + 1]), fabsf(rg.vy[0][(yc - 1) & 3][lr + 1]))));
+          if (rg.vx[0][yc & 3][lr] != rg.vx[0][yc & 3][lr]) vx_seen = __builtin_inff();
+          const float m = speed8(rg.vx[0][yc & 3][lr], rg.vx[0][yc & 3][lr - 1], rg.vx[0][(yc + 1) & 3][lr], rg.vx[0][(yc + 1) & 3][lr - 1],
+                                 rg.vy[0][yc & 3][lr], rg.vy[0][(yc - 1) & 3][lr], rg.vy[0][yc & 3][lr + 1], rg.vy[0][(yc - 1) & 3][lr + 1]);
           fast = m < 0.9f;
         }
         if (fast) {

@@ -182,6 +182,23 @@ struct VxTrack {
   float limit_in;  // the strips in between consume no ghost column -- until |vx| spans the two halo widths that separate them from the ghost
                    // columns: a jet that fast (2 * halo - 8 cells / iteration: a state that has blown up) is a violation too (0: not checked)
 };
+// The per-lane speed test of the marching kernels (rare path, behind a wave vote): the largest of the eight |velocity components| a
+// cell's three back-traces are built from. fmaxf returns the OTHER operand for a NaN; the sum of the magnitudes keeps it, and a NaN among
+// them counts as +Inf: such a cell takes the exact path, whose taps are bounds-checked stages and wrapped global reads.
+__device__ __forceinline__ float speed8(float q0, float q1, float q2, float q3, float q4, float q5, float q6, float q7)
+{
+  const float m = fmaxf(fmaxf(fmaxf(fabsf(q0), fabsf(q1)), fmaxf(fabsf(q2), fabsf(q3))), fmaxf(fmaxf(fabsf(q4), fabsf(q5)), fmaxf(fabsf(q6), fabsf(q7))));
+  const float sn = ((fabsf(q0) + fabsf(q1)) + (fabsf(q2) + fabsf(q3))) + ((fabsf(q4) + fabsf(q5)) + (fabsf(q6) + fabsf(q7)));
+  return sn == sn ? m : __builtin_inff();
+}
+// |v| for the velocity watch where it is not accumulated row by row: a NaN counts as +Inf (fmaxf would drop it, and a blown-up
+// neighbour must not pass for a calm one). The marching loops keep their one v_max per row step and raise +Inf from the rare branch
+// behind the wave vote, which a NaN velocity always sets.
+__device__ __forceinline__ float vx_mag(float v)
+{
+  const float a = fabsf(v);
+  return a == a ? a : __builtin_inff();
+}
 __device__ __forceinline__ void vx_track_commit(const VxTrack &t, float lane_max, int lane, int strip = 0)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -207,7 +224,7 @@ __global__ void k_vx_scan(int X, int Y, int col_l, int col_r, const float4 *__re
   const size_t n = (size_t)X * Y;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % (size_t)X);
-    const float v = fabsf(base[i].x);
+    const float v = vx_mag(base[i].x);
     if (col_l >= col_r || x < col_l || x >= col_r)
       m = fmaxf(m, v);
     else

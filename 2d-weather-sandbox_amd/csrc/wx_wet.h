@@ -748,7 +748,9 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
         (&rg.qw[0][0])[oq] = bq.w;
         vx_seen = fmaxf(vx_seen, fabsf(bb.x));
         // back-traces of this row that may leave the 3x3 cells? (lanes 2 .. 60 feed an advection that is used)
-        WX_H_SET(h_big, __any(lane >= 2 && lane <= 60 && !(fmaxf(fabsf(bb.x), fabsf(bb.y)) < 0.9f)));
+        // (one compare per component, not their fmaxf: that returns the other operand for a NaN, and a NaN back-trace has no footprint in
+        // the ring. For finite velocities the vote is what it was: max >= 0.9)
+        WX_H_SET(h_big, __any(lane >= 2 && lane <= 60 && (!(fabsf(bb.x) < 0.9f) || !(fabsf(bb.y) < 0.9f))));
         WX_H_SET(h_nowall, __all(lane < 2 || lane > 60 || bwl.y != 0)); // no wall cell in this post-boundary row (as far as advection reads it)
         WX_H_SET(h_zw0, __all(bq.z == 0.0f && bq.w == 0.0f));          // no rain / snow / smoke anywhere in it
         if (OPT_OUT) {
@@ -779,8 +781,8 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
       if (h_big & 7u) { // wave-uniform: some velocity of rows ya-1 .. ya+1 is large -> per-lane test of the eight that matter
         const float *vxp = &rg.vx[0][0], *vyp = &rg.vy[0][0];
         const int o0 = a.ob[1] + li, om = a.ob[0] + li, op = a.ob[2] + li;
-        const float m = fmaxf(fmaxf(fmaxf(fabsf(vxp[o0]), fabsf(vxp[o0 - 1])), fmaxf(fabsf(vxp[op]), fabsf(vxp[op - 1]))),
-                              fmaxf(fmaxf(fabsf(vyp[o0]), fabsf(vyp[om])), fmaxf(fabsf(vyp[o0 + 1]), fabsf(vyp[om + 1]))));
+        const float m = speed8(vxp[o0], vxp[o0 - 1], vxp[op], vxp[op - 1], vyp[o0], vyp[om], vyp[o0 + 1], vyp[om + 1]); // (a NaN among them: +Inf)
+        if (vxp[o0] != vxp[o0]) vx_seen = __builtin_inff(); // (the watch: fmaxf dropped a NaN vx in the row loop; it set the vote, so it is seen here and counts as +Inf)
         fast = m < 0.9f || lane < 3 || lane > 59; // (lanes outside 3 .. 59 feed nothing)
         if (!fast) {
           // This cell (column c_out, unwrapped row yu) keeps a placeholder; the OUTPUT cells it feeds that this wave owns -- its own,
@@ -797,7 +799,7 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
           // of a split iteration have a list of their own, consumed on the comm stream before the halo is packed)
           const __attribute__((address_space(4))) WetFixList &fix =
               *(const __attribute__((address_space(4))) WetFixList *)(ka_c + offsetof(KArgs, fix) + (edge_list ? sizeof(WetFixList) : 0));
-          if (fix.fastest) atomicMax(fix.fastest, __float_as_int(m)); // (m >= 0.9 or NaN: the bit patterns of positive floats order like ints)
+          if (fix.fastest) atomicMax(fix.fastest, __float_as_int(m)); // (m >= 0.9, +Inf for a NaN or Inf component: the bit patterns of positive floats order like ints)
           if (n_add) {
             int at = atomicAdd(fix.count, n_add);
             if (at + n_add <= fix.cap) {

@@ -2194,7 +2194,8 @@ int wx_slab_set_vx_bound(wx_sim *s, float v_measured)
   // the margin: a flow measured at v may be at 1.25 v + 0.25 by the time the period it sizes is over (one to two periods later); below
   // 0.6 cells / iteration that still is less than one cell
   const float bound = v_measured * 1.25f + 0.25f;
-  const int cone = WX_SLAB_CONE + (bound >= 1.0f ? (int)floorf(bound) : 0);
+  // (a blown-up flow measures +Inf -- the velocity watch counts a NaN as that: no halo is wide enough, said below like any other excess)
+  const int cone = WX_SLAB_CONE + (bound >= 1.0f ? (bound < 1.0e6f ? (int)floorf(bound) : 1000000) : 0);
   if (s->halo > 0 && (cone > s->halo || (s->pool.remote && 2 * cone + 1 > s->halo)))
     return fail(s, WX_E_STATE, "|vx| up to %.2f cells / iteration needs %d ghost columns per iteration; the handle has %d: a wider halo (wx_create_slab) is needed for this flow",
                 v_measured, cone, s->halo);

@@ -137,6 +137,8 @@ int wx_create_slab(int X_global, int Y, int x0, int X_owned, int halo, int n_dro
  *                                reaches 1 -- WX_E_STATE if the halo is too thin for it
  *   wx_slab_cone(s), wx_slab_period(s)   ghost columns per iteration / iterations per exchange under the current bound (with particles:
  *                                cone for the first iteration, cone + 3 for every further one, a sprite radius left in the last)
+ * A non-finite vx (NaN or Inf: a state that has blown up) counts as +Inf in all of this: wx_slab_vx_take returns +Inf, for which no halo
+ * is wide enough (wx_slab_set_vx_bound: WX_E_STATE), and inside a period it is reported wherever in the slab it lies.
  * A |vx| that reaches the bound inside a period is REPORTED by the next blocking call (WX_E_STATE), never silent; so is a velocity of
  * 2 * halo - 8 cells / iteration and more anywhere in the slab (beyond that even the strips three halo widths from the edges read ghost columns). wx_slab_step /
  * wx_group_step do all of this themselves without a host round trip inside a period: the maxima travel with the exchange (one word per
@@ -468,7 +470,8 @@ int wx_group_sync(wx_group *g);
  * lightning requests. */
 
 /* The largest |velocity component| [cells / iteration] among the cells the marching wet kernel handed to its exact path (back-traces
- * of 0.9 cells and more) since the last call; 0 if there was none; NaN if a velocity was NaN. Resets the value; synchronises the
+ * of 0.9 cells and more) since the last call; 0 if there was none; +Inf if one of them was NaN or Inf (a NaN never shows as a small
+ * number: the state has blown up). Resets the value; synchronises the
  * handle's stream. Whole-domain handles and slabs are exact at any speed (slabs size their exchange period by the |vx| they measure:
  * wx_slab_set_vx_bound above); the value is a diagnostic of the flow, nothing more. */
 int wx_fastest_velocity(wx_sim *s, float *cells_per_iteration);

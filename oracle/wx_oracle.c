@@ -20,6 +20,7 @@
  *   - additive particle splats are summed in droplet-index order
  */
 #include "wx_oracle.h"
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -92,6 +93,18 @@ static inline int wrapmod(int i, int n)
   return r < 0 ? r + n : r;
 }
 static inline int gx_of(const geo_t *g, int x) { return wrapmod(g->xoff + x, g->Xg); }
+/* float -> int where the value may be anything (a blown-up state: NaN, Inf, a back-trace of 1e30 cells). C leaves the cast undefined
+ * out of range and GLSL too; DESIGN.md section 3 fixes it to one choice: NaN -> 0, everything else saturates to INT_MIN / INT_MAX.
+ * (2147483648.0f is exactly 2^31: every float below it fits, and the largest of them is 2^31 - 128.) */
+static inline int f2i_sat(float v)
+{
+  if (!(v == v)) return 0;
+  if (v >= 2147483648.0f) return INT_MAX;
+  if (v <= -2147483648.0f) return INT_MIN;
+  return (int)v;
+}
+/* i + d in 32-bit two's-complement arithmetic (a saturated tap index + 1 wraps to INT_MIN: still a defined cell after wrapmod) */
+static inline int add_wrap(int i, int d) { return (int)((unsigned)i + (unsigned)d); }
 /* simShader.vert:23 fragCoord, :24 texCoord */
 typedef struct {
   float fx, fy, tcx, tcy;
@@ -532,7 +545,7 @@ void wxo_boundary(const wxo_params *p, const float *initial_T, float iterNum, co
                 calcFireIntensity(wl[VEGETATION], w[SOIL_MOISTURE], waterX0Yp[PRECIPITATION]);
               if (fireIntensity < 0.002f) {
                 wl[TYPE] = WALLTYPE_LAND;
-              } else if (iterI % ((int)(10.0f / fireIntensity) + 1) == 0) {
+              } else if (iterI % add_wrap(f2i_sat(10.0f / fireIntensity), 1) == 0) { /* (>= 0.002 or NaN here: the divisor is 1 .. 5001) */
                 wl[VEGETATION] -= 1;
                 if (wl[VEGETATION] < 10) wl[TYPE] = WALLTYPE_LAND;
               }
@@ -570,18 +583,18 @@ void wxo_boundary(const wxo_params *p, const float *initial_T, float iterNum, co
                 w[SOIL_MOISTURE] += (avgNeighborSoilMoisture - w[SOIL_MOISTURE]) * moistureSmoothingRate;
               }
               const int vegetationGrowthRate =
-                (int)(w[SOIL_MOISTURE] * sqrtf(lightAboveSurface[SUNLIGHT]) * 0.01f);
+                f2i_sat(w[SOIL_MOISTURE] * sqrtf(lightAboveSurface[SUNLIGHT]) * 0.01f);
               if (vegetationGrowthRate > 0) {
                 const int interval = (100 / vegetationGrowthRate) * 100;
                 if (interval != 0 && iterI % interval == 0) { /* %0 undefined in GLSL -> false */
-                  if ((int)map_rangeC(realTempAboveSurface, CtoK(0.0f), CtoK(25.0f), 0.0f, 127.0f) > wl[VEGETATION])
+                  if (f2i_sat(map_rangeC(realTempAboveSurface, CtoK(0.0f), CtoK(25.0f), 0.0f, 127.0f)) > wl[VEGETATION])
                     wl[VEGETATION] += 1;
                 }
               }
               const int subInterval = iterI / 100;
               /* (soil moisture / snow far below zero -- a wall brush can leave them there -- make the divisor 0: undefined in GLSL as
                * above -> false; on the CPU the division would trap) */
-              const int fireDivisor = (int)(w[SOIL_MOISTURE] * 0.1f + w[SNOW] * 0.5f) + 10;
+              const int fireDivisor = add_wrap(f2i_sat(w[SOIL_MOISTURE] * 0.1f + w[SNOW] * 0.5f), 10);
               if (fireDivisor != 0 && subInterval % fireDivisor == 0 &&
                   wl[VEGETATION] >= 20 &&
                   (wL[TYPE] == WALLTYPE_FIRE || wR[TYPE] == WALLTYPE_FIRE || waterX0Yp[SMOKE] > 4.5f)) {
@@ -651,11 +664,11 @@ static inline taps_t mktaps(const geo_t *g, int x, int y, float posx, float posy
   const float flx = floorf(stx), fly = floorf(sty);
   t.fx = stx - flx;
   t.fy = sty - fly;
-  const int dx = (int)flx - gx_of(g, x); /* tap offset relative to own (global) column */
-  t.ix0 = wrapmod(x + dx, g->X);
-  t.ix1 = wrapmod(x + dx + 1, g->X);
-  t.iy0 = wrapmod((int)fly, g->Y);
-  t.iy1 = wrapmod((int)fly + 1, g->Y);
+  const int dx = add_wrap(f2i_sat(flx), -gx_of(g, x)); /* tap offset relative to own (global) column */
+  t.ix0 = wrapmod(add_wrap(x, dx), g->X);
+  t.ix1 = wrapmod(add_wrap(x, add_wrap(dx, 1)), g->X);
+  t.iy0 = wrapmod(f2i_sat(fly), g->Y);
+  t.iy1 = wrapmod(add_wrap(f2i_sat(fly), 1), g->Y);
   return t;
 }
 
@@ -1014,8 +1027,8 @@ static inline float light_linear_sun(const float *light, int X, int Y, int x, in
 {
   const float fu = floorf(ox), fv = floorf(oy);
   const float a = ox - fu, bb = oy - fv;
-  const int i0 = wrapmod(x + (int)fu, X), i1 = wrapmod(x + (int)fu + 1, X);
-  int j0 = y + (int)fv, j1 = y + (int)fv + 1;
+  const int i0 = wrapmod(add_wrap(x, f2i_sat(fu)), X), i1 = wrapmod(add_wrap(x, add_wrap(f2i_sat(fu), 1)), X);
+  int j0 = add_wrap(y, f2i_sat(fv)), j1 = add_wrap(y, add_wrap(f2i_sat(fv), 1));
   j0 = j0 < 0 ? 0 : (j0 > Y - 1 ? Y - 1 : j0);
   j1 = j1 < 0 ? 0 : (j1 > Y - 1 ? Y - 1 : j1);
   const float t00 = C4(light, i0, j0)[0], t10 = C4(light, i1, j0)[0];
@@ -1167,8 +1180,8 @@ void wxo_lighting(const wxo_params *p, const float *base_in, const float *water_
  * ---------------------------------------------------------------------------------------- */
 static inline const float *texfetch4(const float *tex, int X, int Y, float u, float v)
 {
-  const int ix = wrapmod((int)floorf(u * (float)X), X);
-  const int iy = wrapmod((int)floorf(v * (float)Y), Y);
+  const int ix = wrapmod(f2i_sat(floorf(u * (float)X)), X);
+  const int iy = wrapmod(f2i_sat(floorf(v * (float)Y)), Y);
   return C4(tex, ix, iy);
 }
 

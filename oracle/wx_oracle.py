@@ -12,7 +12,9 @@ from typing import Any, Dict, Optional
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.path.join(_HERE, "libwxoracle.so")
+# WX_ORACLE_LIB: another build of the same source, by file name (libwxoracle_ubsan.so: `make ubsan`, what tests/test_blowup_cpu.py runs
+# in a child process); build() makes that file's own target when it is stale
+_LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ.get("WX_ORACLE_LIB", "")) or "libwxoracle.so")
 
 
 class OracleParams(C.Structure):
@@ -60,7 +62,7 @@ def build(force: bool = False) -> str:
     stale = (not os.path.exists(_LIB_PATH)) or any(
         os.path.getmtime(f) > os.path.getmtime(_LIB_PATH) for f in (src, hdr))
     if force or stale:
-        subprocess.check_call(["make", "-C", _HERE, "-s", "libwxoracle.so"])
+        subprocess.check_call(["make", "-C", _HERE, "-s", os.path.basename(_LIB_PATH)])
     return _LIB_PATH
 
 
