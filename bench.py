@@ -13,10 +13,17 @@ on a side stream; `--workload dry --X 32768 --Y 4096` runs BASELINE's north-star
 one rank per GPU. An N-rank grid run is self-validating by default (`--no-verify` switches it off): every rank checksums its owned columns and
 rank 0 compares them with an undecomposed run of the same state (`"verify": "ok"`, `ranks_seen`, `transport` in the line).
 Prints one JSON line on rank 0 (contract in the task description): throughput with inputs resident in HBM, plus `roofline`
-(dominant kernel, HIP-event timed on the engine's stream), `cpu_baseline` (the CPU oracle timed on this box's host cores, N = 1 only),
-`hbm_ceiling` (tools/ubench_hbm: read / write / copy streams with the kernels' own access pattern) and `north_star_dry` (N = 1 only):
-BASELINE.json's north-star stencil -- the fused pressure + velocity + advection kernel on a 32768 x 4096 dry grid -- measured in
-the same process with its own roofline, at rest and on the moving fluid.
+(dominant kernel, HIP-event timed on the engine's stream inside the timed region itself).
+A plain run does what that figure needs and nothing else: set-up (with the placement search), the still-state iterations the timed
+state descends from, seeding, warm-up, clock conditioning, the timed steps, the dump, the line. `--full` adds the side measurements,
+each with a switch of its own (`--no-...`) to leave it out again: `at_rest`, `frame_1`, `roofline.measured_copy_GBps` and
+`hbm_ceiling` (tools/ubench_hbm: read / write / copy streams with the kernels' own access pattern), `roofline.traffic` / `valu`
+(rocprofv3 --pmc passes over short runs of this script), `cpu_baseline` (the CPU oracle timed on the host's cores), `north_star_dry`
+(BASELINE.json's north-star stencil -- the fused pressure + velocity + advection kernel on a 32768 x 4096 dry grid -- measured in the
+same process with its own roofline, at rest and on the moving fluid), `configs` (BASELINE's other single-GPU configurations and the
+reference's own grid sizes) and `arith_fast` (the tolerance build, in a run of its own); on N > 1 ranks `strong_scaling_vs_n1` and
+`per_rank`. They all come after the timed region or, like `at_rest`, only read a clock around iterations a plain run issues too: the
+headline `value`, `ms_per_step` and what --dump-outputs writes are the same with and without `--full`.
 `--dump-outputs DIR` (N = 1) writes what the last timed iteration left in the handle -- the fields a caller of wx_step reads back -- as
 DIR/<field>.npy (see dump_outputs()). Everything that runs on the timed handle before that point is a fixed number of iterations of a
 seeded start state, so two runs with the same arguments (of this build or of another one) write the same arrays.
@@ -66,6 +73,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--X", type=int, default=16384)
     ap.add_argument("--Y", type=int, default=2048)
+    ap.add_argument("--full", action="store_true",
+                    help="also take the side measurements (see the module docstring); the --no-... options below each leave one group of them out again. "
+                         "Without it the run is the headline figure alone and those options change nothing, except what --no-extras says")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the short rocprofv3 --pmc passes that fill roofline.traffic")
     ap.add_argument("--workload", choices=["wet", "dry"], default="wet",
@@ -78,7 +88,9 @@ def parse():
                     help="eddies: smooth divergence-free eddies of 50..400 cells (a developed flow; default); noise: white noise per cell (worst case for the ring reads)")
     ap.add_argument("--no-north-star", action="store_true", help="skip the 32768 x 4096 dry north-star measurement (N=1)")
     ap.add_argument("--no-arith-fast", action="store_true", help="skip the side measurement of the opt-in tolerance build (csrc/libwxsim_fast.so) reported as the EXTRA key `arith_fast` (N=1)")
-    ap.add_argument("--no-extras", action="store_true", help="skip at_rest / frame-1 / hbm_ceiling side measurements (N=1)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="skip at_rest / frame-1 / hbm_ceiling side measurements (N=1) -- and, with or without --full, the still-state iterations "
+                         "at_rest times before the flow is seeded: the timed region then starts from another state than the default command's")
     ap.add_argument("--tune", type=int, default=20, help="wx_tune_placement: further device allocations to try for the handle's planes (0: keep the first)")
     ap.add_argument("--dry-pairs", type=int, default=1, choices=[0, 1], help="dry stencil: WX_OPT_DRY_PAIRS (two iterations per launch; round 5 prototype)")
     ap.add_argument("--verify", dest="verify", action="store_true", default=True,
@@ -88,6 +100,9 @@ def parse():
                     help="N = 1: after the timed steps write the fields the last timed iteration produced as DIR/<field>.npy (float32; at most 64 MB: a seeded sample of the cells of a larger grid)")
     a = ap.parse_args()
     a.frame = max(1, a.frame)  # (0 or a negative value would never advance run_frames)
+    a.still_prelude = not a.no_extras  # (the timed handle's history: the same with and without --full)
+    if not a.full:  # a plain run: every side measurement off, as if its own switch had been given
+        a.no_cpu_baseline = a.no_pmc = a.no_north_star = a.no_arith_fast = a.no_extras = True
     if a.dump_outputs and a.gpus != 1:
         ap.error("--dump-outputs writes the undecomposed handle's fields: --gpus 1 only")
     return a
@@ -177,8 +192,7 @@ def pmc_traffic(a, kernel, X=None, Y=None, workload=None):
             # one per frame that also writes the display fields
             nfr = max(1, int(a.frame))
             cmd = [exe, "--pmc", counter, "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--steps", str(nfr), "--warmup", str(nfr),
-                   "--X", str(X or a.X), "--Y", str(Y or a.Y), "--workload", workload or a.workload, "--no-cpu-baseline", "--no-pmc",
-                   "--no-north-star", "--no-extras", "--no-arith-fast", "--frame", str(a.frame), "--flow", str(a.flow), "--flow-kind", a.flow_kind, "--tune", "0", "--dry-pairs", str(a.dry_pairs)]
+                   "--X", str(X or a.X), "--Y", str(Y or a.Y), "--workload", workload or a.workload, "--no-extras", "--frame", str(a.frame), "--flow", str(a.flow), "--flow-kind", a.flow_kind, "--tune", "0", "--dry-pairs", str(a.dry_pairs)]
             env = dict(os.environ, TMPDIR="/tmp")
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=240, check=True)
             dbs = [os.path.join(r, f) for r, _, fs in os.walk(d) for f in fs if f.endswith(".db")]
@@ -207,7 +221,7 @@ def arith_fast_entry(a):
     if not os.path.exists(fast) or os.environ.get("WXSIM_LIB"):
         return None
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(a.steps), "--warmup", str(a.warmup), "--X", str(a.X), "--Y", str(a.Y), "--workload", a.workload,
-           "--frame", str(a.frame), "--flow", str(a.flow), "--flow-kind", a.flow_kind, "--tune", str(min(a.tune, 6)), "--no-cpu-baseline", "--no-pmc", "--no-extras", "--no-arith-fast"]
+           "--frame", str(a.frame), "--flow", str(a.flow), "--flow-kind", a.flow_kind, "--tune", str(min(a.tune, 6)), "--full", "--no-cpu-baseline", "--no-pmc", "--no-extras", "--no-arith-fast"]
     if a.no_north_star:
         cmd.append("--no-north-star")
     try:
@@ -678,12 +692,16 @@ def main():
     at_rest = None
     # one GPU: a fixed count (the state after the timed region is a function of the arguments: --dump-outputs); N ranks: by the clock, agreed
     cond_iters = conditioning_iterations(X * Y, a.frame, a.workload) if world == 1 else None
-    if world == 1 and a.flow > 0 and not a.no_extras and not a.particles:  # the still start state first (round 2's definition)
+    if world == 1 and a.flow > 0 and a.still_prelude and not a.particles:  # the still start state first (round 2's definition)
+        # These warm-up + conditioning + --steps iterations are part of the timed handle's history: the flow is seeded on top of what they
+        # leave, and the timed region and --dump-outputs descend from that. A plain run therefore issues them exactly like --full, which
+        # alone reports them as `at_rest`.
         run_frames(step, a.warmup, a.frame)
         condition_clocks(step, sync, a.frame, iters=cond_iters)
         dt0, _ = timed_run(stepper, a.steps, a.frame, profile=False)
-        at_rest = {"value": X * Y * a.steps / dt0 / 1e6, "ms_per_step": dt0 / a.steps * 1e3, "flow": devtools.flow_stats(stepper),
-                   "state": "still start state (what round 2 timed)", "placement": "the kept one (same as value)"}
+        if a.full:
+            at_rest = {"value": X * Y * a.steps / dt0 / 1e6, "ms_per_step": dt0 / a.steps * 1e3, "flow": devtools.flow_stats(stepper),
+                       "state": "still start state (what round 2 timed)", "placement": "the kept one (same as value)"}
     if a.flow > 0:  # a moving fluid: identical on slabs and on the undecomposed grid (function of the global cell index)
         devtools.seed_flow(stepper, a.flow, Xg=X, x0=x0_owned, kind=a.flow_kind)
     flow0 = devtools.flow_stats(stepper)
@@ -759,11 +777,11 @@ def main():
                 verify = "ok" if not bad else "MISMATCH: " + ", ".join(bad)
         elif a.verify:
             verify = "not available with particles (a period may differ from the undecomposed run by a few re-spawn probes: tests/test_gpu_fullsize.py quantifies it)"
-        # Round-5 verdict, item 7: what the curve decomposes into, measured in THIS run on rank 0's GPU while the other ranks wait in the final
+        # --full (round-5 verdict, item 7): what the curve decomposes into, measured in THIS run on rank 0's GPU while the other ranks wait in the final
         # barrier -- (a) the same grid UNDECOMPOSED on the same box (`strong_scaling_vs_n1`: SCALE's N = 1 point without a second run; the handle
         # searches its placement inside its first step), (b) this rank's slab with NO exchange at all (`per_rank.plain_slab_ms_per_step`: the
         # kernel on a narrow launch; the rest of ms_per_step is the exchange protocol + the link).
-        if rank == 0 and not a.particles:
+        if rank == 0 and a.full and not a.particles:
             try:
                 if whole is None:
                     whole = make_whole()

@@ -23,6 +23,28 @@ def test_conditioning_count_is_a_function_of_the_arguments():
     assert bench.conditioning_iterations(100 * 100, 10, "wet") == 10000  # launch-bound grids: 25 us per iteration
 
 
+def test_a_plain_run_takes_no_side_measurement(monkeypatch):
+    """Without --full every side measurement is off, whatever --no-... options are given; the still-state iterations the timed state
+    descends from are run with and without it, and --no-extras alone leaves them out."""
+    import bench
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+
+    def off(a):
+        return [a.no_cpu_baseline, a.no_pmc, a.no_north_star, a.no_arith_fast, a.no_extras]
+
+    a = parsed("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert not a.full and all(off(a)) and a.still_prelude and (a.steps, a.warmup, a.tune, a.frame) == (20, 5, 20, 10)
+    a = parsed("--full")
+    assert a.full and not any(off(a)) and a.still_prelude
+    a = parsed("--full", "--no-pmc", "--no-extras")
+    assert off(a) == [False, True, False, False, True] and not a.still_prelude
+    a = parsed("--no-extras")
+    assert all(off(a)) and not a.still_prelude
+
+
 def _bench(out_dir, steps, grid, *extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "3", "--X", str(grid[0]), "--Y", str(grid[1]),
            "--no-cpu-baseline", "--no-pmc", "--no-north-star", "--no-arith-fast", "--tune", "2", "--dump-outputs", str(out_dir)] + list(extra)
@@ -53,11 +75,14 @@ def test_dump_is_reproducible_and_steps_sets_the_timed_iterations(tmp_path):
 
 @pytest.mark.gpu
 def test_dump_of_a_large_grid_is_a_seeded_sample_with_sums_over_every_cell(tmp_path):
-    """With the side measurements that run on the timed handle before the fluid is seeded (at_rest), like the default command."""
+    """With the still-state iterations that run on the timed handle before the fluid is seeded, like the default command -- a plain
+    run, and one with the side measurements that --full times around them and after the dump (at_rest, frame_1): the same bytes."""
     X, Y = 1024, 256
     d1, a1 = _bench(tmp_path / "a", 20, (X, Y))
-    d2, a2 = _bench(tmp_path / "b", 20, (X, Y))
-    assert "at_rest" in d1 and sorted(a1) == sorted(a2) == sorted(WET_FIELDS + [f + s for f in WET_FIELDS for s in ("_colsum", "_rowsum")])
+    d2, a2 = _bench(tmp_path / "b", 20, (X, Y), "--full")
+    assert "at_rest" in d2 and "frame_1" in d2 and not {"at_rest", "frame_1", "hbm_ceiling", "configs", "cpu_baseline", "north_star_dry", "arith_fast"} & set(d1)
+    assert d1["dump_outputs"]["iteration"] == d2["dump_outputs"]["iteration"] == 2 * (3 + 10000 + 20)  # still, then moving: warm-up + conditioning + steps
+    assert sorted(a1) == sorted(a2) == sorted(WET_FIELDS + [f + s for f in WET_FIELDS for s in ("_colsum", "_rowsum")])
     K = (32 << 20) // (4 * 37)
     assert K < X * Y
     for f in WET_FIELDS:

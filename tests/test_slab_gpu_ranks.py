@@ -131,7 +131,7 @@ def test_bench_verify_two_ranks(workload, grid):
     env = dict(os.environ, WX_BENCH_SHARE_GPU="1", WX_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "8", "--X", str(grid[0]),
-           "--Y", str(grid[1]), "--workload", workload, "--verify", "--no-pmc"]
+           "--Y", str(grid[1]), "--workload", workload, "--verify", "--full", "--no-pmc"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     line = [l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1]
