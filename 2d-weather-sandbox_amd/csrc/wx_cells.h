@@ -496,7 +496,9 @@ __device__ __forceinline__ void boundary_cell(const UT &u, const float iterNum, 
             }
           }
           const int subInterval = iterI / 100;
-          if (subInterval % ((int)(w.z * 0.1f + w.w * 0.5f) + 10) == 0 && wl[VEGETATION] >= 20 &&
+          // (soil moisture / snow far below zero -- the ABI accepts such a state -- make the divisor 0: undefined in GLSL -> false, as the oracle)
+          const int fireDivisor = (int)(w.z * 0.1f + w.w * 0.5f) + 10;
+          if (fireDivisor != 0 && subInterval % fireDivisor == 0 && wl[VEGETATION] >= 20 &&
               (wL.x == WALLTYPE_FIRE || wR.x == WALLTYPE_FIRE || waterX0Yp.w > 4.5f)) {
             wl[TYPE] = WALLTYPE_FIRE;
           }

@@ -704,6 +704,157 @@ def fx_sliders64_lightning():
                        iter0=40, keep=("base_disp", "water_cur"), points=True)
 
 
+
+# ------------------------------------------------------------------------------------------------
+# surface64: the slow physics of the surface row (boundaryShader.frag:305-480) -- vegetation growth, fire spread and burn-down, the
+# industrial chimneys, dust, the sea's temperature reset. Drawn as GL_POINTS. Each scene is built so that the reference's own dumps
+# show the event (tests/test_oracle_surface.py asserts it from them).
+# ------------------------------------------------------------------------------------------------
+def surface_terrain(X, Y, rng, height, types, veg, soil, snow, gui=None, sun=80.0, wind=0.02):
+    """Hand-built terrain: per column the wall rows, surface type, vegetation, soil moisture and snow; quiet moist air above."""
+    if gui is None:
+        gui = dict(pkg.params.GUI_DEFAULTS)
+        gui["sunAngle"] = sun
+    u = pkg.params.uniforms_from_gui(gui, Y)
+    T0 = u["initial_T"]
+    base = np.zeros((Y, X, 4), np.float32)
+    water = np.zeros((Y, X, 4), np.float32)
+    wall = np.zeros((Y, X, 4), np.int8)
+    for x in range(X):
+        h, t = int(height[x]), int(types[x])
+        wall[:, x, 0] = t
+        wall[:h, x, 2] = np.arange(-(h - 1), 1)
+        wall[:h, x, 3] = veg[x]
+        wall[h:, x, 1] = np.minimum(np.arange(1, Y - h + 1), 127)
+        wall[h:, x, 2] = np.minimum(np.arange(1, Y - h + 1), 127)
+        base[:h, x, 3] = 298.15 if t == 2 else 1000.0
+        water[:h, x, 0] = 1002.0 if t == 2 else 1001.0
+        water[:h, x, 2] = 100.0 if t == 2 else soil[x]
+        water[:h, x, 3] = 0.0 if t == 2 else snow[x]
+    yy = np.arange(Y)[:, None]
+    air = wall[..., 1] != 0
+    base[..., 3] = np.where(air, T0[:Y][:, None] + rng.normal(0, 0.1, (Y, X)).astype(np.float32), base[..., 3])
+    base[..., 0] = np.where(air, rng.normal(0, wind, (Y, X)), 0).astype(np.float32)
+    base[..., 1] = np.where(air, rng.normal(0, wind, (Y, X)), 0).astype(np.float32)
+    realT = base[..., 3] - ((yy + 0.5) / Y) * u["dryLapse"]
+    water[..., 0] = np.where(air, (realT / 250.0) ** 17 * 0.6, water[..., 0]).astype(np.float32)
+    return gui, u, base, water, wall
+
+
+def _trim(name, out, keep_full, its):
+    """Re-save a fixture with base / water kept at the dumps ``keep_full`` only (the wall texture at every dump)."""
+    path = os.path.join(OUT_DIR, name + ".npz")
+    dropped = tuple(f"it{it}_" for it in its if it not in keep_full)
+    keep = {k: v for k, v in out.items() if k.endswith("wall_cur") or not k.startswith(dropped)}
+    np.savez_compressed(path, **keep)
+    print(f"[{name}] trimmed: {os.path.getsize(path) / 1024:.0f} KiB")
+
+
+def fx_surface64_growth(it_growth=9_240_000, name="surface64_growth"):
+    """Vegetation growth: flat and stepped land whose soil moisture makes every rate 1 .. 10 occur under full sunlight (and, soaked,
+    rates beyond 100: interval 0), vegetation below and above the temperature cap. The sunlight needs Y iterations to come down, so
+    the run starts 70 iterations before ``it_growth`` -- 9 240 000, the least common multiple of the ten intervals (exact as a float);
+    10 000 in the second fixture, where rates 3 and 6 .. 9 must NOT grow."""
+    rng = np.random.default_rng(8101)
+    # 64 rows. With fewer than 50 the top row's texCoord.y is below 0.99, so boundaryShader's "wall above -> wall" rule (the row above the
+    # top row is row 0, the ground) fills it, then the row under it: a ceiling comes down one row per iteration and no sunlight with it
+    X, Y = 64, 64
+    x = np.arange(X)
+    height = np.where((x >= 40) & (x < 52), 4, 2) + np.where((x >= 44) & (x < 48), 3, 0)
+    types = np.ones(X, np.int64)
+    soil = 2.0 + 0.5 * x  # 2 .. 33.5: rate (int)(soil * sqrt(light) * 0.01) = 0 .. 11 at ~1270 W/m2
+    soil[56:] = (150.0, 300.0, 450.0, 600.0, 800.0, 1000.0, 290.0, 285.0)  # rates 50 .. 350: (100 / rate) * 100 is 100 or 0
+    veg = np.where(x % 3 == 0, 100, np.where(x % 3 == 1, 20, 45))  # above the cap (about 55 at 11 C), far below, below
+    snow = np.zeros(X)
+    gui, u, base, water, wall = surface_terrain(X, Y, rng, height, types, veg, soil, snow)
+    pre = 70
+    its = [pre, pre + 1, pre + 5]
+    out = run_fixture(name, X, Y, base, water, wall, None, u, niter=pre + 5, dump_iters=its, precip=False, iter0=it_growth - pre,
+                      keep=("base_cur", "water_cur", "wall_cur", "light_0", "light_1"), points=True)
+    _trim(name, out, (pre + 1,), its)
+
+
+def _fire_strip(rng, X=64, Y=48):
+    """Flat land, two wall rows, vegetation 60, soil moisture 5 (spread divisor 10), quiet air."""
+    return dict(height=np.full(X, 2), types=np.ones(X, np.int64), veg=np.full(X, 60), soil=np.full(X, 5.0), snow=np.zeros(X))
+
+
+def fx_surface64_fire():
+    """How a fire ENDS: vegetation 10 on soil moisture 1 burns every 4348th iteration (intensity 0.0023) down to 9 and back to land;
+    rain above a fire and soaked soil under another put them out at once; a fourth keeps burning. Twelve iterations from iterNum 8690:
+    8696 = 2 x 4348; 8700 smooths, but 87 is a multiple of no divisor here (10 beside the fires): nothing may spread."""
+    rng = np.random.default_rng(8102)
+    X, Y = 64, 48
+    t = _fire_strip(rng)
+    types, veg, soil = t["types"], t["veg"], t["soil"]
+    types[12] = 3  # keeps burning: smoke and heat above it
+    types[30], veg[30], soil[30] = 3, 10, 1.0  # burn-down
+    types[34], veg[34] = 3, 90  # rain above it
+    types[38], veg[38], soil[38] = 3, 60, 300.0  # soaked
+    gui, u, base, water, wall = surface_terrain(X, Y, rng, t["height"], types, veg, soil, t["snow"], wind=0.005)
+    water[2:6, 33:36, 2] = 3.0   # precipitation (display channel) over the fire at 34
+    water[2:4, 11:14, 3] = 5.0   # flames
+    its = [1, 5, 6, 7, 11, 12]
+    out = run_fixture("surface64_fire", X, Y, base, water, wall, None, u, niter=12, dump_iters=its, precip=False, iter0=8690,
+                      keep=("base_cur", "water_cur", "wall_cur"), points=True)
+    _trim("surface64_fire", out, (1, 7, 12), its)
+
+
+SPREAD_RINGS = ((5.0, 0.0), (15.0, 0.0), (5.0, 3.4), (22.0, 2.4))  # (soil moisture, snow) at distance 1 .. 4: divisors 10, 11, 12, 13
+
+
+def fx_surface64_spread():
+    """How a fire SPREADS, over four smoothing iterations: from iterNum 995 a fire at column 12 takes one cell each way at 1000, 1100,
+    1200 and 1300, because the rings around it carry soil moisture / snow whose divisors `(int)(soil * 0.1 + snow * 0.5) + 10` are 10,
+    11, 12 (dry, under snow) and 13 (moist, under snow) -- each a value that a wrong factor moves to another integer. A second fire
+    between vegetation 20 (ignites) and 19 (never). Smoke of 4.9, 5.3 and 4.3 over vegetated land: above 4.5 ignites at 1000."""
+    rng = np.random.default_rng(8104)
+    X, Y = 64, 64  # (not 48: see fx_surface64_growth -- below 50 rows the ceiling comes down and the domain is solid after Y iterations)
+    t = _fire_strip(rng)
+    types, veg, soil, snow = t["types"], t["veg"], t["soil"], t["snow"]
+    types[12] = 3
+    for d, (so, sn) in enumerate(SPREAD_RINGS, start=1):
+        for xx in (12 - d, 12 + d):
+            soil[xx], snow[xx] = so, sn
+    types[26] = 3
+    veg[25], veg[27] = 20, 19
+    gui, u, base, water, wall = surface_terrain(X, Y, rng, t["height"], types, veg, soil, snow, wind=0.005)
+    water[2:4, 11:14, 3] = 5.0    # flames
+    water[2:6, 36:43, 3] = 4.9    # smoke over vegetated land: above the threshold
+    water[2:6, 45:52, 3] = 5.3
+    water[2:6, 54:61, 3] = 4.3    # below it
+    its = [5, 6, 105, 106, 205, 206, 305, 306, 310]
+    out = run_fixture("surface64_spread", X, Y, base, water, wall, None, u, niter=310, dump_iters=its, precip=False, iter0=995,
+                      keep=("base_cur", "water_cur", "wall_cur"), points=True, timeout=1200.0)
+    _trim("surface64_spread", out, (5, 6, 310), its)
+
+
+def fx_surface112_industry():
+    """Industry, dust and the sea: industrial surface under the columns with x % 80 = 17 .. 30 in the first period AND the second
+    (X = 112: the modulus is not the identity), urban cells with vegetation 100 beside it (caps 15 / 75), bare dry soil under wind
+    (dust), sea cells uploaded at 600 K across iterNum 100 (a multiple of 20: reset to 25 C)."""
+    rng = np.random.default_rng(8103)
+    X, Y = 112, 40
+    x = np.arange(X)
+    height = np.full(X, 2)
+    types = np.ones(X, np.int64)
+    types[(x % 80 >= 17) & (x % 80 <= 30)] = 6
+    types[(x >= 32) & (x < 38)] = 4
+    types[(x >= 60) & (x < 72)] = 2
+    veg = np.full(X, 100)
+    veg[40:56] = np.where(x[40:56] % 2 == 0, 5, 12)  # bare (below 10) and not
+    soil = np.full(X, 20.0)
+    soil[40:56] = 1.0  # (the dust line does not read it: its "soil moisture" is channel 2 of the AIR cell, the precipitation there)
+    snow = np.zeros(X)
+    gui, u, base, water, wall = surface_terrain(X, Y, rng, height, types, veg, soil, snow)
+    base[2:8, 38:58, 0] = 0.35  # wind over the bare soil
+    water[2, [44, 46], 2] = 6.0  # precipitation of 5 and more in the first air cell of two bare columns: no dust there
+    base[:2, 62:66, 3] = 600.0  # sea far above 500 K
+    base[:2, 66:68, 3] = 499.0  # and just below: clamped, not reset
+    return run_fixture("surface112_industry", X, Y, base, water, wall, None, u, niter=10, dump_iters=[1, 10], perpass_iter=0, precip=False, iter0=100,
+                       keep=("base_cur", "water_cur", "wall_cur"), points=True, keep_perpass=("boundary_base", "boundary_water", "boundary_wall"))
+
+
 FIXTURES = {
     "randwalls64": fx_randwalls64,
     "brush64": fx_brush64,
@@ -720,6 +871,11 @@ FIXTURES = {
     "setup256": fx_setup256,
     **{f"sliders64_{k:02d}": (lambda k=k: fx_sliders64(k)) for k in range(SLIDERS64_N)},
     "sliders64_lightning": fx_sliders64_lightning,
+    "surface64_growth": fx_surface64_growth,
+    "surface64_growth10k": lambda: fx_surface64_growth(10_000, "surface64_growth10k"),
+    "surface64_fire": fx_surface64_fire,
+    "surface64_spread": fx_surface64_spread,
+    "surface112_industry": fx_surface112_industry,
 }
 
 if __name__ == "__main__":

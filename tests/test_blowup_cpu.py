@@ -14,6 +14,7 @@ import pytest
 
 import blowup_scenes as B
 import impulse_scenes as I
+import surface_scenes as S
 from test_impulse_cpu import _missing
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,14 +26,16 @@ import hashlib, json, sys
 sys.path[:0] = [%(root)r, %(root)r + "/oracle", %(root)r + "/tests"]
 import numpy as np
 import blowup_scenes as B
+import surface_scenes as S
 import wx_oracle
 names = json.loads(sys.argv[1])
 out = {}
-def run(name, X, Y, scene, u, n):
+def run(name, X, Y, scene, u, n, iter0=0):
     base, water, wall, drops, _ = scene
     o = wx_oracle.OracleSim(X, Y, 0 if drops is None else len(drops))
     o.upload(base, water, wall, drops)
     o.set_params(u)
+    o.iter = iter0
     h = hashlib.sha256()
     for _ in range(n):
         o.step(1)
@@ -51,6 +54,11 @@ if "droplets" in names:
 for sp in B.GROWN_SPEEDS:
     if "grown%%d" %% sp in names:
         run("grown%%d" %% sp, B.GROWN_GRID[0], B.GROWN_GRID[1], B.grown_scene(B.GROWN_GRID[0], B.GROWN_GRID[1], sp), B.scene_uniforms(B.GROWN_GRID[1]), B.GROWN_ITERATIONS)
+for kind in S.DIVISOR_KINDS:  # the fire divisor 0 / -10 (surface_scenes.divisor_scene), first iteration at iterNum 1000
+    for variant in S.VARIANTS:
+        if "%%s-%%s" %% (kind, variant) in names:
+            b, w, wl, sites = S.divisor_scene(S.PHASE_GRID[0], S.PHASE_GRID[1], kind, offset=1, variant=variant)
+            run("%%s-%%s" %% (kind, variant), S.PHASE_GRID[0], S.PHASE_GRID[1], (b, w, wl, None, sites), S.scene_uniforms(S.PHASE_GRID[1]), %(n)d, iter0=1000)
 print(json.dumps(out))
 """
 
@@ -59,7 +67,7 @@ def _names():
     n = []
     for c in B.cases():
         n += [B.case_id(c) + ("-dry" if dry else "") for dry in sorted({cfg.startswith("dry") for cfg in c["configs"]})]
-    return n + ["droplets"] + ["grown%d" % sp for sp in B.GROWN_SPEEDS]
+    return n + ["droplets"] + ["grown%d" % sp for sp in B.GROWN_SPEEDS] + [f"{k}-{v}" for k in S.DIVISOR_KINDS for v in S.VARIANTS]
 
 
 def _child(names, lib=None, threads=None):

@@ -225,3 +225,21 @@ def test_slabs_report_a_nonfinite_vx(pkg, mode, nslab, where):
         assert "vx" in str(ei.value), str(ei.value)
     finally:
         g.close()
+
+
+@pytest.mark.parametrize("variant", ["flat", "stepped"])
+@pytest.mark.parametrize("kind", ["divisor_soil", "divisor_snow"])
+def test_fire_divisor_zero_and_negative_vs_oracle(pkg, oracle, fuzz, kind, variant):
+    """surface_scenes.divisor_scene: uploaded soil moisture / snow far below zero make the fire-spread divisor of the sites 0 (`% 0`:
+    fixed to false, guarded on both sides -- no integer division by zero is executed) and -10 (ignites at iterNum 1000), under smoke
+    that would light every site. Wet marching (display / plain / MORE_TO_COME, stored waterTexture_0, row bands) and per-pass, lattice
+    offsets that put the sites on the first and last output lanes of a strip, bit for bit."""
+    import surface_scenes as S
+    X, Y = S.PHASE_GRID
+    for off in (0, 2, 4):
+        scene = S.divisor_scene(X, Y, kind, offset=off, variant=variant)
+        for config in B.WET_CONFIGS + B.BAND_CONFIGS[:2]:
+            bad, wall = S.run_scene(pkg, fuzz, oracle, scene, X, Y, config, 1000, fuzz.IMPULSE_CONFIGS[config].get("steps", (1, 1, 3)))
+            assert not bad, json.dumps({"kind": kind, "variant": variant, "offset": off, "config": config, "mismatches": bad})
+            lit = [int(wall[y, x, 0]) == S.FIRE for x, y in scene[3]]
+            assert lit == S.divisor_sites_lit(X, scene[3], variant), (config, lit)

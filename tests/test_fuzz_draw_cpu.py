@@ -21,6 +21,10 @@ DIGESTS = {
 }
 
 
+# sha256 of json.dumps of the "surface" entries draw_surface adds to the first 150 cases of seed 11
+SURFACE_DIGEST = "73dc00380a0eefaecfb41cf57eee0e2dcb43c441c29c7fa9809c53dc84878195"
+
+
 def _recipes(mode, seed, n=150):
     rng, rng_script = np.random.default_rng(seed), np.random.default_rng(seed + 2000003)
     out = []
@@ -75,3 +79,28 @@ def test_scripts_are_a_function_of_the_seed_and_leave_the_scenes_alone():
     assert kinds == set(fuzz_parity.SCRIPT_ACTIONS + ["step"]) - {"pieces"}, kinds
     assert any(s.get("first_piece") for c in a for s in c["script"])
     json.loads(json.dumps(a))  # a recipe is plain JSON: it alone reproduces the case
+
+
+def test_the_surface_draw_is_a_function_of_the_case_and_reaches_the_life_cycle():
+    """draw_surface adds the recipe key "surface" without a draw from the case's generator (the digests above hold, recipes without the
+    key run as before), is pinned by a digest of its own, and over 300 cases reaches every surface type, vegetation on both sides of
+    the fire floor (20) and the bare-soil limit (10), soaked and dry soil, snow, and a first iteration at most 8 below a multiple of
+    100, 1000, 10 000 and 9 240 000 -- among them runs that START on such a multiple."""
+    cs = [fuzz_parity.draw_surface(c)["surface"] for c in _recipes("oracle", 11, 300)]
+    assert cs == [fuzz_parity.draw_surface(c)["surface"] for c in _recipes("oracle", 11, 300)]
+    assert hashlib.sha256(json.dumps(cs[:150], sort_keys=True).encode()).hexdigest() == SURFACE_DIGEST
+    assert all("surface" not in c for c in _recipes("oracle", 11, 20))
+    st = [s for c in cs for s in c["stretches"]]
+    assert {s[2] for s in st} == set(fuzz_parity.SURFACE_TYPES)
+    veg, soil, snow = [s[3] for s in st], [s[4] for s in st], [s[5] for s in st]
+    assert min(veg) < 10 and any(10 <= v < 20 for v in veg) and max(veg) > 100 and 0 <= min(veg) and max(veg) <= 127
+    assert min(soil) == 0.0 and max(soil) > 500.0 and max(soil) <= 1000.0 and max(snow) > 1000.0 and max(snow) <= 4000.0
+    its = [c["iter0"] for c in cs if c["iter0"] is not None]
+    assert 100 < len(its) < 250
+    for base in (100, 1000, 10000, 9240000):
+        assert any(0 < (-i) % base <= 8 for i in its) and any(i % base == 0 for i in its), base
+    c = fuzz_parity.draw_surface(_recipes("oracle", 11, 1)[0])
+    assert fuzz_parity.case_iter0(c) == (c["iter0"] if c["surface"]["iter0"] is None else c["surface"]["iter0"])
+    for f in ("fuzz_group_regressions.json", "fuzz_script_regressions.json"):
+        with open(os.path.join(ROOT, "tests", "golden", f)) as fh:
+            assert all("surface" not in r["recipe"] for r in json.load(fh))

@@ -53,6 +53,25 @@ def test_fuzz_slabs_against_one_handle(pkg, oracle, fuzz, seed):
     assert compared >= 100, (ran, compared)
 
 
+@pytest.mark.parametrize("seed", [21, 22])
+def test_fuzz_surface_life_cycle_against_the_oracle(pkg, oracle, fuzz, seed):
+    """Drawn cases with fuzz_parity.draw_surface on top: fire / urban / runway / industrial stretches, vegetation, soil moisture and
+    snow over their ranges, the first iteration just below (or on) a multiple of 100 / 1000 / 10 000 / 9 240 000. Seeds of their own:
+    the cases of the tests above are what they were."""
+    rng = np.random.default_rng(seed)
+    compared = smoothing = 0
+    for k in range(120):
+        c = fuzz.draw_surface(fuzz.draw_more_sliders(fuzz.draw_case(rng, 120000)))
+        bad, info = fuzz.run_case(pkg, pkg.engine, oracle, c)
+        if info.get("error") or info.get("blown_up"):
+            continue
+        compared += 1
+        it0 = fuzz.case_iter0(c)
+        smoothing += int(c["terrain"] and not c["dry"] and any((it0 + j) % 100 == 0 for j in range(sum(c["steps"]))))
+        assert not bad, json.dumps({"seed": seed, "case": k, "recipe": c, "mismatches": bad})
+    assert compared >= 90 and smoothing >= 15, (compared, smoothing)
+
+
 def test_fuzz_regressions_of_round_6(pkg, fuzz):
     recs = json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_group_regressions.json")))
     assert len(recs) >= 3

@@ -135,6 +135,29 @@ def test_vs_reference_off_default_settings(pkg, golden, E, fused, name):
     assert len(out) >= 9 and S.check_against_reference(out, g, u) == []
 
 
+@pytest.mark.parametrize("name", ["surface112_industry", "surface64_fire", "surface64_growth", "surface64_growth10k", "surface64_spread"])
+def test_vs_reference_surface_scenes(pkg, golden, E, fused, name):
+    """HIP (quad_scale = 1) straight against the reference's own output on the surface fixtures (tests/test_oracle_surface.py): growth by
+    rate and interval, fire spread over four smoothing iterations, burn-down, rain, the chimneys, dust, the sea's reset -- so that a
+    misreading in csrc/wx_cells.h ALONE cannot hide behind the oracle. Walls bit for bit at every dump, fields within the bounds
+    stated there for the oracle."""
+    import test_oracle_surface as S
+    g, u = golden(name)
+    u = dict(u, quad_scale=1)
+    X, Y = int(g["X"]), int(g["Y"])
+    h = E.Handle(X, Y, 0)
+    h.upload(g["in_base"], g["in_water"], g["in_wall"])
+    h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"])
+    h.iter = int(g["iter0"])
+    out, done = {}, 0
+    for it in S.DUMPS[name]:
+        h.step(it - done)
+        done = it
+        out[it] = tuple(h.read_rect(f) for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR", "LIGHT_0", "LIGHT_1"))
+    assert h.iter == int(g["iter0"]) + done
+    assert S.check_fields(out, g, S.DUMPS[name]) == []
+
+
 @pytest.mark.parametrize("name", ["sliders64_01", "sliders64_04", "sliders64_07"])
 def test_sliders64_particles_bit_exact_vs_oracle(pkg, oracle, golden, E, fused, name):
     """The scenes with droplets and every precipitation control off default, 20 iterations with the particle pass on, against the

@@ -73,6 +73,44 @@ def draw_more_sliders(c):
     return c
 
 
+# The surface row's life cycle (tests/surface_scenes.py): surface types beyond land and sea on stretches of the terrain, vegetation /
+# soil moisture / snow over their clamped ranges, and a first iteration just below a multiple of 100 / 1000 / 10 000 / the least common
+# multiple of the growth intervals -- drawn like draw_more_sliders, as a function of the case (recipe key "surface").
+SURFACE_TYPES = (1, 3, 4, 5, 6)  # land, fire, urban, runway, industrial
+SURFACE_ITER_BASES = (100, 200, 1000, 2000, 10000, 30000, 9240000)
+
+
+def draw_surface(c):
+    """Adds c["surface"]: {"stretches": [[start, width (fractions of X), type, vegetation, soil moisture, snow], ...], "iter0": first
+    iteration or None (keep the case's)}. No draw from the case's generator."""
+    r = np.random.default_rng([int(c["data_seed"]) & 0x7FFFFFFF, 0x5FACE])
+    n = int(r.integers(1, 7)) if c["terrain"] else 0
+    st = [[float(r.random()), float(r.uniform(0.002, 0.15)), int(r.choice(SURFACE_TYPES)), int(r.integers(0, 128)),
+           float(r.choice([0.0, 3.0, 5.0, 25.0, 250.0, 1000.0]) * r.random()), float(r.choice([0.0, 0.0, 30.0, 4000.0]) * r.random())] for _ in range(n)]
+    it0 = int(r.choice(SURFACE_ITER_BASES)) - int(r.integers(0, 9)) if r.random() < 0.6 else None
+    c["surface"] = {"stretches": st, "iter0": it0}
+    return c
+
+
+def case_iter0(c):
+    it0 = (c.get("surface") or {}).get("iter0")
+    return c["iter0"] if it0 is None else it0
+
+
+def paint_surface(c, base, water, wall):
+    """The stretches of c["surface"] on the LAND columns of a terrain: type up the whole column, vegetation / soil moisture / snow in its wall cells."""
+    X = wall.shape[1]
+    for start, width, t, veg, soil, snow in (c.get("surface") or {}).get("stretches", []):
+        for x in (int(start * X) + np.arange(max(1, int(width * X)))) % X:
+            if wall[0, x, 0] != 1:
+                continue
+            rows = wall[:, x, 1] == 0
+            wall[:, x, 0] = t
+            wall[rows, x, 3] = veg
+            water[rows, x, 2] = soil
+            water[rows, x, 3] = snow
+
+
 def draw_case(rng, max_cells, big=False):
     c = {}
     kind = rng.choice(["tiny", "small", "small", "mid", "wide", "tall"])
@@ -133,6 +171,7 @@ def build_case(pkg, c):
         base, water, wall = S.terrain_grid(X, Y, seed=c["tseed"], height_mult=c["tmult"])
     else:
         base, water, wall = S.dry_grid(X, Y)
+    paint_surface(c, base, water, wall)
     air = wall[..., 1] != 0
     if c["sigma"] > 0:
         for ch in (0, 1):
@@ -211,8 +250,8 @@ def case_steps(pkg, E, wx_oracle, c):
         o.upload(base, water, wall, drops)
         h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"])
         o.set_params(u)
-        h.iter = c["iter0"]
-        o.iter = c["iter0"]
+        h.iter = case_iter0(c)
+        o.iter = case_iter0(c)
         h.set_option(h.OPT_DRY_PAIRS, c["pairs"])
         h.set_option(h.OPT_ROW_BANDS, c["bands"])
         h.set_option(h.OPT_KERNEL_SET, c["kernel_set"])
@@ -239,27 +278,27 @@ def case_steps(pkg, E, wx_oracle, c):
             o.step(n)
             yield
             if not c["dry"] and not np.array_equal(h.read_rect("CURL"), o.field("CURL"), equal_nan=True):
-                bad.append({"field": "CURL", "after_iterations": h.iter - c["iter0"]})
+                bad.append({"field": "CURL", "after_iterations": h.iter - case_iter0(c)})
             if c.get("subrect"):
                 x0, y0 = int(rng.integers(0, X)), int(rng.integers(0, Y))
                 w, hh = int(rng.integers(1, X - x0 + 1)), int(rng.integers(1, Y - y0 + 1))
                 for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR") + (() if c["dry"] else ("LIGHT_1", "BASE_DISP")):
                     a, b = h.read_rect(f, x0, y0, w, hh), o.field(f)[y0:y0 + hh, x0:x0 + w]
                     if not np.array_equal(a, b, equal_nan=True):
-                        bad.append({"field": f + " sub-rectangle", "rect": [x0, y0, w, hh], "after_iterations": h.iter - c["iter0"]})
+                        bad.append({"field": f + " sub-rectangle", "rect": [x0, y0, w, hh], "after_iterations": h.iter - case_iter0(c)})
             fields = list(GRID_FIELDS if not c["dry"] else ["BASE_CUR", "BASE_DISP", "WATER_CUR", "WATER_0", "WALL_CUR"])
             for f in fields:
                 a, b = h.read_rect(f), o.field(f)
                 if not np.array_equal(a, b, equal_nan=True):
                     ne = (a != b) & ~(np.isnan(a.astype(np.float64)) & np.isnan(b.astype(np.float64)))
                     ys, xs = np.nonzero(ne.any(axis=-1))
-                    bad.append({"field": f, "after_iterations": h.iter - c["iter0"], "values": int(ne.sum()), "first": [int(xs[0]), int(ys[0])],
+                    bad.append({"field": f, "after_iterations": h.iter - case_iter0(c), "values": int(ne.sum()), "first": [int(xs[0]), int(ys[0])],
                                 "max_abs": float(np.nanmax(np.abs(a.astype(np.float64) - b)))})
             if nd:
                 for f, a, b in (("DROPS", h.read_particles(), o.field("DROPS")), ("PRECIP_FB", h.read_rect("PRECIP_FB"), o.field("PRECIP_FB")),
                                 ("PRECIP_DEP", h.read_rect("PRECIP_DEP"), o.field("PRECIP_DEP")), ("LIGHTNING", h.read_rect("LIGHTNING"), o.field("LIGHTNING"))):
                     if not np.array_equal(a, b, equal_nan=True):
-                        bad.append({"field": f, "after_iterations": h.iter - c["iter0"], "values": int((a != b).sum())})
+                        bad.append({"field": f, "after_iterations": h.iter - case_iter0(c), "values": int((a != b).sum())})
             if bad:
                 break
         info = {"blown_up": not bool(np.isfinite(o.field("BASE_CUR")).all() and np.isfinite(o.field("WATER_CUR")).all() and np.abs(o.field("BASE_CUR")[..., :2]).max() < 1e4), "fastest": float(h.fastest_velocity()) if hasattr(h, "fastest_velocity") else None}
@@ -897,7 +936,7 @@ def main():
         print(json.dumps({"mode": a.mode, "seed": a.seed, "cases_run": ran, "mismatching_cases": n_bad, "seconds": round(time.time() - t0, 1)}))
         sys.exit(1 if n_bad else 0)
     for k in range(a.cases):
-        c = draw_more_sliders(draw_case(rng, a.max_cells, a.big))
+        c = draw_surface(draw_more_sliders(draw_case(rng, a.max_cells, a.big)))
         if a.mode == "group":
             c = draw_group(rng, c)
         if a.mode == "script":
