@@ -344,6 +344,8 @@ struct wx_sim {
   void *det_tmp = nullptr;
   size_t det_tmp_bytes = 0;
   WetLaunch wet_shape{};       // cached launch shape for run.air_from_row
+  int wet_shape_members = 1;   // ... made for a 1 / wet_shape_members share of the chip (a member of an ensemble launch; 1: the whole chip)
+  wx_ensemble *ens = nullptr;  // the ensemble that owns this handle (wx_ensemble_member): its stream is the ensemble's, no placement search
   // marching wet kernel: output cells fed by a back-trace longer than 0.9 cells, recomputed exactly by k_wet_fix (wx_wet.h)
   FixList fix;
   // the pair kernel's exact path (wx_march2.h, Dry2Fix): control words, the list of recorded cells, the host-visible length of the last list
@@ -908,11 +910,31 @@ template <class Launch> int split_iteration(wx_sim *s, int edge_mode, int nl, in
   return WX_OK;
 }
 
+// no brush input and no airplane event in the coming iterations (k_march_wet's QUIET instantiations)
+static bool march_wet_quiet(const wx_sim *s) { return !(s->uni.userInputType >= 1) && !(s->uni.airplaneValues[3] < 0.0f || s->uni.airplaneValues[3] > 0.9f); }
+
 // The whole iteration as ONE row-marching kernel (wx_wet.h). Reads base[0], wall[0], water[1], the light_0 planes and the source
 // light planes; writes the other buffer of each pair and swaps the pointers, so that afterwards the usual roles hold again
 // (base[0] / wall[0] = post-pressure state, water[1] = post-advection water, lp[0] / lp[1] = light_0 / light_1 as in the reference).
 // edge_mode: see split_iteration
-int iterate_march_wet(wx_sim *s, bool opt_out, bool precip, int edge_mode = 0)
+// In three parts, so that an ensemble (wx_ensemble_step) can prepare every member of a partition, launch ONCE and commit every member; a
+// lone handle runs the three in sequence (iterate_march_wet).
+#ifdef WX_WET_TIMING
+static unsigned long long *dbg_cycles = nullptr;
+#endif
+struct WetIter { // what march_wet_prepare hands to the launch: one iteration's arguments
+  WetIn in;
+  WetOut out;
+  bool opt_out, quiet;
+  float iter;
+};
+// host bookkeeping in front of the launch: the iteration's inputs / outputs, the display-side flags, the launch shape (for the whole chip,
+// or for this handle's share of it as one of `share_members` members of an ensemble launch), the exact-path list
+// PRECONDITION the ensemble driver relies on (wx_ensemble.h runs prepare + commit of up to 16 iterations AHEAD of their launches): whatever
+// this function enqueues on the stream -- light_to_planes, the terrain scan, the exact-path list's first zeroing -- it enqueues in the FIRST
+// iteration prepared after an upload / option change only, never per iteration, and march_wet_commit enqueues nothing. Work enqueued here
+// in a later iteration would run before the launches of the iterations in front of it.
+int march_wet_prepare(wx_sim *s, bool opt_out, bool precip, WetIter &wi, int share_members = 1)
 {
   const int src = s->run.even ? 0 : 1;
   light_to_planes(s);
@@ -939,7 +961,6 @@ int iterate_march_wet(wx_sim *s, bool opt_out, bool precip, int edge_mode = 0)
     s->w0.uni.iterI = (int)s->w0.uni.iterNum;
   }
 #ifdef WX_WET_TIMING
-  static unsigned long long *dbg_cycles = nullptr;
   if (!dbg_cycles && hipMalloc((void **)&dbg_cycles, 16 * 8192 * WMAXSEG) != hipSuccess) return fail(s, WX_E_NOMEM, "wx_step: timing buffer");
   out.cycles = dbg_cycles;
 #endif
@@ -956,25 +977,40 @@ int iterate_march_wet(wx_sim *s, bool opt_out, bool precip, int edge_mode = 0)
     s->run.air_from_row = v < s->Y ? v : s->Y;
     s->run.wet_shape_valid = false;
   }
-  if (!s->run.wet_shape_valid) {
-    s->wet_shape = wet_launch_shape(s->geo, s->run.air_from_row, s->opt.bands_mode);
+  if (!s->run.wet_shape_valid || s->wet_shape_members != share_members) {
+    s->wet_shape = share_members > 1 ? wet_launch_shape_member(s->geo, s->run.air_from_row, s->opt.bands_mode, share_members)
+                                     : wet_launch_shape(s->geo, s->run.air_from_row, s->opt.bands_mode);
+    s->wet_shape_members = share_members;
     s->run.wet_shape_valid = true;
     if (wx_tune_env("WX_MARCH_DEBUG")) fprintf(stderr, "[wx_wet] air_from_row=%d of %d\n", s->run.air_from_row, s->Y);
   }
-  const WetLaunch &shape = s->wet_shape;
   if (!s->fix.cells) { // (once per handle) room for a quarter of the grid's cells, at most 8 M entries
     size_t cap = std::min<size_t>(std::max<size_t>(ncell(s) / 4, 1u << 16), 1u << 23);
     if (s->opt.fix_cap_request > 0) cap = (size_t)s->opt.fix_cap_request; // (WX_OPT_FIX_CAP; tests: provoke the overflow report)
     // words: {entries, arrival ticket of the fix pass, what the hint word was last told, -}: the fix pass leaves the first two at 0
     if (!s->fix.create(s->stream, cap, 4, 2, true)) return fail(s, WX_E_NOMEM, "wx_step: %zu bytes for the exact-path cell list", cap * sizeof(int2));
   }
+  wi.in = in;
+  wi.out = out;
+  wi.opt_out = opt_out;
+  // no brush input, no airplane event (the common case: a running simulation): the instantiation without those sections
+  wi.quiet = march_wet_quiet(s);
+  wi.iter = (float)s->run.iter;
+  return WX_OK;
+}
+
+// the launch group(s) of a lone handle's iteration
+int march_wet_launch(wx_sim *s, const WetIter &wi, int edge_mode)
+{
+  const WetIn &in = wi.in;
+  const WetOut &out = wi.out;
+  const bool opt_out = wi.opt_out, quiet = wi.quiet;
+  const WetLaunch &shape = s->wet_shape;
   {
     ProfScope ps(s, K_MARCH_WET);
     const WetFixList fix = s->fix.wet(&s->state->fastest_bits);
-    // no brush input, no airplane event (the common case: a running simulation): the instantiation without those sections
-    const bool quiet = !(s->uni.userInputType >= 1) && !(s->uni.airplaneValues[3] < 0.0f || s->uni.airplaneValues[3] > 0.9f);
     const VxTrack vt = vx_track(s);
-    const float iter = (float)s->run.iter;
+    const float iter = wi.iter;
     // one launch group: marching kernel over a strip range (or two, both in ONE launch) -> the fix pass over what it recorded (leaves the
     // list empty). A wave records -- and the fix pass rewrites -- only output cells of its own strip: the groups of a split iteration never
     // write each other's columns, and the edge group (on its own stream, half-height segments: done before the interior) has its own list
@@ -1033,10 +1069,24 @@ int iterate_march_wet(wx_sim *s, bool opt_out, bool precip, int edge_mode = 0)
     }
   }
 #endif
+  return WX_OK;
+}
+
+// behind the launch: the ping-pong (afterwards the usual roles hold again, see above)
+void march_wet_commit(wx_sim *s)
+{
   std::swap(s->base[0], s->base[1]);
   std::swap(s->wall[0], s->wall[1]);
   std::swap(s->water[1], s->water[2]);
   if (!s->run.even) std::swap(s->lp[0], s->lp[2]);
+}
+
+int iterate_march_wet(wx_sim *s, bool opt_out, bool precip, int edge_mode = 0)
+{
+  WetIter wi;
+  if (int rc = march_wet_prepare(s, opt_out, precip, wi)) return rc;
+  if (int rc = march_wet_launch(s, wi, edge_mode)) return rc;
+  march_wet_commit(s);
   return WX_OK;
 }
 
@@ -1559,6 +1609,41 @@ int wx_set_params(wx_sim *s, const wx_params *p, const float *initial_T, const f
   return WX_OK;
 }
 
+// does a step with the handle's current options and pass mask run the marching wet kernel? (the full grid-pass set on the default kernel set)
+static bool step_runs_march_wet(const wx_sim *s) { return s->opt.fused && (s->p.pass_mask & 0x3Fu) == 0x3Fu; }
+
+// What a step settles before its first iteration -- wx_step_overlap, and wx_ensemble_step for the members it batches.
+static int step_begin(wx_sim *s, bool dry)
+{
+  settle_edges(s); // (the previous call ended with an edges-first iteration that no halo pack followed)
+  if (s->copy_in_flight) { // a streamed frame still reads the display fields: order this step after it (device-side wait)
+    HIPCHK(s, hipStreamWaitEvent(s->stream, s->ev_copy_done, 0));
+    s->copy_in_flight = false;
+  }
+  // the vegetation byte stays known non-negative only while nothing but the brush-free dry iteration touches the wall texture
+  if (!dry || s->p.userInputType >= 0 || s->p.airplaneValues[3] > 0.9f) s->run.wall_veg_ok = false;
+  // ... and the water texture stays known trivial only through water-free dry iterations (iterate_dry's `water == false` case)
+  // (local_water_free goes with it: it is what wx_slab_assert_water_free re-arms water_trivial from, and after a step that can create
+  // water only a new upload may establish it again -- ADVICE round 3)
+  if (!dry || s->p.userInputType >= 0 || s->p.airplaneValues[3] != 0.0f || s->p.soundingForcing != 0.0f) s->run.water_trivial = s->run.local_water_free = s->run.halo_base_only = false;
+  if (s->p.userInputType >= 10) s->run.air_from_row = -1; // wall tools: the terrain may grow (re-measured after the call)
+  return WX_OK;
+}
+static void step_begin_iterations(wx_sim *s, int n_iter)
+{
+  s->split.edges_recorded = false;
+  if (n_iter > 0) s->split.gate_passed = false;
+  if (n_iter > 0) s->run.water0_pending = false; // (the inputs of the previous step's last iteration are about to be overwritten)
+}
+// ... and what it leaves behind its last one
+static void step_end(wx_sim *s, int n_iter, bool dry)
+{
+  if (n_iter > 0) {
+    s->run.emit_lit = !dry && (s->p.pass_mask & WX_PASS_LIGHTING) != 0;
+    s->run.emit_uni = s->uni;
+  }
+}
+
 int wx_step(wx_sim *s, int n_iter) { return wx_step_overlap(s, n_iter, 0u); }
 
 int wx_step_overlap(wx_sim *s, int n_iter, unsigned flags)
@@ -1590,23 +1675,12 @@ int wx_step_overlap(wx_sim *s, int n_iter, unsigned flags)
       }
     }
   }
-  settle_edges(s); // (the previous call ended with an edges-first iteration that no halo pack followed)
   const unsigned mask = s->p.pass_mask;
   const bool precip = (mask & WX_PASS_PRECIPITATION) && s->p.enablePrecipitation && s->n_drops > 0;
   // the marching kernel implements the full grid-pass set; any other pass_mask (but the dry one) runs the per-pass kernels
-  const bool fused = s->opt.fused && (mask & 0x3Fu) == 0x3Fu;
+  const bool fused = step_runs_march_wet(s);
   const bool dry = s->opt.fused && (mask & 0x3Fu) == WX_PASS_DRY;
-  if (s->copy_in_flight) { // a streamed frame still reads the display fields: order this step after it (device-side wait)
-    HIPCHK(s, hipStreamWaitEvent(s->stream, s->ev_copy_done, 0));
-    s->copy_in_flight = false;
-  }
-  // the vegetation byte stays known non-negative only while nothing but the brush-free dry iteration touches the wall texture
-  if (!dry || s->p.userInputType >= 0 || s->p.airplaneValues[3] > 0.9f) s->run.wall_veg_ok = false;
-  // ... and the water texture stays known trivial only through water-free dry iterations (iterate_dry's `water == false` case)
-  // (local_water_free goes with it: it is what wx_slab_assert_water_free re-arms water_trivial from, and after a step that can create
-  // water only a new upload may establish it again -- ADVICE round 3)
-  if (!dry || s->p.userInputType >= 0 || s->p.airplaneValues[3] != 0.0f || s->p.soundingForcing != 0.0f) s->run.water_trivial = s->run.local_water_free = s->run.halo_base_only = false;
-  if (s->p.userInputType >= 10) s->run.air_from_row = -1; // wall tools: the terrain may grow (re-measured after the call)
+  if (int rc = step_begin(s, dry)) return rc;
   if (precip && s->pool.remote && s->opt.pool_exact && n_iter > 0 && (n_iter > 1 || s->pool.exact_pending > 0))
     return fail(s, WX_E_STATE, "wx_step: WX_OPT_POOL_EXACT takes one iteration per call, each followed by wx_pool_events_pack / all-gather / wx_pool_events_apply");
   if (precip && s->pool.remote && n_iter > 0) { // slab with particles: refuse an over-long call BEFORE any iteration runs
@@ -1629,9 +1703,7 @@ int wx_step_overlap(wx_sim *s, int n_iter, unsigned flags)
     wait_unpacked(s);
     light_to_rgba(s);
   }
-  s->split.edges_recorded = false;
-  if (n_iter > 0) s->split.gate_passed = false;
-  if (n_iter > 0) s->run.water0_pending = false; // (the inputs of the previous step's last iteration are about to be overwritten)
+  step_begin_iterations(s, n_iter);
   const int show_at = (flags & WX_OVERLAP_MORE_TO_COME) ? -1 : n_iter - 1; // the iteration that also stores the display-side fields
   for (int it = 0; it < n_iter; it++) {
     int edge_mode = 0;
@@ -1722,10 +1794,7 @@ int wx_step_overlap(wx_sim *s, int n_iter, unsigned flags)
     }
     s->run.iter++;
   }
-  if (n_iter > 0) {
-    s->run.emit_lit = !dry && (mask & WX_PASS_LIGHTING) != 0;
-    s->run.emit_uni = s->uni;
-  }
+  step_end(s, n_iter, dry);
   HIPCHK(s, hipGetLastError());
   return WX_OK;
 }
@@ -1969,6 +2038,7 @@ int wx_tune_placement(wx_sim *s, int tries, int iters_per_try, float *ms_before,
   if (!s) return WX_E_INVALID;
   DeviceScope dev_scope(s);
   if (tries < 1 || iters_per_try < 1) return fail(s, WX_E_INVALID, "wx_tune_placement: tries >= 1, iters_per_try >= 1");
+  if (s->ens) return fail(s, WX_E_STATE, "wx_tune_placement: the handle is a member of an ensemble (its iterations share their launches with the other members)");
   if (!s->uploaded || !s->have_params) return fail(s, WX_E_STATE, "wx_tune_placement before wx_upload / wx_set_params");
   if (s->pool.remote) return fail(s, WX_E_STATE, "wx_tune_placement: not on slab handles with particles (the exchange period would advance)");
   if (int rc = materialize_water0(s)) return rc; // (the probes' iterations overwrite the inputs it is made from)
@@ -2609,6 +2679,7 @@ int wx_stream_wait(wx_sim *s)
 int wx_set_stream(wx_sim *s, void *hip_stream)
 {
   if (!s) return WX_E_INVALID;
+  if (s->ens) return fail(s, WX_E_STATE, "wx_set_stream: the handle is a member of an ensemble and runs on the ensemble's stream");
   HIPCHK(s, hipStreamSynchronize(s->stream));
   s->stream = (hipStream_t)hip_stream;
   return WX_OK;
@@ -2617,6 +2688,7 @@ int wx_set_stream(wx_sim *s, void *hip_stream)
 int wx_set_comm_stream(wx_sim *s, void *hip_stream)
 {
   if (!s) return WX_E_INVALID;
+  if (s->ens) return fail(s, WX_E_STATE, "wx_set_comm_stream: the handle is a member of an ensemble (whole-domain members have no halo exchange)");
   DeviceScope dev_scope(s);
   HIPCHK(s, hipStreamSynchronize(s->stream));
   settle_edges(s);
@@ -2997,3 +3069,4 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 } // extern "C"
 
 #include "wx_comm.h" // (its entry points are declared extern "C" by include/wxsim.h)
+#include "wx_ensemble.h" // (likewise)

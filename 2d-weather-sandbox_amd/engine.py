@@ -41,6 +41,8 @@ EXPORTS = [
     "wx_group_count", "wx_group_transport", "wx_group_slab", "wx_group_agree", "wx_group_step", "wx_group_sync", "wx_group_set_option",
     "wx_group_exchange", "wx_slab_vx_take", "wx_slab_set_vx_bound", "wx_slab_cone", "wx_slab_period", "wx_pair_stats", "wx_placement_info", "wx_arith",
     "wx_diag_collect", "wx_diag_merge", "wx_diag_finish", "wx_diag_accumulate", "wx_diag_accumulate_cells", "wx_diagnostics", "wx_group_diagnostics",
+    "wx_ensemble_create", "wx_ensemble_destroy", "wx_ensemble_last_error", "wx_ensemble_count", "wx_ensemble_member", "wx_ensemble_step",
+    "wx_ensemble_sync", "wx_ensemble_diagnostics", "wx_ensemble_stats",
 ]
 
 
@@ -282,6 +284,18 @@ def lib() -> C.CDLL:
     L.wx_diag_accumulate_cells.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.wx_diagnostics.argtypes = [vp, vp]
     L.wx_group_diagnostics.argtypes = [vp, vp]
+    L.wx_ensemble_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.wx_ensemble_destroy.argtypes = [vp]
+    L.wx_ensemble_destroy.restype = None
+    L.wx_ensemble_last_error.argtypes = [vp]
+    L.wx_ensemble_last_error.restype = C.c_char_p
+    L.wx_ensemble_count.argtypes = [vp]
+    L.wx_ensemble_member.argtypes = [vp, i32]
+    L.wx_ensemble_member.restype = vp
+    L.wx_ensemble_step.argtypes = [vp, i32]
+    L.wx_ensemble_sync.argtypes = [vp]
+    L.wx_ensemble_diagnostics.argtypes = [vp, vp]
+    L.wx_ensemble_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -785,6 +799,65 @@ class Group:
                 h._h = None
             lib().wx_group_destroy(self._g)
             self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Ensemble:
+    """B independent whole-domain simulations of one size (wx_ensemble_*): ``members`` are borrowed ``Handle``s -- upload, set_params,
+    set_option, read_rect ... exactly as on any handle --, ``step`` advances all of them in one marching launch per iteration."""
+
+    def __init__(self, n_members: int, X: int, Y: int):
+        L = lib()
+        e = C.c_void_p()
+        _apply_env_defaults()
+        rc = L.wx_ensemble_create(int(n_members), int(X), int(Y), C.byref(e))
+        if rc != 0:
+            raise WxError(rc, (L.wx_ensemble_last_error(None) or b"").decode())
+        self._e = e
+        self.n, self.X, self.Y = L.wx_ensemble_count(e), X, Y
+        self.members = [Handle._borrowed(L.wx_ensemble_member(e, i), X, Y, 0, self, 0) for i in range(self.n)]
+
+    def _chk(self, rc: int):
+        if rc != 0:
+            raise WxError(rc, (lib().wx_ensemble_last_error(self._e) or b"").decode())
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i: int) -> Handle:
+        return self.members[i]
+
+    def step(self, n: int = 1):
+        self._chk(lib().wx_ensemble_step(self._e, int(n)))
+        for h in self.members:
+            h._stepped = True
+
+    def sync(self):
+        self._chk(lib().wx_ensemble_sync(self._e))
+
+    def diagnostics(self) -> list:
+        """wx_ensemble_diagnostics: one dict per member (what ``Handle.diagnostics`` returns for it)."""
+        d = (WxDiag * self.n)()
+        self._chk(lib().wx_ensemble_diagnostics(self._e, d))
+        return [_diag_dict(d[i]) for i in range(self.n)]
+
+    def stats(self) -> dict:
+        """wx_ensemble_stats: member-iterations that shared a launch / ran their own path, and marching launches issued, so far."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(lib().wx_ensemble_stats(self._e, C.byref(a), C.byref(b), C.byref(c)))
+        return {"member_iters_batched": a.value, "member_iters_solo": b.value, "march_launches": c.value}
+
+    def close(self):
+        if getattr(self, "_e", None):
+            for h in self.members:
+                h._h = None
+            lib().wx_ensemble_destroy(self._e)
+            self._e = None
 
     def __del__(self):
         try:

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import datetime as _dt
 import sys
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Sequence
 
 import numpy as np
 
@@ -51,13 +51,15 @@ def advance_sim_datetime(t: _dt.datetime, delta_hours: float):
 
 class WeatherSim:
     def __init__(self, X: int, Y: int, base, water, wall, droplets=None, settings: Optional[Dict[str, Any]] = None, *,
-                 sun_angle_deg: Optional[float] = None, quad_scale: int = 0, pass_mask: int = params.PASS_ALL, columns=None):
+                 sun_angle_deg: Optional[float] = None, quad_scale: int = 0, pass_mask: int = params.PASS_ALL, columns=None,
+                 handle: Optional[Handle] = None):
         """``mainScript``: take the four initial arrays + saved settings (app.js:1495, 3375-3399, 5189-5317), or -- for a
-        new simulation -- the 1-D setup descriptors ``columns`` (synth.terrain_columns) that the device expands."""
+        new simulation -- the 1-D setup descriptors ``columns`` (synth.terrain_columns) that the device expands.
+        ``handle``: an engine handle somebody else owns (a member of a ``WeatherEnsemble``) instead of a new one."""
         self.X, self.Y = int(X), int(Y)
         self.gui = params.merge_settings(settings)
         n_drops = 0 if droplets is None else int(np.asarray(droplets).size // 5)
-        self._h = Handle(self.X, self.Y, n_drops)
+        self._h = handle if handle is not None else Handle(self.X, self.Y, n_drops)
         if columns is not None:
             self._h.setup_columns(columns, droplets)
         else:
@@ -208,3 +210,71 @@ class WeatherSim:
     @property
     def handle(self) -> Handle:
         return self._h
+
+
+class WeatherEnsemble:
+    """B ``WeatherSim`` members of one size on one ``engine.Ensemble``: one scene (arrays, a save file or a synthetic terrain) plus
+    per-member setting overrides -- a sweep over the sliders, a perturbed ensemble. Every member is a full ``WeatherSim`` (``set_gui``,
+    ``set_brush``, ``read_rect`` ...); ``step`` advances all of them in one marching launch per iteration. No droplets."""
+
+    def __init__(self, n_members: int, X: int, Y: int, base, water, wall, settings: Optional[Dict[str, Any]] = None,
+                 overrides: Optional[Sequence[Optional[Dict[str, Any]]]] = None, *, perturb=None, columns=None, **kw):
+        """``overrides[i]``: guiControls entries of member i on top of ``settings``; ``perturb(i, base, water, wall)`` may return member
+        i's own copies of the arrays."""
+        from .engine import Ensemble
+        if overrides is not None and len(overrides) != n_members:
+            raise ValueError("one overrides entry per member")
+        self._e = Ensemble(n_members, X, Y)
+        self.members = []
+        for i in range(n_members):
+            st = dict(settings or {})
+            st.update((overrides[i] if overrides is not None else None) or {})
+            b, w, wl = (base, water, wall) if perturb is None or columns is not None else perturb(i, base, water, wall)
+            m = WeatherSim(X, Y, b, w, wl, None, st, columns=columns, handle=self._e[i], **kw)
+            m.verbose = False
+            m._placement_told = True  # (members never search for a placement)
+            self.members.append(m)
+
+    @classmethod
+    def from_save(cls, n_members: int, sf: "codec.SaveFile | str", overrides=None, **kw) -> "WeatherEnsemble":
+        if isinstance(sf, str):
+            sf = codec.load(sf)
+        return cls(n_members, sf.X, sf.Y, sf.base, sf.water, sf.wall, sf.settings, overrides, **kw)
+
+    @classmethod
+    def new_simulation(cls, n_members: int, X: int, Y: int, settings: Optional[Dict[str, Any]] = None, overrides=None, *, seed: float = 0.5,
+                       height_mult: float = 0.3, **kw) -> "WeatherEnsemble":
+        from . import synth
+        cols = synth.terrain_columns(X, Y, params.merge_settings(settings), seed=seed, height_mult=height_mult)
+        return cls(n_members, X, Y, None, None, None, settings, overrides, columns=cols, **kw)
+
+    def __len__(self):
+        return len(self.members)
+
+    def __getitem__(self, i: int) -> WeatherSim:
+        return self.members[i]
+
+    def step(self, n_iter: Optional[int] = None):
+        """One frame for every member: the members' own sun updates, then n iterations of all of them together (``IterPerFrame`` of
+        member 0 by default)."""
+        n = int(self.members[0].gui["IterPerFrame"]) if n_iter is None else int(n_iter)
+        for m in self.members:
+            if m.gui.get("dayNightCycle") and m._manual_sun is None:
+                m.update_sunlight(TIME_PER_ITERATION * n)
+        self._e.step(n)
+
+    def sync(self):
+        self._e.sync()
+
+    def diagnostics(self) -> list:
+        return self._e.diagnostics()
+
+    def stats(self) -> dict:
+        return self._e.stats()
+
+    @property
+    def engine(self):
+        return self._e
+
+    def close(self):
+        self._e.close()

@@ -1,0 +1,139 @@
+#!/usr/bin/env python3
+"""Times an ensemble (wx_ensemble_step) against what a host does without one: B handles from wx_create stepped round-robin in frames
+of 10 iterations in one process. Prints ONE JSON line.
+
+    python tools/ensemble_bench.py --mode ensemble                        # this checkout's ensemble, the three shapes
+    python tools/ensemble_bench.py --mode handles --root ../parent        # the baseline, run from a checkout of the parent commit
+    python tools/ensemble_bench.py --mode ensemble --shapes 100x100x1,100x100x8,100x100x64     # how the time grows with B
+
+Shapes are XxYxB. 100 x 100 runs the reference's own save (tests/golden/save100raw.npz), the other sizes the setup-pass terrain; every
+member gets a moving fluid of its own (devtools.seed_flow, seed = member index) -- as bench.py seeds its `configs`. Before every timed
+region the chip is conditioned with untimed frames for a quarter of a second (bench.py: condition_clocks); a region is at least
+--steps iterations of every member; --repeats regions are timed and all of them reported (compare the SLOWEST of each side).
+The roofline fraction is 104 B / cell-step against bench.py's HBM_PEAK_GBS = 8000 GB/s (--peak-gbs).
+--share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["ensemble", "handles"], default="ensemble")
+    ap.add_argument("--root", default=ROOT, help="checkout to load the package and the library from (the parent commit for the baseline)")
+    ap.add_argument("--shapes", default="100x100x64,2500x300x8,16000x500x2")
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--frame", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--flow", type=float, default=0.2)
+    ap.add_argument("--peak-gbs", type=float, default=8000.0, help="what the roofline fraction is quoted against [GB/s]: bench.py's HBM_PEAK_GBS")
+    ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
+                    "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
+    return ap.parse_args()
+
+
+def make_members(pkg, X, Y, B, make, flow=0.2):
+    """`make(i)` -> a handle of X x Y; uploads the scene, sets the parameters, seeds member i's own flow."""
+    import numpy as np
+    from weather_sandbox_amd import devtools
+    P = pkg.params
+    hs = []
+    if (X, Y) == (100, 100):
+        g = np.load(os.path.join(ROOT, "tests", "golden", "save100raw.npz"))
+        u = json.loads(str(g["uniforms_json"]))
+        u["initial_T"] = g["initial_T"]
+        for k in ("userInputValues", "userInputMove", "airplaneValues"):
+            u[k] = tuple(u[k])
+        u = dict(u, quad_scale=0, enablePrecipitation=0)
+    else:
+        gui = P.merge_settings(None)
+        gui["sunAngle"] = 50.0
+        u = P.uniforms_from_gui(gui, Y, quad_scale=0)
+        u["enablePrecipitation"] = 0
+        cols = pkg.synth.terrain_columns(X, Y)
+    for i in range(B):
+        h = make(i)
+        if (X, Y) == (100, 100):
+            h.upload(g["in_base"], g["in_water"], g["in_wall"])
+        else:
+            h.setup_columns(cols)
+        h.set_params(P.fill_struct(P.WxParams(), u), u["initial_T"])
+        devtools.seed_flow(h, flow, seed=1 + i)
+        hs.append(h)
+    return hs
+
+
+def main():
+    a = parse()
+    sys.path.insert(0, a.root)
+    if a.share > 0:
+        if "debug" not in os.environ.get("WXSIM_LIB", ""):
+            sys.exit("--share needs WXSIM_LIB to name the debug build (the shipped library reads no environment variable)")
+        os.environ["WX_ENS_SHARE"] = str(a.share)
+    import torch
+    import wxpkg
+    pkg = wxpkg.load_package()
+    E = pkg.engine
+    E.lib().wx_set_option(None, E.Handle.OPT_PLACEMENT_SEARCH, 0)
+    torch.cuda.set_device(0)
+    out = {"tool": "ensemble_bench", "mode": a.mode, "root": os.path.relpath(a.root, ROOT), "frame": a.frame, "steps": a.steps, "share": a.share, "shapes": {}}
+    for spec in a.shapes.split(","):
+        X, Y, B = (int(v) for v in spec.split("x"))
+        if a.mode == "ensemble":
+            ens = E.Ensemble(B, X, Y)
+            make_members(pkg, X, Y, B, lambda i: ens[i], a.flow)
+            step, sync, close = ens.step, ens.sync, ens.close
+        else:
+            hs = make_members(pkg, X, Y, B, lambda i: E.Handle(X, Y, 0), a.flow)
+
+            def step(n):
+                for h in hs:
+                    h.step(n)
+
+            def sync():
+                for h in hs:
+                    h.sync()
+
+            def close():
+                for h in hs:
+                    h.close()
+
+        def frames(n):
+            done = 0
+            while done < n:
+                k = min(a.frame, n - done)
+                step(k)
+                done += k
+
+        times = []
+        for _ in range(a.repeats):
+            sync()
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < 0.25:  # clock conditioning: a quarter of a second of the same load, untimed
+                frames(a.frame)
+                sync()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            frames(a.steps)
+            sync()
+            torch.cuda.synchronize()
+            times.append(time.perf_counter() - t0)
+        per_iter = [t / a.steps for t in times]  # one iteration of ALL members
+        worst = max(per_iter)
+        rec = {"members": B, "us_per_iteration_of_all_members": [round(1e6 * t, 2) for t in per_iter],
+               "slowest_us": round(1e6 * worst, 2), "slowest_us_per_member_iteration": round(1e6 * worst / B, 3),
+               "mcell_steps_per_s_slowest": round(X * Y * B / worst / 1e6, 1),
+               "roofline_fraction_slowest": round(X * Y * B * 104 / worst / (a.peak_gbs * 1e9), 4)}
+        if a.mode == "ensemble":
+            rec["stats"] = ens.stats()
+        out["shapes"][spec] = rec
+        close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
