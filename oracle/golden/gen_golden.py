@@ -96,7 +96,8 @@ def js_uniforms(u: dict) -> dict:
 
 def run_fixture(name, X, Y, base, water, wall, drops, u, *, niter, dump_iters, perpass_iter=None, precip=False,
                 iter0=0, keep=("base_cur", "water_cur", "wall_cur", "light_0", "light_1", "water_0", "base_disp"), points=False,
-                dump_emitted=False, keep_particles=("drops", "lightning", "precip_fb", "precip_dep"), timeout=600.0, keep_perpass=None):
+                dump_emitted=False, keep_particles=("drops", "lightning", "precip_fb", "precip_dep"), timeout=600.0, keep_perpass=None,
+                uniform_changes=None, store_inputs=True):
     tmp = tempfile.mkdtemp(prefix="wxgold_")
     np.ascontiguousarray(base, np.float32).tofile(os.path.join(tmp, "base.f32"))
     np.ascontiguousarray(water, np.float32).tofile(os.path.join(tmp, "water.f32"))
@@ -110,6 +111,8 @@ def run_fixture(name, X, Y, base, water, wall, drops, u, *, niter, dump_iters, p
         "niter": niter, "dump_iters": list(dump_iters), "precip": bool(precip), "iter0": iter0, "points": bool(points),
         "dump_emitted": bool(dump_emitted),
     }
+    if uniform_changes:  # {iteration of the run: {uniform: value}} (harness.js): absent from every older fixture's job
+        job["uniform_changes"] = {str(k): js_uniforms(v) for k, v in uniform_changes.items()}
     if "sounding_T" in u:
         job["sounding"] = {k: [float(v) for v in u["sounding_" + k]] for k in ("T", "W", "Vel")}
     if perpass_iter is not None:
@@ -131,6 +134,11 @@ def run_fixture(name, X, Y, base, water, wall, drops, u, *, niter, dump_iters, p
         "renderer": res["renderer"], "its_per_s": 1000.0 * (res["niter"] - 1) / max(res["ms_after_first"], 1e-9),
         "points": int(bool(points)),  # 1: every pass drawn as one GL_POINT per pixel (see harness.js), 0: as the reference's quad
     }
+    if uniform_changes:
+        out["uniform_changes_json"] = json.dumps({str(k): js_uniforms(v) for k, v in uniform_changes.items()})
+    if not store_inputs:  # (a family of runs on one scene keeps the scene once: see fx_tools64)
+        for k in ("in_base", "in_water", "in_wall", "varyings"):
+            del out[k]
     if n_drops:
         out["in_drops"] = np.asarray(drops, np.float32).reshape(n_drops, 5)
     shapes = {"curl": (Y, X), "vort": (Y, X, 2), "precip_dep": (Y, X, 2), "drops": (-1, 5), "precip_drops": (-1, 5), "lightning": (4,)}
@@ -855,6 +863,179 @@ def fx_surface112_industry():
                        keep=("base_cur", "water_cur", "wall_cur"), points=True, keep_perpass=("boundary_base", "boundary_water", "boundary_wall"))
 
 
+# ------------------------------------------------------------------------------------------------
+# tools64 / crash64: the wall-editing tools (advectionShader.frag:291-400) and the airplane crash (:444-457) over EVERY surface type,
+# held and then RELEASED in one run (harness.js `uniform_changes`), with 20 iterations after the release. Drawn as GL_POINTS: a
+# circular edit is not quad aligned. tests/test_oracle_tools.py asserts from these dumps alone that every edit happened where the
+# shader says and nowhere else.
+# ------------------------------------------------------------------------------------------------
+TOOLS64_X = TOOLS64_Y = 64
+TOOLS64_ITER0 = 990   # the held iterations are 990 ..; 1000 (fire spread: 10 is a multiple of the divisor 10 of soil moisture 5) falls inside the 20 after release
+CRASH64_ITER0 = 997
+TOOLS64_AFTER = 20
+WALL_TOOLS = (10, 11, 12, 13, 14, 15, 16, 20, 21, 22)
+# |intensity| per tool: the wall-type tools read its sign only; soil moisture moves by 10 x, snow by 0.5 x
+TOOLS64_INTENSITY = {20: 0.7, 21: 3.0}
+TOOLS64_VEG = (60, 0, 127, 1, 126)  # by x % 5: co-prime with the stretches' 4 and the period 28, so every type meets every value
+# (centre x, centre y, radius) in cells, by held iterations. Held 1: over the first period of the terrain, the surface row well
+# inside. Held 3: over the second period and centred BELOW the surface, so that towards its rim it removes buried cells and leaves
+# the surface cell above them. tools64_discs() moves them by 1e-3 cells until no cell centre lies within 1e-5 (relative) of the rim.
+TOOLS64_DISCS = {1: (14.31, 5.23, 14.6), 3: (42.27, 1.37, 14.9)}
+TOOLS64_EXTRA = (("wholewidth", 10, -1, 1), ("wholewidth", 21, +1, 1), ("nowrap", 12, +1, 1), ("nowrap", 13, +1, 1), ("nowrap", 10, -1, 1))
+TOOLS64_NOWRAP_DISC = (1.83, 4.61, 9.7)  # cut by x = 0; with the wrap on it would reach columns 56 .. 63 as well
+TOOLS64_BAND = (2.07, 2.2)  # whole-width mode: centre row (cells) and half-width: rows 0 .. 3 (|dy| < 2.2)
+RIM_MARGIN = 1e-5
+
+
+def tools64_terrain():
+    """Every surface type as a stretch of four columns, twice (columns 0 .. 27 and 28 .. 55: inert, land, sea, fire, urban, runway,
+    industrial), then eight flat land columns. Four wall rows (three buried cells under every surface cell); the third column of a
+    stretch is one row HIGHER in the first period, the third and fourth one row LOWER in the second (two columns: a pit ONE cell wide
+    whose floor a tool turns into land blows up within three iterations, in the reference as in the oracle -- the air cell in it takes
+    the whole soil moisture at once -- and a state with NaN is the blow-up tests' business, not this family's). Two floating blocks (rows 8 .. 9 over columns
+    5 .. 6 and 45 .. 46): cells with air below them. Vegetation 60 / 0 / 127 / 1 / 126 by x % 5, soil moisture 5 / 30 / 80 by x % 3
+    and snow 6 / 1 on two residues of x % 7 -- except on the first land stretch and the last eight columns, which keep soil moisture
+    5 without snow (fire divisor 10: what is lit there spreads at iterNum 1000) and, the last eight, vegetation 60."""
+    rng = np.random.default_rng(8201)
+    X, Y = TOOLS64_X, TOOLS64_Y
+    x = np.arange(X)
+    types = np.where(x < 56, (x % 28) // 4, 1)
+    height = np.full(X, 4)
+    height[(x < 28) & (x % 4 == 2)] = 5
+    height[(x >= 28) & (x < 56) & (x % 4 >= 2)] = 3
+    veg = np.array(TOOLS64_VEG)[x % 5]
+    soil = np.array((5.0, 30.0, 80.0))[x % 3]
+    snow = np.where(x % 7 == 0, 6.0, np.where(x % 7 == 3, 1.0, 0.0))
+    plain = ((x >= 4) & (x < 8)) | (x >= 56)
+    soil[plain], snow[plain] = 5.0, 0.0
+    veg[x >= 56] = 60
+    gui, u, base, water, wall = surface_terrain(X, Y, rng, height, types, veg, soil, snow, wind=0.005)
+    for cols in ((5, 6), (45, 46)):
+        for xx in cols:
+            wall[8:10, xx, 1] = 0
+            wall[8:10, xx, 2] = (-1, 0)
+            wall[8:10, xx, 3] = 60
+            wall[10:, xx, 1] = np.minimum(np.arange(1, Y - 9), 127)
+            wall[10:, xx, 2] = np.minimum(np.arange(1, Y - 9), 127)
+            base[8:10, xx] = (0.0, 0.0, 0.0, 1000.0)
+            water[8:10, xx] = (1001.0, 0.0, 5.0, 0.0)
+    return gui, u, base, water, wall
+
+
+def disc_distance(varyings, cx, cy, wrap):
+    """advectionShader.frag:241-249 in float32 on the stored texCoords (square grid: the aspect factor is 1)."""
+    f = np.float32
+    tcx, tcy = varyings[..., 2].astype(f), varyings[..., 3].astype(f)
+    a = f(cx)
+    dx = np.abs(a - tcx)
+    if wrap:  # absHorizontalDist (common.glsl:268-271)
+        dx = np.minimum(np.minimum(dx, np.abs(f(1.0) + a - tcx)), f(1.0) - a + tcx)
+    dy = f(cy) - tcy
+    return np.sqrt(dx * dx + dy * dy, dtype=f)
+
+
+def rim_clear(varyings, values, wrap):
+    """No cell within RIM_MARGIN (relative) of the rim: `length()` / `sqrt` may round either way there."""
+    r = np.float32(values[3]) * np.float32(1.0 / varyings.shape[0])
+    if values[0] < -0.5:
+        d = np.abs(np.float32(values[1]) - varyings[..., 3].astype(np.float32))
+    else:
+        d = disc_distance(varyings, values[0], values[1], wrap)
+    return bool((np.abs(d.astype(np.float64) - float(r)) > RIM_MARGIN * float(r)).all())
+
+
+def tools64_values(varyings, disc, inten, wrap=True):
+    """userInputValues of a disc given in cells, nudged until the rim is clear."""
+    cx, cy, r = disc
+    for k in range(200):
+        v = ((cx + 1e-3 * k) / TOOLS64_X, (cy + 1e-3 * k) / TOOLS64_Y, inten, r)
+        if rim_clear(varyings, v, wrap):
+            return tuple(float(np.float32(c)) for c in v)
+    raise RuntimeError("no clear rim")
+
+
+def _tools64_run(name, scene, u, varyings, tool, values, held, wrap=True, fields_at=None):
+    gui, _, base, water, wall = scene
+    assert rim_clear(varyings, values, wrap)
+    uu = dict(u, userInputType=tool, userInputValues=values, userInputMove=(0.0, 0.0), wrapHorizontally=int(wrap))
+    n = held + TOOLS64_AFTER
+    its = sorted({held, held + 1, n})
+    out = run_fixture(name, TOOLS64_X, TOOLS64_Y, base, water, wall, None, uu, niter=n, dump_iters=its, precip=False, iter0=TOOLS64_ITER0,
+                      keep=("base_cur", "water_cur", "wall_cur"), points=True, uniform_changes={held: {"userInputType": -1}}, store_inputs=False)
+    _trim(name, out, fields_at if fields_at is not None else ((held, n) if held == 1 else (n,)), its)
+    return out
+
+
+def _tools64_scene():
+    scene = tools64_terrain()
+    probe = run_harness({"X": TOOLS64_X, "Y": TOOLS64_Y, "probe": True, "n_drops": 0, "points": True})
+    varyings = _dec(probe["probe"], np.float32).reshape(TOOLS64_Y, TOOLS64_X, 4)
+    return scene, scene[1], varyings
+
+
+def fx_tools64_in():
+    """The scene of the tools64 / crash64 family, once: inputs, varyings, settings."""
+    scene, u, varyings = _tools64_scene()
+    path = os.path.join(OUT_DIR, "tools64_in.npz")
+    np.savez_compressed(path, X=TOOLS64_X, Y=TOOLS64_Y, in_base=scene[2], in_water=scene[3], in_wall=scene[4], varyings=varyings,
+                        initial_T=np.asarray(u["initial_T"], np.float32), uniforms_json=json.dumps(js_uniforms(u)), points=1)
+    print(f"[tools64_in] wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
+def fx_tools64_quiet():
+    """No tool at all: what the edited runs are compared WITH by the non-vacuity test (the tool acts on the wall texture the boundary
+    pass of the same iteration wrote, which is this run's)."""
+    scene, u, varyings = _tools64_scene()
+    for wrap, name in ((True, "tools64_quiet"), (False, "tools64_quiet_nowrap")):
+        out = run_fixture(name, TOOLS64_X, TOOLS64_Y, scene[2], scene[3], scene[4], None, dict(u, wrapHorizontally=int(wrap)), niter=3, dump_iters=[1, 3],
+                          precip=False, iter0=TOOLS64_ITER0, keep=("base_cur", "water_cur", "wall_cur"), points=True, store_inputs=False)
+        _trim(name, out, (1,), [1, 3])
+
+
+def tools64_name(tool, sign, held, mode="disc"):
+    return f"tools64_{'' if mode == 'disc' else mode + '_'}t{tool}{'p' if sign > 0 else 'n'}_h{held}"
+
+
+def fx_tools64(tool, sign, held, mode="disc"):
+    scene, u, varyings = _tools64_scene()
+    inten = sign * TOOLS64_INTENSITY.get(tool, 0.01)
+    if mode == "wholewidth":
+        values = tools64_values(varyings, (-TOOLS64_X, TOOLS64_BAND[0], TOOLS64_BAND[1]), inten)
+        values = (-1.0,) + values[1:]
+        assert rim_clear(varyings, values, True)
+    elif mode == "nowrap":
+        values = tools64_values(varyings, TOOLS64_NOWRAP_DISC, inten, wrap=False)
+    else:
+        values = tools64_values(varyings, TOOLS64_DISCS[held], inten)
+    return _tools64_run(tools64_name(tool, sign, held, mode), scene, u, varyings, tool, values, held, wrap=mode != "nowrap")
+
+
+# (name, column, row) of the crash's centre cell: its 3 x 3 cells lie within 1.5 cells. Surface land (the flat stretch at the end),
+# land with nothing but buried cells in reach, every other surface type, open air.
+CRASH64_CASES = (("land", 59, 3), ("buried", 61, 1), ("inert", 1, 3), ("sea", 9, 3), ("fire", 13, 3), ("urban", 17, 3), ("runway", 21, 3),
+                 ("industrial", 25, 3), ("air", 40, 30), ("stepped_land", 33, 3))
+
+
+def fx_crash64(case):
+    """airplaneValues[3] = 1 for ONE iteration (iterNum 997), then released; 23 iterations in all, across 1000."""
+    scene, u, varyings = _tools64_scene()
+    if case == "quiet":  # no plane: what the crashed runs' first iteration is compared with
+        out = run_fixture("crash64_quiet", TOOLS64_X, TOOLS64_Y, scene[2], scene[3], scene[4], None, dict(u, userInputType=-1), niter=1, dump_iters=[1],
+                          precip=False, iter0=CRASH64_ITER0, keep=("base_cur", "water_cur", "wall_cur"), points=True, store_inputs=False)
+        return _trim("crash64_quiet", out, (1,), [1])
+    name, cx, cy = next(c for c in CRASH64_CASES if c[0] == case)
+    av = ((cx + 0.5) / TOOLS64_X, (cy + 0.5) / TOOLS64_Y, 0.0, 1.0)
+    uu = dict(u, userInputType=-1, airplaneValues=av)
+    its = [1, 2, 23]
+    out = run_fixture("crash64_" + name, TOOLS64_X, TOOLS64_Y, scene[2], scene[3], scene[4], None, uu, niter=23, dump_iters=its, precip=False,
+                      iter0=CRASH64_ITER0, keep=("base_cur", "water_cur", "wall_cur"), points=True,
+                      uniform_changes={1: {"airplaneValues": (0.0, 0.0, 0.0, 0.0)}}, store_inputs=False)
+    _trim("crash64_" + name, out, (1,) if name not in ("land", "air") else (1, 23), its)
+
+
+TOOLS64_RUNS = [(t, s, h, "disc") for t in WALL_TOOLS for s in (+1, -1) for h in (1, 3)] + [(t, s, h, m) for m, t, s, h in TOOLS64_EXTRA]
+
+
 FIXTURES = {
     "randwalls64": fx_randwalls64,
     "brush64": fx_brush64,
@@ -876,6 +1057,11 @@ FIXTURES = {
     "surface64_fire": fx_surface64_fire,
     "surface64_spread": fx_surface64_spread,
     "surface112_industry": fx_surface112_industry,
+    "tools64_in": fx_tools64_in,
+    "tools64_quiet": fx_tools64_quiet,
+    **{tools64_name(t, s, h, m): (lambda t=t, s=s, h=h, m=m: fx_tools64(t, s, h, m)) for t, s, h, m in TOOLS64_RUNS},
+    **{"crash64_" + c[0]: (lambda c=c: fx_crash64(c[0])) for c in CRASH64_CASES},
+    "crash64_quiet": lambda: fx_crash64("quiet"),
 }
 
 if __name__ == "__main__":

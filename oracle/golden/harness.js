@@ -307,10 +307,12 @@ function run(o)
       sndW[ys] = o.sounding.W[ys];
       sndV[ys] = o.sounding.Vel[ys];
     }
-  function setU(prog, list)
+  var uniformSites = {}; // name -> [[program, type], ...]: where job option `uniform_changes` finds a uniform again
+  function setU(prog, list, again)
   {
     gl.useProgram(P[prog]);
     list.forEach(function(e) {
+      if (!again) (uniformSites[e[0]] = uniformSites[e[0]] || []).push([prog, e[1]]);
       var loc = gl.getUniformLocation(P[prog], e[0]);
       if (loc === null) return;
       var v = e[2];
@@ -568,9 +570,22 @@ function run(o)
 
   var dumpAt = {};
   (o.dump_iters || []).forEach(function(i) { dumpAt[i] = true; });
+  // ---- job option `uniform_changes` (absent by default): {iteration: {name: value}} replaces uniforms BEFORE that iteration of
+  // the run (0-based, counted from the run's start, not iterNum), in every program that declares them: a brush held for k iterations
+  // and then released is ONE run -- the light textures are no input, so two chained runs would not be the same thing ----
+  function applyUniformChanges(it)
+  {
+    var ch = (o.uniform_changes || {})[String(it)];
+    if (!ch) return;
+    Object.keys(ch).forEach(function(name) {
+      if (!uniformSites[name]) throw new Error('uniform_changes: no uniform named ' + name);
+      uniformSites[name].forEach(function(s) { setU(s[0], [[name, s[1], ch[name]]], true); });
+    });
+  }
   var t0 = 0, t1 = 0;
   for (var it = 0; it < o.niter; it++) {
     if (it == 1) { gl.finish(); t0 = performance.now(); }
+    applyUniformChanges(it);
     var pp = null;
     if (o.perpass_iter === it) pp = out.perpass;
     if (typeof o.mark == 'function') o.mark('iteration', it, gl); // (run_harness_mock.js: cuts the recorded GL calls into iterations)

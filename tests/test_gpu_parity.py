@@ -135,12 +135,31 @@ def test_vs_reference_off_default_settings(pkg, golden, E, fused, name):
     assert len(out) >= 9 and S.check_against_reference(out, g, u) == []
 
 
-@pytest.mark.parametrize("name", ["surface112_industry", "surface64_fire", "surface64_growth", "surface64_growth10k", "surface64_spread"])
+def _tool_fixtures():
+    import test_oracle_tools as T
+    return T.TOOL_RUNS + T.CRASH_RUNS + ["tools64_quiet", "tools64_quiet_nowrap", "crash64_quiet"]
+
+
+@pytest.mark.parametrize("name", ["surface112_industry", "surface64_fire", "surface64_growth", "surface64_growth10k", "surface64_spread"] + _tool_fixtures())
 def test_vs_reference_surface_scenes(pkg, golden, E, fused, name):
     """HIP (quad_scale = 1) straight against the reference's own output on the surface fixtures (tests/test_oracle_surface.py): growth by
     rate and interval, fire spread over four smoothing iterations, burn-down, rain, the chimneys, dust, the sea's reset -- so that a
     misreading in csrc/wx_cells.h ALONE cannot hide behind the oracle. Walls bit for bit at every dump, fields within the bounds
-    stated there for the oracle."""
+    stated there for the oracle. The tools64 / crash64 fixtures (tests/test_oracle_tools.py): every wall tool with both signs over every
+    surface type and the airplane crash, held, released inside the run and followed for 20 iterations, with that file's bounds."""
+    if name.startswith(("tools64", "crash64")):
+        import test_oracle_tools as T
+        g, u, changes = T.load_run(name)
+        s = T.scene()
+        h = E.Handle(int(s["X"]), int(s["Y"]), 0)
+        h.upload(s["in_base"], s["in_water"], s["in_wall"])
+        h.iter = int(g["iter0"])
+        out = T.play(g, u, changes, lambda uu: h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), dict(uu, quad_scale=1)), uu["initial_T"]), h.step,
+                     lambda: tuple(h.read_rect(f) for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR")))
+        assert h.iter == int(g["iter0"]) + max(out)
+        h.close()
+        assert T.check_fields(out, g) == []
+        return
     import test_oracle_surface as S
     g, u = golden(name)
     u = dict(u, quad_scale=1)
@@ -1617,6 +1636,15 @@ def test_brush_and_airplane_inputs_bit_exact(pkg, oracle, E, fused):
         o.step(n)
         for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR", "WATER_0", "LIGHT_1"):
             assert np.array_equal(h.read_rect(f), o.field(f)), (case, f)
+        # the input released (the brush let go, the plane gone) and 20 iterations more: what the edit left behind is then carried by
+        # the brush-free launch decisions of the handle
+        u.update(userInputType=-1, airplaneValues=(0.0, 0.0, 0.0, 0.0))
+        h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"])
+        o.set_params(u)
+        h.step(20)
+        o.step(20)
+        for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR", "WATER_0", "LIGHT_1"):
+            assert np.array_equal(h.read_rect(f), o.field(f)), (case, f, "20 iterations after release")
         h.close()
 
 

@@ -2,10 +2,10 @@
 """Which lines and branch outcomes of the CPU oracle do the oracle-vs-reference tests execute?  CPU only, not part of the test run.
 
 Builds oracle/libwxoracle_cov.so (gcc --coverage, -O0), runs the tests that compare the oracle with the reference's own output
-(tests/test_oracle_golden.py, tests/test_oracle_sliders.py, tests/test_oracle_surface.py) in a child process that loads that library in place of
+(tests/test_oracle_golden.py, tests/test_oracle_sliders.py, tests/test_oracle_surface.py, tests/test_oracle_tools.py) in a child process that loads that library in place of
 libwxoracle.so, then prints gcov's totals and every branch outcome never taken, with its source line.
 
-    python tools/oracle_coverage.py [pytest arguments, default: the three test files]
+    python tools/oracle_coverage.py [pytest arguments, default: the four test files]
 
 A high figure says the STRUCTURE is pinned; it says nothing about the VALUES the uniforms took (that is what
 the sliders64 fixtures and their sensitivity table are for)."""
@@ -28,7 +28,7 @@ sys.exit(pytest.main(sys.argv[1:]))
 
 
 def main():
-    tests = sys.argv[1:] or [os.path.join(ROOT, "tests", f) for f in ("test_oracle_golden.py", "test_oracle_sliders.py", "test_oracle_surface.py")]
+    tests = sys.argv[1:] or [os.path.join(ROOT, "tests", f) for f in ("test_oracle_golden.py", "test_oracle_sliders.py", "test_oracle_surface.py", "test_oracle_tools.py")]
     for f in os.listdir(ORACLE):
         if f.endswith((".gcda", ".gcov")):
             os.remove(os.path.join(ORACLE, f))
