@@ -468,11 +468,11 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 // copy in front of the launch), read through the constant address space exactly as the lone kernel reads its kernel-argument segment:
 // the row loop keeps its scalar loads where it has them, and the scalars the body names directly come from the same slot. gridDim.x is a
 // multiple of 8 (blockIdx.x & 7 is still the XCD) sized for the member with the most segments; the surplus workgroups of the others
-// exit at once. Whole-domain members without droplets: no feedback textures (HAS_FB false), no split order.
-template <bool OPT_OUT, bool QUIET>
+// exit at once. Whole-domain members, no split order. HAS_FB as on a lone handle: the members of a launch all hand in feedback textures
+// (their droplets ran in the iteration before) or none does -- the driver partitions by it.
+template <bool OPT_OUT, bool HAS_FB, bool QUIET>
 __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet_ens(const WetEnsSlot *__restrict__ table)
 {
-  constexpr bool HAS_FB = false;
   typedef WetKArgs KArgs;
   typedef const __attribute__((address_space(4))) char *KBytes;
   const KBytes ka_c = (KBytes)(const char *)table + (size_t)blockIdx.y * sizeof(WetEnsSlot);
@@ -938,22 +938,25 @@ inline void launch_wet_fix(float iterNum, const FullCtx *ctx, const WetIn &in, c
 }
 
 // An ensemble launch (wx_ensemble_step): `table` holds n_members slots (device memory, written in front of the launch on the same stream),
-// groups_x = the largest ens_member_groups among the members' shapes. All members run the instantiation <opt_out, quiet>.
+// groups_x = the largest ens_member_groups among the members' shapes. All members run the instantiation <opt_out, has_fb, quiet>.
 inline int ens_member_groups(const WetLaunch &w)
 {
   const int groups = ((w.segs.bands ? w.n_strips : (w.n_strips + 7) / 8) + WX_WET_WPB - 1) / WX_WET_WPB;
   return 8 * groups * w.segs.n_seg;
 }
-inline void launch_march_wet_ens(const WetEnsSlot *table, int n_members, int groups_x, bool opt_out, bool quiet, hipStream_t stream)
+inline void launch_march_wet_ens(const WetEnsSlot *table, int n_members, int groups_x, bool opt_out, bool has_fb, bool quiet, hipStream_t stream)
 {
   const dim3 grid(groups_x, n_members), block(64 * WX_WET_WPB);
+#define WX_LAUNCH_E(O, F, Q) hipLaunchKernelGGL((k_march_wet_ens<O, F, Q>), grid, block, 0, stream, table)
+#define WX_LAUNCH_EQ(O, F) \
+  do { if (quiet) WX_LAUNCH_E(O, F, true); else WX_LAUNCH_E(O, F, false); } while (0)
   if (opt_out) {
-    if (quiet) hipLaunchKernelGGL((k_march_wet_ens<true, true>), grid, block, 0, stream, table);
-    else hipLaunchKernelGGL((k_march_wet_ens<true, false>), grid, block, 0, stream, table);
+    if (has_fb) WX_LAUNCH_EQ(true, true); else WX_LAUNCH_EQ(true, false);
   } else {
-    if (quiet) hipLaunchKernelGGL((k_march_wet_ens<false, true>), grid, block, 0, stream, table);
-    else hipLaunchKernelGGL((k_march_wet_ens<false, false>), grid, block, 0, stream, table);
+    if (has_fb) WX_LAUNCH_EQ(false, true); else WX_LAUNCH_EQ(false, false);
   }
+#undef WX_LAUNCH_EQ
+#undef WX_LAUNCH_E
 }
 // wgs_per_member: sized by the caller from the largest stale hint word of the members (launch_wet_fix's rule); any size is correct
 inline void launch_wet_fix_ens(const WetEnsSlot *table, int n_members, int wgs_per_member, bool opt_out, hipStream_t stream)

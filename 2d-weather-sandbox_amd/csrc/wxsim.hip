@@ -11,6 +11,7 @@
 #include "wx_march.h"
 #include "wx_march2.h"
 #include "wx_kernels.h"
+#include "wx_precip_ens.h"
 #include "wx_diag.h"
 
 #include <hip/hip_runtime.h>
@@ -933,7 +934,9 @@ struct WetIter { // what march_wet_prepare hands to the launch: one iteration's 
 // PRECONDITION the ensemble driver relies on (wx_ensemble.h runs prepare + commit of up to 16 iterations AHEAD of their launches): whatever
 // this function enqueues on the stream -- light_to_planes, the terrain scan, the exact-path list's first zeroing -- it enqueues in the FIRST
 // iteration prepared after an upload / option change only, never per iteration, and march_wet_commit enqueues nothing. Work enqueued here
-// in a later iteration would run before the launches of the iterations in front of it.
+// in a later iteration would run before the launches of the iterations in front of it. (The one-time clear of the feedback textures after
+// precipitation was switched off is NOT enqueued from that loop: the first iteration's launch still reads them -- the driver enqueues
+// clear_particle_textures_enqueue behind that launch.)
 int march_wet_prepare(wx_sim *s, bool opt_out, bool precip, WetIter &wi, int share_members = 1)
 {
   const int src = s->run.even ? 0 : 1;
@@ -1150,14 +1153,20 @@ int iterate_dry(wx_sim *s, bool write_disp, int edge_mode = 0)
 
 // The reference clears the feedback / deposition textures every iteration (app.js:5933-5937); here they are rewritten by the box sum while
 // particles run, and cleared ONCE by the first iteration after they were switched off (whichever kernel runs it).
-static void clear_particle_textures(wx_sim *s)
+// (the memsets alone: wx_ensemble_step, whose host bookkeeping runs ahead of its launches, enqueues them behind the launch that still reads
+// the textures -- wx_ensemble.h)
+static void clear_particle_textures_enqueue(wx_sim *s)
 {
-  if (!s->run.fb_dirty) return;
   const size_t n = ncell(s);
   hipMemsetAsync(s->fb, 0, n * 12, s->stream);
   hipMemsetAsync(s->dep, 0, n * 8, s->stream);
   hipMemsetAsync(&s->state->mailbox_w, 0, 4, s->stream); // (texel (1,0)'s alpha, the one the texture has: kept in the state, cleared with the texture)
   if (s->sg.fb_zero) hipMemsetAsync(s->sg.fb_zero, 1, 2 * (size_t)s->sg.TXn * s->sg.TYn, s->stream);
+}
+static void clear_particle_textures(wx_sim *s)
+{
+  if (!s->run.fb_dirty) return;
+  clear_particle_textures_enqueue(s);
   s->run.fb_dirty = false;
 }
 

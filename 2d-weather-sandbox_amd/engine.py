@@ -42,7 +42,7 @@ EXPORTS = [
     "wx_group_exchange", "wx_slab_vx_take", "wx_slab_set_vx_bound", "wx_slab_cone", "wx_slab_period", "wx_pair_stats", "wx_placement_info", "wx_arith",
     "wx_diag_collect", "wx_diag_merge", "wx_diag_finish", "wx_diag_accumulate", "wx_diag_accumulate_cells", "wx_diagnostics", "wx_group_diagnostics",
     "wx_ensemble_create", "wx_ensemble_destroy", "wx_ensemble_last_error", "wx_ensemble_count", "wx_ensemble_member", "wx_ensemble_step",
-    "wx_ensemble_sync", "wx_ensemble_diagnostics", "wx_ensemble_stats",
+    "wx_ensemble_sync", "wx_ensemble_diagnostics", "wx_ensemble_stats", "wx_ensemble_create_droplets", "wx_ensemble_particle_stats",
 ]
 
 
@@ -285,6 +285,8 @@ def lib() -> C.CDLL:
     L.wx_diagnostics.argtypes = [vp, vp]
     L.wx_group_diagnostics.argtypes = [vp, vp]
     L.wx_ensemble_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.wx_ensemble_create_droplets.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
+    L.wx_ensemble_particle_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.wx_ensemble_destroy.argtypes = [vp]
     L.wx_ensemble_destroy.restype = None
     L.wx_ensemble_last_error.argtypes = [vp]
@@ -809,18 +811,23 @@ class Group:
 
 class Ensemble:
     """B independent whole-domain simulations of one size (wx_ensemble_*): ``members`` are borrowed ``Handle``s -- upload, set_params,
-    set_option, read_rect ... exactly as on any handle --, ``step`` advances all of them in one marching launch per iteration."""
+    set_option, read_rect, read_particles ... exactly as on any handle --, ``step`` advances all of them in one marching launch per
+    iteration, and the ``n_droplets`` droplets of each in one set of particle launches."""
 
-    def __init__(self, n_members: int, X: int, Y: int):
+    def __init__(self, n_members: int, X: int, Y: int, n_droplets: int = 0):
         L = lib()
         e = C.c_void_p()
         _apply_env_defaults()
-        rc = L.wx_ensemble_create(int(n_members), int(X), int(Y), C.byref(e))
+        if n_droplets:
+            rc = L.wx_ensemble_create_droplets(int(n_members), int(X), int(Y), int(n_droplets), C.byref(e))
+        else:
+            rc = L.wx_ensemble_create(int(n_members), int(X), int(Y), C.byref(e))
         if rc != 0:
             raise WxError(rc, (L.wx_ensemble_last_error(None) or b"").decode())
         self._e = e
         self.n, self.X, self.Y = L.wx_ensemble_count(e), X, Y
-        self.members = [Handle._borrowed(L.wx_ensemble_member(e, i), X, Y, 0, self, 0) for i in range(self.n)]
+        self.n_droplets = int(n_droplets)
+        self.members = [Handle._borrowed(L.wx_ensemble_member(e, i), X, Y, 0, self, self.n_droplets) for i in range(self.n)]
 
     def _chk(self, rc: int):
         if rc != 0:
@@ -851,6 +858,12 @@ class Ensemble:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(lib().wx_ensemble_stats(self._e, C.byref(a), C.byref(b), C.byref(c)))
         return {"member_iters_batched": a.value, "member_iters_solo": b.value, "march_launches": c.value}
+
+    def particle_stats(self) -> dict:
+        """wx_ensemble_particle_stats: member-iterations whose particle pass shared its launches, and particle launches issued, so far."""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(lib().wx_ensemble_particle_stats(self._e, C.byref(a), C.byref(b)))
+        return {"member_iters_particles_batched": a.value, "particle_launches": b.value}
 
     def close(self):
         if getattr(self, "_e", None):

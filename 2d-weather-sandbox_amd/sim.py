@@ -215,22 +215,31 @@ class WeatherSim:
 class WeatherEnsemble:
     """B ``WeatherSim`` members of one size on one ``engine.Ensemble``: one scene (arrays, a save file or a synthetic terrain) plus
     per-member setting overrides -- a sweep over the sliders, a perturbed ensemble. Every member is a full ``WeatherSim`` (``set_gui``,
-    ``set_brush``, ``read_rect`` ...); ``step`` advances all of them in one marching launch per iteration. No droplets."""
+    ``set_brush``, ``read_rect``, ``read_particles`` ...); ``step`` advances all of them in one marching launch per iteration, their
+    droplets in one set of particle launches."""
 
     def __init__(self, n_members: int, X: int, Y: int, base, water, wall, settings: Optional[Dict[str, Any]] = None,
-                 overrides: Optional[Sequence[Optional[Dict[str, Any]]]] = None, *, perturb=None, columns=None, **kw):
+                 overrides: Optional[Sequence[Optional[Dict[str, Any]]]] = None, *, perturb=None, columns=None, droplets=None, **kw):
         """``overrides[i]``: guiControls entries of member i on top of ``settings``; ``perturb(i, base, water, wall)`` may return member
-        i's own copies of the arrays."""
+        i's own copies of the arrays -- three, or four with the member's own droplet pool; ``droplets``: one pool (n x 5) that every
+        member starts from (all members hold the same number of droplets)."""
         from .engine import Ensemble
         if overrides is not None and len(overrides) != n_members:
             raise ValueError("one overrides entry per member")
-        self._e = Ensemble(n_members, X, Y)
+        for o in overrides or ():
+            for k in o or ():  # (as set_gui: an unknown name would be merged and never reach a uniform)
+                if k not in params.GUI_DEFAULTS:
+                    raise KeyError(k)
+        n_drops = 0 if droplets is None else int(np.asarray(droplets).size // 5)
+        self._e = Ensemble(n_members, X, Y, n_drops)
         self.members = []
         for i in range(n_members):
             st = dict(settings or {})
             st.update((overrides[i] if overrides is not None else None) or {})
-            b, w, wl = (base, water, wall) if perturb is None or columns is not None else perturb(i, base, water, wall)
-            m = WeatherSim(X, Y, b, w, wl, None, st, columns=columns, handle=self._e[i], **kw)
+            arrays = (base, water, wall) if perturb is None or columns is not None else tuple(perturb(i, base, water, wall))
+            b, w, wl = arrays[:3]
+            d = arrays[3] if len(arrays) > 3 else droplets
+            m = WeatherSim(X, Y, b, w, wl, d if n_drops else None, st, columns=columns, handle=self._e[i], **kw)
             m.verbose = False
             m._placement_told = True  # (members never search for a placement)
             self.members.append(m)
@@ -239,14 +248,20 @@ class WeatherEnsemble:
     def from_save(cls, n_members: int, sf: "codec.SaveFile | str", overrides=None, **kw) -> "WeatherEnsemble":
         if isinstance(sf, str):
             sf = codec.load(sf)
-        return cls(n_members, sf.X, sf.Y, sf.base, sf.water, sf.wall, sf.settings, overrides, **kw)
+        drops = sf.droplets if sf.droplets is not None and len(sf.droplets) else None
+        return cls(n_members, sf.X, sf.Y, sf.base, sf.water, sf.wall, sf.settings, overrides, droplets=drops, **kw)
 
     @classmethod
     def new_simulation(cls, n_members: int, X: int, Y: int, settings: Optional[Dict[str, Any]] = None, overrides=None, *, seed: float = 0.5,
-                       height_mult: float = 0.3, **kw) -> "WeatherEnsemble":
+                       height_mult: float = 0.3, n_droplets: int = 0, droplet_seed: int = 1, **kw) -> "WeatherEnsemble":
+        """``n_droplets`` per member, initialised on the device (wx_init_droplets; member i with seed ``droplet_seed + i``)."""
         from . import synth
         cols = synth.terrain_columns(X, Y, params.merge_settings(settings), seed=seed, height_mult=height_mult)
-        return cls(n_members, X, Y, None, None, None, settings, overrides, columns=cols, **kw)
+        n = int(n_droplets)
+        ens = cls(n_members, X, Y, None, None, None, settings, overrides, columns=cols, droplets=synth.init_rain_drops(n) if n else None, **kw)
+        for i, m in enumerate(ens.members if n else ()):
+            m.handle.init_droplets(int(droplet_seed) + i)
+        return ens
 
     def __len__(self):
         return len(self.members)
@@ -271,6 +286,9 @@ class WeatherEnsemble:
 
     def stats(self) -> dict:
         return self._e.stats()
+
+    def particle_stats(self) -> dict:
+        return self._e.particle_stats()
 
     @property
     def engine(self):

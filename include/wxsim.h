@@ -560,24 +560,38 @@ int wx_group_diagnostics(wx_group *g, wx_diag *out);
 /* ---- Ensembles: many independent simulations of one size, stepped in one launch (no reference counterpart: the reference runs one
  * simulation per page). A lone 100 x 100 grid is two strips and two dependent launches per iteration, a lone 2500 x 300 grid has to be cut
  * into 4-row segments to put a wave on every SIMD; a host that has MANY such grids -- a sweep over the sliders, a perturbed ensemble, a
- * fuzzer -- puts them into an ensemble: n_members whole-domain handles of X x Y cells on the current device, without droplets, whose
- * iterations share ONE marching launch and ONE fix launch per iteration and kernel instantiation.
+ * fuzzer -- puts them into an ensemble: n_members whole-domain handles of X x Y cells on the current device, with or without droplets
+ * (wx_ensemble_create_droplets: every member as from wx_create(X, Y, n_droplets); wx_ensemble_create: n_droplets = 0), whose iterations
+ * share ONE marching launch and ONE fix launch per iteration and kernel instantiation, and whose particle passes share their launches too.
  *
  * A MEMBER IS AN ORDINARY HANDLE (wx_ensemble_member; borrowed, like wx_group_slab): wx_upload / wx_setup_* / wx_set_params / wx_set_option /
- * wx_set_iter / wx_read_rect / wx_diagnostics / wx_fastest_velocity exactly as on a handle from wx_create. After wx_ensemble_step(e, n)
+ * wx_set_iter / wx_read_rect / wx_diagnostics / wx_fastest_velocity exactly as on a handle from wx_create, and with droplets wx_upload /
+ * wx_setup_* with a pool, wx_init_droplets, wx_read_particles, WX_OPT_SPLAT_ORDER, inactiveDroplets / enablePrecipitation of wx_set_params,
+ * the droplet entries of wx_diagnostics and WX_FIELD_PRECIP_FB / _PRECIP_DEP / _LIGHTNING. After wx_ensemble_step(e, n)
  * every readable field, wx_get_iter, wx_diagnostics, wx_fastest_velocity and every reported error of member i are what a handle from
- * wx_create(X, Y, 0) with the same uploads, parameters, options and iteration counter shows after wx_step(h, n) -- bit for bit, the
+ * wx_create(X, Y, n_droplets) with the same uploads, parameters, options and iteration counter shows after wx_step(h, n), the
  * display-side fields (WX_FIELD_BASE_DISP, _WATER_0, _CURL, _WALL_DISP, _EMITTED) included: the last iteration of the call is the
- * display iteration for all members. Members differ freely in state, parameters (every uniform of wx_params, the sounding arrays,
- * wrapHorizontally, brush / airplane inputs), iteration counter and terrain.
+ * display iteration for all members. Bit for bit where a lone handle is reproducible: always without droplets; with droplets the pool
+ * always, and every readable field under WX_OPT_SPLAT_ORDER 1. Under the default order (fp32 atomics in arrival order) the pool after the
+ * first iteration and whatever lone sprites make order-free are bit-identical, and the rest agrees to summation order -- exactly as two
+ * runs of a lone handle do. Members differ freely in state, droplet pool, parameters (every uniform of wx_params, the sounding arrays,
+ * wrapHorizontally, brush / airplane inputs), options, iteration counter and terrain.
  *
  * What is batched: the member-iterations the marching wet kernel would run on a lone handle (default kernel set, all grid passes). The
  * members of a call are partitioned by the instantiation they need -- a brush held on one member does not push the others into the general
  * instantiation --, one marching and one fix launch per iteration and non-empty partition; every member keeps its own exact-path list,
- * hint word, fastest-velocity word and overflow flag. What is not: a member whose iterations do not qualify (WX_PASS_DRY or any partial
- * pass mask, WX_OPT_KERNEL_SET 0) runs n_iter iterations of its own path (wx_step) on the ensemble's stream, behind the batched members,
- * in member order. wx_ensemble_stats counts both, so that a host can see that the batch path ran: member-iterations batched / run solo
- * and marching launches issued, since the ensemble was created (any pointer may be NULL).
+ * hint word, fastest-velocity word and overflow flag. (Whether a member hands in feedback textures -- its droplets ran in the iteration
+ * before -- is part of the instantiation, as on a lone handle.) Of the batched members, those whose droplets run (WX_PASS_PRECIPITATION in
+ * the pass mask, enablePrecipitation, n_droplets > 0) share the particle pass behind the fix launches: ONE launch each of the
+ * precipitation, classify, box-sum and clear kernels per iteration, however many members -- every member keeps its own pool, device
+ * state, accumulation grid and textures. Under WX_OPT_SPLAT_ORDER 1 a member's deposit records are sorted by its own radix sort and
+ * added by its own run-sum launch between the shared launches (a per-member sort, not a segmented one: the mode is for tests, and any
+ * stable sort gives the same bits); members of either order share the four launches. What is not batched: a member whose iterations do
+ * not qualify (WX_PASS_DRY or any partial pass mask, WX_OPT_KERNEL_SET 0) runs n_iter iterations of its own path (wx_step), droplets
+ * included, on the ensemble's stream, behind the batched members, in member order. wx_ensemble_stats counts both, so that a host can
+ * see that the batch path ran: member-iterations batched / run solo and marching launches issued, since the ensemble was created (any
+ * pointer may be NULL). wx_ensemble_particle_stats counts the member-iterations whose particle pass was shared and the particle launches
+ * issued for them (4 per iteration, + 2 per order-1 member: its sort and its run sums), likewise.
  *
  * An error is the member's: an overflowed exact-path list of member 3 is reported (WX_E_STATE) by member 3's next blocking call or by
  * wx_ensemble_sync / wx_ensemble_diagnostics -- whichever looks first consumes the report, as on a lone handle --, and
@@ -589,11 +603,14 @@ int wx_group_diagnostics(wx_group *g, wx_diag *out);
  * wx_set_comm_stream / wx_tune_placement on a member return WX_E_STATE, and the implicit placement search never runs on a member (as on a
  * slab). wx_step on a member stays legal and means what it always meant. wx_ensemble_step is asynchronous like wx_step; wx_profile on a
  * member does not see the shared launches. wx_ensemble_destroy destroys the member handles too (do not wx_destroy them).
- * Refused with WX_E_INVALID: n_members < 1, droplets (members are created with n_droplets = 0), slab members and members of different
- * sizes (there is no way to add a handle to an ensemble). Not batched yet: the water-free dry kernels and the particle pass. */
+ * Refused with WX_E_INVALID: n_members < 1 or > 65535, n_droplets < 0; there are no slab members, no members of different sizes or
+ * droplet counts (there is no way to add a handle to an ensemble). WX_OPT_CHECK_LAUNCHES on any batched member synchronises behind the
+ * particle launches too. Not batched yet: the water-free dry kernels. */
 #define WX_HAVE_ENSEMBLE 1
+#define WX_HAVE_ENSEMBLE_DROPLETS 1
 typedef struct wx_ensemble wx_ensemble;
 int wx_ensemble_create(int n_members, int X, int Y, wx_ensemble **out);
+int wx_ensemble_create_droplets(int n_members, int X, int Y, int n_droplets, wx_ensemble **out);
 void wx_ensemble_destroy(wx_ensemble *e);
 const char *wx_ensemble_last_error(const wx_ensemble *e); /* also valid with e == NULL for create failures */
 int wx_ensemble_count(const wx_ensemble *e);
@@ -602,6 +619,7 @@ int wx_ensemble_step(wx_ensemble *e, int n_iter);
 int wx_ensemble_sync(wx_ensemble *e);
 int wx_ensemble_diagnostics(wx_ensemble *e, wx_diag *out);
 int wx_ensemble_stats(wx_ensemble *e, int64_t *member_iters_batched, int64_t *member_iters_solo, int64_t *march_launches);
+int wx_ensemble_particle_stats(wx_ensemble *e, int64_t *member_iters_particles_batched, int64_t *particle_launches);
 
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts

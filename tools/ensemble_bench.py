@@ -11,6 +11,9 @@ member gets a moving fluid of its own (devtools.seed_flow, seed = member index) 
 region the chip is conditioned with untimed frames for a quarter of a second (bench.py: condition_clocks); a region is at least
 --steps iterations of every member; --repeats regions are timed and all of them reported (compare the SLOWEST of each side).
 The roofline fraction is 104 B / cell-step against bench.py's HBM_PEAK_GBS = 8000 GB/s (--peak-gbs).
+--droplets N: every member carries N droplets (synth.init_rain_drops, seed = member index), enablePrecipitation = 1 and a cloud deck
+(synth.add_cloud_deck) so that droplets spawn, grow and fall -- in both modes; the ensemble's record gains `particle_stats`. The default 0
+is the droplet-free run.
 --share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
 import argparse
 import json
@@ -31,13 +34,14 @@ def parse():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--flow", type=float, default=0.2)
     ap.add_argument("--peak-gbs", type=float, default=8000.0, help="what the roofline fraction is quoted against [GB/s]: bench.py's HBM_PEAK_GBS")
+    ap.add_argument("--droplets", type=int, default=0, help="droplets per member (0: none, precipitation off)")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     return ap.parse_args()
 
 
-def make_members(pkg, X, Y, B, make, flow=0.2):
-    """`make(i)` -> a handle of X x Y; uploads the scene, sets the parameters, seeds member i's own flow."""
+def make_members(pkg, X, Y, B, make, flow=0.2, droplets=0):
+    """`make(i)` -> a handle of X x Y (with `droplets` droplets); uploads the scene, sets the parameters, seeds member i's own flow."""
     import numpy as np
     from weather_sandbox_amd import devtools
     P = pkg.params
@@ -49,16 +53,25 @@ def make_members(pkg, X, Y, B, make, flow=0.2):
         for k in ("userInputValues", "userInputMove", "airplaneValues"):
             u[k] = tuple(u[k])
         u = dict(u, quad_scale=0, enablePrecipitation=0)
+        base, water, wall = g["in_base"], g["in_water"].copy(), g["in_wall"]
     else:
         gui = P.merge_settings(None)
         gui["sunAngle"] = 50.0
         u = P.uniforms_from_gui(gui, Y, quad_scale=0)
         u["enablePrecipitation"] = 0
-        cols = pkg.synth.terrain_columns(X, Y)
+        if droplets:
+            base, water, wall = pkg.synth.terrain_grid(X, Y)
+        else:
+            cols = pkg.synth.terrain_columns(X, Y)
+    if droplets:
+        u["enablePrecipitation"] = 1
+        pkg.synth.add_cloud_deck(water, wall)
     for i in range(B):
         h = make(i)
-        if (X, Y) == (100, 100):
-            h.upload(g["in_base"], g["in_water"], g["in_wall"])
+        if droplets:
+            h.upload(base, water, wall, pkg.synth.init_rain_drops(droplets, seed=7 + i))
+        elif (X, Y) == (100, 100):
+            h.upload(base, water, wall)
         else:
             h.setup_columns(cols)
         h.set_params(P.fill_struct(P.WxParams(), u), u["initial_T"])
@@ -80,15 +93,16 @@ def main():
     E = pkg.engine
     E.lib().wx_set_option(None, E.Handle.OPT_PLACEMENT_SEARCH, 0)
     torch.cuda.set_device(0)
-    out = {"tool": "ensemble_bench", "mode": a.mode, "root": os.path.relpath(a.root, ROOT), "frame": a.frame, "steps": a.steps, "share": a.share, "shapes": {}}
+    out = {"tool": "ensemble_bench", "mode": a.mode, "root": os.path.relpath(a.root, ROOT), "frame": a.frame, "steps": a.steps, "share": a.share, "droplets": a.droplets,
+           "shapes": {}}
     for spec in a.shapes.split(","):
         X, Y, B = (int(v) for v in spec.split("x"))
         if a.mode == "ensemble":
-            ens = E.Ensemble(B, X, Y)
-            make_members(pkg, X, Y, B, lambda i: ens[i], a.flow)
+            ens = E.Ensemble(B, X, Y, a.droplets) if a.droplets else E.Ensemble(B, X, Y)
+            make_members(pkg, X, Y, B, lambda i: ens[i], a.flow, a.droplets)
             step, sync, close = ens.step, ens.sync, ens.close
         else:
-            hs = make_members(pkg, X, Y, B, lambda i: E.Handle(X, Y, 0), a.flow)
+            hs = make_members(pkg, X, Y, B, lambda i: E.Handle(X, Y, a.droplets), a.flow, a.droplets)
 
             def step(n):
                 for h in hs:
@@ -130,6 +144,8 @@ def main():
                "roofline_fraction_slowest": round(X * Y * B * 104 / worst / (a.peak_gbs * 1e9), 4)}
         if a.mode == "ensemble":
             rec["stats"] = ens.stats()
+            if a.droplets:
+                rec["particle_stats"] = ens.particle_stats()
         out["shapes"][spec] = rec
         close()
     print(json.dumps(out))
