@@ -53,11 +53,12 @@ enum KernelId {
   K_MARCH_DRY,  // the same as a row-marching wavefront kernel (wx_march.h)
   K_MARCH_WET,  // the whole iteration as one row-marching wavefront kernel (wx_wet.h)
   K_MARCH_DRY2, // TWO dry iterations per launch (wx_march2.h)
+  K_ENS_STAT,   // per-cell statistics over the members of an ensemble (wx_ens_stat.h)
   K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "boundary", "advection", "pressure", "lighting",
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
-                                           "march_wet_full_iteration", "march_dry2_two_iterations_per_launch"};
+                                           "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -3079,3 +3080,4 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 
 #include "wx_comm.h" // (its entry points are declared extern "C" by include/wxsim.h)
 #include "wx_ensemble.h" // (likewise)
+#include "wx_ens_stat.h" // (likewise)

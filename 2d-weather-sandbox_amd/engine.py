@@ -43,6 +43,7 @@ EXPORTS = [
     "wx_diag_collect", "wx_diag_merge", "wx_diag_finish", "wx_diag_accumulate", "wx_diag_accumulate_cells", "wx_diagnostics", "wx_group_diagnostics",
     "wx_ensemble_create", "wx_ensemble_destroy", "wx_ensemble_last_error", "wx_ensemble_count", "wx_ensemble_member", "wx_ensemble_step",
     "wx_ensemble_sync", "wx_ensemble_diagnostics", "wx_ensemble_stats", "wx_ensemble_create_droplets", "wx_ensemble_particle_stats",
+    "wx_ensemble_statistics", "wx_ens_stat_cells",
 ]
 
 
@@ -152,6 +153,69 @@ def diag_accumulate_cells(raw, X_global: int, Y: int, x: int, y: int, base, wate
     if rc != 0:
         raise WxError(rc, "wx_diag_accumulate_cells: bad geometry or range")
     return bytes(r)
+
+
+class WxEnsStat(C.Structure):
+    """``wx_ens_stat`` of include/wxsim.h: caller-owned output planes (NULL = not wanted) and the four thresholds."""
+    _fields_ = [
+        ("mean", C.c_void_p), ("variance", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p), ("argmin", C.c_void_p), ("argmax", C.c_void_p),
+        ("count", C.c_void_p), ("n_above", C.c_void_p), ("n_wall", C.c_void_p), ("threshold", C.c_float * 4),
+    ]
+
+
+# the planes of wx_ens_stat: name, element type, channels per cell
+ENS_STAT_PLANES = (("mean", np.float32, 4), ("variance", np.float32, 4), ("min", np.float32, 4), ("max", np.float32, 4), ("argmin", np.int32, 4),
+                   ("argmax", np.int32, 4), ("count", np.int32, 4), ("n_above", np.int32, 4), ("n_wall", np.int32, 1))
+ENS_STAT_ALL = tuple(name for name, _, _ in ENS_STAT_PLANES)
+
+
+def _ens_stat_struct(shape, threshold, want):
+    """A wx_ens_stat over fresh arrays of ``shape`` + (4,) (n_wall: ``shape``) for the planes named in ``want``, and those arrays by name."""
+    unknown = set(want) - set(ENS_STAT_ALL)
+    if unknown:
+        raise KeyError(f"no such plane of wx_ens_stat: {sorted(unknown)} (there are {ENS_STAT_ALL})")
+    st, planes = WxEnsStat(), {}
+    for name, dt, ch in ENS_STAT_PLANES:
+        if name in want:
+            planes[name] = np.zeros(tuple(shape) + ((ch,) if ch > 1 else ()), dt)
+            setattr(st, name, planes[name].ctypes.data)
+    st.threshold[:] = [float(t) for t in threshold]
+    return st, planes
+
+
+def _member_mask(n: int, members) -> Optional[np.ndarray]:
+    """``members``: None (all), member indices, or n booleans -> the n bytes wx_ensemble_statistics / wx_ens_stat_cells take."""
+    if members is None:
+        return None
+    m = np.asarray(members)
+    if m.dtype == np.bool_:
+        if m.shape != (n,):
+            raise ValueError(f"a boolean member mask has one entry per member ({n})")
+        return np.ascontiguousarray(m, np.uint8)
+    mask = np.zeros(n, np.uint8)
+    for i in m.ravel():
+        if not 0 <= int(i) < n:
+            raise IndexError(f"member {int(i)} of {n}")
+        mask[int(i)] = 1
+    return mask
+
+
+def ens_stat_cells(fields, walls, *, members=None, threshold=(0, 0, 0, 0), want=ENS_STAT_ALL) -> dict:
+    """wx_ens_stat_cells: the statistics kernel's per-cell function on the CPU. ``fields[i]`` / ``walls[i]``: member i's cells, float32
+    (..., 4) and int8 (..., 4) of one common shape (what ``read_rect`` returns); the planes come back in that shape."""
+    f = [np.ascontiguousarray(a, np.float32) for a in fields]
+    wl = [np.ascontiguousarray(a, np.int8) for a in walls]
+    n = len(f)
+    if n < 1 or len(wl) != n or any(a.shape != f[0].shape or a.shape[-1:] != (4,) for a in f + wl):
+        raise ValueError("one (..., 4) field and one (..., 4) wall array per member, all of one shape")
+    shape = f[0].shape[:-1]
+    st, planes = _ens_stat_struct(shape, threshold, want)
+    fp, wp = (C.c_void_p * n)(*[a.ctypes.data for a in f]), (C.c_void_p * n)(*[a.ctypes.data for a in wl])
+    mask = _member_mask(n, members)
+    rc = lib().wx_ens_stat_cells(n, int(np.prod(shape, dtype=np.int64)), fp, wp, None if mask is None else mask.ctypes.data, C.byref(st))
+    if rc != 0:
+        raise WxError(rc, "wx_ens_stat_cells: no member selected")
+    return planes
 
 
 def build(force: bool = False, fast: bool = False) -> str:
@@ -298,6 +362,8 @@ def lib() -> C.CDLL:
     L.wx_ensemble_sync.argtypes = [vp]
     L.wx_ensemble_diagnostics.argtypes = [vp, vp]
     L.wx_ensemble_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.wx_ensemble_statistics.argtypes = [vp, i32, i32, i32, i32, i32, vp, C.POINTER(WxEnsStat)]
+    L.wx_ens_stat_cells.argtypes = [i32, C.c_size_t, vp, vp, vp, C.POINTER(WxEnsStat)]
     _lib = L
     return L
 
@@ -864,6 +930,18 @@ class Ensemble:
         a, b = C.c_int64(), C.c_int64()
         self._chk(lib().wx_ensemble_particle_stats(self._e, C.byref(a), C.byref(b)))
         return {"member_iters_particles_batched": a.value, "particle_launches": b.value}
+
+    def statistics(self, field: str, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, *, members=None,
+                   threshold=(0, 0, 0, 0), want=ENS_STAT_ALL) -> dict:
+        """wx_ensemble_statistics: per cell of the rectangle, over the selected members (None: all; member indices; or one boolean
+        per member), the planes named in ``want`` -- mean, variance, min, max (float32), argmin, argmax, count, n_above (int32), all
+        (h, w, 4), and n_wall (h, w). ``field``: BASE_CUR or WATER_CUR. Computed on the device in one launch; blocks like ``sync``."""
+        w = self.X - x if w is None else w
+        h = self.Y - y if h is None else h
+        st, planes = _ens_stat_struct((max(h, 0), max(w, 0)), threshold, want)
+        mask = _member_mask(self.n, members)
+        self._chk(lib().wx_ensemble_statistics(self._e, FIELD_IDS[field], int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data, C.byref(st)))
+        return planes
 
     def close(self):
         if getattr(self, "_e", None):

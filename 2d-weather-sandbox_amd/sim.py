@@ -290,6 +290,19 @@ class WeatherEnsemble:
     def particle_stats(self) -> dict:
         return self._e.particle_stats()
 
+    def statistics(self, field: str, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, *, members=None,
+                   threshold=(0, 0, 0, 0), want=None) -> dict:
+        """``engine.Ensemble.statistics`` over the members (mean, variance, extremes and who holds them, counts), plus
+        ``probability`` = n_above / count in float64 -- the fraction of the entered values above ``threshold`` -- NaN where no value
+        entered. ``want`` (default: every plane) always gains ``count`` and ``n_above``."""
+        from .engine import ENS_STAT_ALL
+        want = tuple(ENS_STAT_ALL if want is None else want)
+        out = self._e.statistics(field, x, y, w, h, members=members, threshold=threshold, want=want + tuple(k for k in ("count", "n_above") if k not in want))
+        n = out["count"].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["probability"] = np.where(n > 0, out["n_above"].astype(np.float64) / n, np.nan)
+        return out
+
     @property
     def engine(self):
         return self._e

@@ -621,6 +621,60 @@ int wx_ensemble_diagnostics(wx_ensemble *e, wx_diag *out);
 int wx_ensemble_stats(wx_ensemble *e, int64_t *member_iters_batched, int64_t *member_iters_solo, int64_t *march_launches);
 int wx_ensemble_particle_stats(wx_ensemble *e, int64_t *member_iters_particles_batched, int64_t *particle_launches);
 
+/* ---- Ensemble statistics: per cell of a rectangle the mean, spread, extremes and exceedance count OVER THE MEMBERS, computed on the
+ * device in one launch (no reference counterpart). What wx_diag is for the space axis this is for the member axis: without it every
+ * per-cell look at an ensemble is n_members wx_read_rect calls and host arithmetic.
+ *
+ * THE PER-CELL FUNCTION (the kernel, wx_ens_stat_cells and the tests all evaluate this definition). For cell (x, y) and channel c take
+ * the selected members in MEMBER ORDER, 0 first.
+ *   Which values enter. A member in which the cell is a WALL cell -- wx_diag's test: channel 1 of its WX_FIELD_WALL_CUR texel is 0 --
+ *   counts into n_wall and contributes nothing. Of the remaining values the FINITE ones enter, and `count` counts them; NaN and +-Inf
+ *   do not enter (their number is: selected members - n_wall - count).
+ *   Sums. n = count. S = the entered values converted to double and added one at a time in member order, every addition rounded to
+ *   double. m = S / n in double; mean = (float)m. Q = the sum, in the same order, of d * d with d = (double)v - m, the product and the
+ *   addition rounded separately (no fused multiply-add); variance = (float)(Q / n), the POPULATION variance. n = 0: mean and variance
+ *   are NaN.
+ *   Extremes. min and max over the entered values; -0.0 and 0.0 compare equal, a zero extreme is reported as +0.0; among equal values
+ *   the smallest member index wins (argmin / argmax: the member's index in the ensemble -- in `field` for wx_ens_stat_cells --, not
+ *   its position in the selection). n = 0: min and max are NaN, argmin and argmax -1.
+ *   Exceedance. n_above = the number of entered values with v > threshold[c]; a NaN threshold gives 0. Probabilities are left to the
+ *   host: an integer is exact.
+ * These are NOT math.fsum sums like wx_diag's: they are sums IN A FIXED ORDER, and the result depends on that order (1e30, 1, -1e30, 1
+ * sums to 1, sorted to 0). An exact sum needs a 320-bit accumulator per quantity -- per cell and channel that is more memory than the
+ * fields it summarises. The order is part of the definition instead, the function is evaluated with floating-point contraction off
+ * in every build, and libwxsim.so, libwxsim_fast.so, the device and the host give the same bits.
+ *
+ * wx_ensemble_statistics: `field` is WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR (the fields that are stored whole and interleaved, the
+ * ones wx_diag covers; any other: WX_E_INVALID), the rectangle lies inside the grid (no wrap, as wx_read_rect: WX_E_RANGE),
+ * member_mask has one byte per member, non-zero = selected, NULL = all (nobody selected: WX_E_INVALID; a selected member that was
+ * never uploaded: WX_E_STATE, the message names it); e or out NULL: WX_E_INVALID. These checks answer before the device is touched.
+ * The work is enqueued on the ensemble's stream behind everything pending -- the members' pointers are taken at the time of the call
+ * --, and the call then BLOCKS like wx_ensemble_sync; like it, it is a place where a member's pending report (an overflowed
+ * exact-path list, ...) is consumed and returned ("member i: ...") instead of numbers. It changes nothing: not the members' fields,
+ * not the fields that are made on demand, not the iteration counters, the diagnostics or wx_ensemble_stats. The device buffers (a
+ * table of the selected members, the wanted planes of the rectangle and their pinned copy) belong to the ensemble, are made by the
+ * first call, grow on demand and go with wx_ensemble_destroy. wx_profile on member 0 times the launch, whoever is selected (kernel name
+ * "ensemble_statistics"). The kernel takes one lane per cell and walks the members serially, as
+ * the definition demands: a small rectangle under-fills the chip whatever the number of members. */
+#define WX_HAVE_ENSEMBLE_STATISTICS 1
+typedef struct wx_ens_stat {      /* caller-owned host arrays over the rectangle, rows bottom-up; any pointer may be NULL (not wanted) */
+  float   *mean, *variance;       /* w*h*4, channel-interleaved like the field */
+  float   *min, *max;             /* w*h*4 */
+  int32_t *argmin, *argmax;       /* w*h*4: member index of the extreme; -1: none */
+  int32_t *count;                 /* w*h*4: values that entered (see above) */
+  int32_t *n_above;               /* w*h*4: entered values with v > threshold[c] */
+  int32_t *n_wall;                /* w*h:   selected members in which the cell is a wall cell */
+  float    threshold[4];
+} wx_ens_stat;
+
+int wx_ensemble_statistics(wx_ensemble *e, int field, int x, int y, int w, int h,
+                           const uint8_t *member_mask /* n_members bytes, NULL = all */, wx_ens_stat *out);
+/* host only, pure: the kernel's per-cell function over n_cells cells held by the caller, member i's cells at field[i] (4 floats per cell) /
+ * wall[i] (4 bytes per cell); outputs as above with w*h = n_cells. WX_E_INVALID: n_members < 1, a NULL table or output struct, a NULL
+ * entry of a selected member, nobody selected. */
+int wx_ens_stat_cells(int n_members, size_t n_cells, const float *const *field, const int8_t *const *wall,
+                      const uint8_t *member_mask, wx_ens_stat *out);
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

@@ -14,6 +14,11 @@ The roofline fraction is 104 B / cell-step against bench.p
 --droplets N: every member carries N droplets (synth.init_rain_drops, seed = member index), enablePrecipitation = 1 and a cloud deck
 (synth.add_cloud_deck) so that droplets spawn, grow and fall -- in both modes; the ensemble's record gains `particle_stats`. The default 0
 is the droplet-free run.
+--statistics FIELD (BASE_CUR or WATER_CUR; --mode ensemble): instead of the stepping time, what ONE wx_ensemble_statistics call over the
+whole grid costs (all nine planes, host to host: the call blocks) against the route it replaces -- B read_rect calls of the field and B of
+WALL_CUR plus the same arithmetic in numpy, member by member in member order as include/wxsim.h defines it -- after --frame iterations;
+--repeats calls of each, the slowest and the median reported under the shape's "statistics" key, with the kernel's own time (wx_profile
+on member 0) and the bytes it reads per second (members x 20 B per cell and pass, two passes).
 --share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
 import argparse
 import json
@@ -35,6 +40,7 @@ def parse():
     ap.add_argument("--flow", type=float, default=0.2)
     ap.add_argument("--peak-gbs", type=float, default=8000.0, help="what the roofline fraction is quoted against [GB/s]: bench.py's HBM_PEAK_GBS")
     ap.add_argument("--droplets", type=int, default=0, help="droplets per member (0: none, precipitation off)")
+    ap.add_argument("--statistics", default="", metavar="FIELD", help="time one statistics call over the whole grid against B read_rect calls + numpy (BASE_CUR or WATER_CUR)")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     return ap.parse_args()
@@ -80,8 +86,91 @@ def make_members(pkg, X, Y, B, make, flow=0.2, droplets=0):
     return hs
 
 
+def numpy_statistics(fields, walls, threshold):
+    """The per-cell function of include/wxsim.h in numpy: members in member order, vectorised over the cells (what a host does today)."""
+    import numpy as np
+    shape = fields[0].shape
+    thr = np.asarray(threshold, np.float32)
+    S, n, above = np.zeros(shape), np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+    n_wall = np.zeros(shape[:-1], np.int32)
+    mn, mx = np.full(shape, np.inf, np.float32), np.full(shape, -np.inf, np.float32)
+    amn, amx = np.full(shape, -1, np.int32), np.full(shape, -1, np.int32)
+    takes = []
+    with np.errstate(all="ignore"):
+        for i, (v, wl) in enumerate(zip(fields, walls)):
+            is_wall = wl[..., 1] == 0
+            n_wall += is_wall
+            take = ~is_wall[..., None] & np.isfinite(v)
+            takes.append(take)
+            S = np.where(take, S + v.astype(np.float64), S)
+            n += take
+            lo, hi = take & (v < mn), take & (v > mx)
+            mn, amn = np.where(lo, v, mn), np.where(lo, np.int32(i), amn)
+            mx, amx = np.where(hi, v, mx), np.where(hi, np.int32(i), amx)
+            above += take & (v > thr)
+        m = np.where(n > 0, S / n, np.nan)
+        Q = np.zeros(shape)
+        for v, take in zip(fields, takes):
+            d = v.astype(np.float64) - m
+            Q = np.where(take, Q + d * d, Q)
+        none = n == 0
+        return {"mean": m.astype(np.float32), "variance": np.where(none, np.nan, Q / n).astype(np.float32),
+                "min": np.where(none, np.float32(np.nan), np.where(mn == 0, np.float32(0), mn)), "max": np.where(none, np.float32(np.nan), np.where(mx == 0, np.float32(0), mx)),
+                "argmin": amn, "argmax": amx, "count": n, "n_above": above, "n_wall": n_wall}
+
+
+def time_statistics(a, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    field, thr = a.statistics, (0.0, 0.0, 0.0, 0.0)
+
+    def device():
+        return ens.statistics(field, threshold=thr)
+
+    def reads():
+        return [m.read_rect(field) for m in ens.members], [m.read_rect("WALL_CUR") for m in ens.members]
+
+    def host():
+        return numpy_statistics(*reads(), thr)
+
+    ens.step(a.frame)
+    ens.sync()
+    got, want = device(), host()
+    differ = [k for k in want if not np.array_equal(got[k], want[k], equal_nan=got[k].dtype.kind == "f")]
+    if differ:  # two routes that disagree are not two timings of one thing
+        sys.exit("--statistics %s %dx%dx%d: wx_ensemble_statistics and the read_rect route disagree in %s" % (field, X, Y, B, ", ".join(differ)))
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        device()
+    ens[0].profile(True)
+    t_dev, t_read, t_host = [], [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        device()
+        t_dev.append(time.perf_counter() - t0)
+    kernel_ms, launches = ens[0].profile_read().get("ensemble_statistics", (0.0, 0))
+    ens[0].profile(False)
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        r = reads()
+        t1 = time.perf_counter()
+        numpy_statistics(*r, thr)
+        t_read.append(t1 - t0)
+        t_host.append(time.perf_counter() - t0)
+    kernel_us = 1e3 * kernel_ms / max(launches, 1)
+    ms = lambda t: round(1e3 * t, 3)
+    return {"field": field, "members": B, "calls": a.repeats, "same_numbers": True,
+            "statistics_call_ms": {"slowest": ms(max(t_dev)), "median": ms(statistics.median(t_dev))},
+            "read_rect_route_ms": {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))},
+            "speedup_slowest": round(max(t_host) / max(t_dev), 2),
+            "kernel_us": round(kernel_us, 2), "kernel_launches_timed": launches,
+            "kernel_gb_read_per_s": round(2 * 20 * X * Y * B / (kernel_us * 1e-6) / 1e9, 1) if kernel_us > 0 else None}
+
+
 def main():
     a = parse()
+    if a.statistics and (a.mode != "ensemble" or a.statistics not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--statistics BASE_CUR | WATER_CUR needs --mode ensemble")
     sys.path.insert(0, a.root)
     if a.share > 0:
         if "debug" not in os.environ.get("WXSIM_LIB", ""):
@@ -115,6 +204,11 @@ def main():
             def close():
                 for h in hs:
                     h.close()
+
+        if a.statistics:
+            out["shapes"][spec] = {"members": B, "statistics": time_statistics(a, ens, X, Y, B)}
+            close()
+            continue
 
         def frames(n):
             done = 0
