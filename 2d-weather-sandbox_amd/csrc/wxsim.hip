@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <utility>
@@ -54,11 +55,12 @@ enum KernelId {
   K_MARCH_WET,  // the whole iteration as one row-marching wavefront kernel (wx_wet.h)
   K_MARCH_DRY2, // TWO dry iterations per launch (wx_march2.h)
   K_ENS_STAT,   // per-cell statistics over the members of an ensemble (wx_ens_stat.h)
+  K_ENS_PERTURB, // smooth noise added to / multiplied into the members of an ensemble (wx_ens_perturb.h)
   K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "boundary", "advection", "pressure", "lighting",
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
-                                           "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics"};
+                                           "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -283,6 +285,10 @@ struct Storage {
   size_t arena_skew = 0;
   int arena_count = 0;
   std::vector<void **> slots;
+  // what wx_create made: two handles of one geometry agree on these blocks, their sizes and these slots (wx_copy_state); what
+  // WX_OPT_SPLAT_ORDER adds later lies behind them
+  int created_blocks = 0, created_slots = 0;
+  size_t created_small_used = 0;
   std::vector<void *> alloc_pads;          // (WX_ALLOC_PADS experiment: pads between the planes' allocations)
 };
 
@@ -1318,6 +1324,9 @@ int wx_create_slab(int X_global, int Y, int x0, int X_owned, int halo, int n_dro
     wx_destroy(s);
     return rc == WX_E_DEVICE ? WX_E_NOMEM : rc;
   }
+  s->store.created_blocks = (int)s->store.blocks.size();
+  s->store.created_slots = (int)s->store.slots.size();
+  s->store.created_small_used = s->store.small_used;
   s->p.pass_mask = WX_PASS_ALL;
   build_geo(s);
   // The allocations above were zeroed with hipMemset on the default stream, which may return before the device is done. A host that
@@ -3080,4 +3089,6 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 
 #include "wx_comm.h" // (its entry points are declared extern "C" by include/wxsim.h)
 #include "wx_ensemble.h" // (likewise)
+#include "wx_state_copy.h" // (likewise)
 #include "wx_ens_stat.h" // (likewise)
+#include "wx_ens_perturb.h" // (likewise)

@@ -44,6 +44,7 @@ EXPORTS = [
     "wx_ensemble_create", "wx_ensemble_destroy", "wx_ensemble_last_error", "wx_ensemble_count", "wx_ensemble_member", "wx_ensemble_step",
     "wx_ensemble_sync", "wx_ensemble_diagnostics", "wx_ensemble_stats", "wx_ensemble_create_droplets", "wx_ensemble_particle_stats",
     "wx_ensemble_statistics", "wx_ens_stat_cells",
+    "wx_copy_state", "wx_ensemble_broadcast", "wx_ensemble_perturb", "wx_ens_perturb_cells",
 ]
 
 
@@ -218,6 +219,63 @@ def ens_stat_cells(fields, walls, *, members=None, threshold=(0, 0, 0, 0), want=
     return planes
 
 
+class WxEnsPerturb(C.Structure):
+    """``wx_ens_perturb`` of include/wxsim.h, member for member."""
+    _fields_ = [
+        ("field", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("mode", C.c_int32), ("scale", C.c_int32),
+        ("wrap_x", C.c_int32), ("seed", C.c_uint32), ("amplitude", C.c_float * 4), ("lo", C.c_float * 4), ("hi", C.c_float * 4),
+    ]
+
+
+PERTURB_MODES = {"add": 0, "mul": 1}
+
+
+def _four(v, fill):
+    """A scalar or up to four per-channel values (None: ``fill``) as four floats."""
+    if v is None:
+        return [fill] * 4
+    a = np.asarray(v, np.float64).ravel()
+    if a.size == 1:
+        return [float(a[0])] * 4
+    if a.size != 4:
+        raise ValueError("one value or one per channel (4)")
+    return [float(x) for x in a]
+
+
+def _perturb_struct(field, amplitude, mode, scale, seed, wrap_x, rect, lo, hi) -> WxEnsPerturb:
+    p = WxEnsPerturb()
+    p.field = int(FIELD_IDS.get(field, field))
+    p.x, p.y, p.w, p.h = [int(v) for v in rect]
+    p.mode = int(PERTURB_MODES.get(mode, mode))
+    p.scale, p.wrap_x, p.seed = int(scale), 1 if wrap_x else 0, int(seed) & 0xFFFFFFFF
+    p.amplitude[:] = _four(amplitude, 0.0)
+    p.lo[:] = _four(lo, float("nan"))
+    p.hi[:] = _four(hi, float("nan"))
+    return p
+
+
+def ens_perturb_cells(fields, walls, X: int, Y: int, field, amplitude, *, mode="add", scale=1, seed=0, wrap_x=False, rect=None, members=None,
+                      lo=None, hi=None) -> list:
+    """wx_ens_perturb_cells: the perturbation kernel's per-cell function on the CPU. ``fields[i]`` / ``walls[i]``: member i's cells of the
+    rectangle ``rect`` = (x, y, w, h) (None: the whole X x Y grid), float32 (h, w, 4) and int8 (h, w, 4); an unselected member's entries
+    may be None. Returns new arrays (the selected members' perturbed, the others as given); the arguments are not changed."""
+    rect = (0, 0, int(X), int(Y)) if rect is None else tuple(int(v) for v in rect)
+    n = len(fields)
+    mask = _member_mask(n, members)
+    shape = (max(rect[3], 0), max(rect[2], 0), 4)
+    out = [None if a is None else np.array(a, np.float32, order="C") for a in fields]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    if n < 1 or len(wl) != n or any(a is not None and a.shape != shape for a in out + wl):
+        raise ValueError(f"one {shape} field and one {shape} wall array per member")
+    fp = (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in out])
+    wp = (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in wl])
+    p = _perturb_struct(field, amplitude, mode, scale, seed, wrap_x, rect, lo, hi)
+    rc = lib().wx_ens_perturb_cells(C.byref(p), int(X), int(Y), n, fp, wp, None if mask is None else mask.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_ens_perturb_cells: bad descriptor, rectangle outside the grid, or no member selected")
+    return out
+
+
 def build(force: bool = False, fast: bool = False) -> str:
     """Compile libwxsim.so (``fast``: the tolerance build libwxsim_fast.so) for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -364,6 +422,10 @@ def lib() -> C.CDLL:
     L.wx_ensemble_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.wx_ensemble_statistics.argtypes = [vp, i32, i32, i32, i32, i32, vp, C.POINTER(WxEnsStat)]
     L.wx_ens_stat_cells.argtypes = [i32, C.c_size_t, vp, vp, vp, C.POINTER(WxEnsStat)]
+    L.wx_copy_state.argtypes = [vp, vp]
+    L.wx_ensemble_broadcast.argtypes = [vp, i32, vp]
+    L.wx_ensemble_perturb.argtypes = [vp, C.POINTER(WxEnsPerturb), vp]
+    L.wx_ens_perturb_cells.argtypes = [C.POINTER(WxEnsPerturb), i32, i32, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -489,6 +551,14 @@ class Handle:
 
     def sync(self):
         self._chk(lib().wx_sync(self._h))
+
+    def copy_from(self, src: "Handle"):
+        """wx_copy_state: this handle becomes a complete device-side clone of ``src`` (same X, Y and droplet count, same device; lone
+        handles or ensemble members alike) -- every field, the droplet pool, iteration counter, parameters; the options stay this
+        handle's own. Blocks like ``sync`` on both; device pointers of this handle obtained earlier dangle."""
+        self.generation += 1
+        self._chk(lib().wx_copy_state(self._h, src._h))
+        self._stepped = self._stepped or src._stepped
 
     def tune_placement(self, tries: int = 6, iters_per_try: int = 30):
         """wx_tune_placement: try ``tries`` further device allocations for the handle's planes, keep the fastest; returns
@@ -942,6 +1012,26 @@ class Ensemble:
         mask = _member_mask(self.n, members)
         self._chk(lib().wx_ensemble_statistics(self._e, FIELD_IDS[field], int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data, C.byref(st)))
         return planes
+
+    def broadcast(self, src: int, members=None):
+        """wx_ensemble_broadcast: every selected member (None: all others) becomes a device-side clone of member ``src``
+        (``Handle.copy_from``); one wait at the end."""
+        mask = _member_mask(self.n, members)
+        for i, h in enumerate(self.members):
+            if i != int(src) and (mask is None or mask[i]):
+                h.generation += 1
+        self._chk(lib().wx_ensemble_broadcast(self._e, int(src), None if mask is None else mask.ctypes.data))
+
+    def perturb(self, field: str, amplitude, *, mode="add", scale: int = 1, seed: int = 0, wrap_x: bool = False, rect=None, members=None, lo=None, hi=None):
+        """wx_ensemble_perturb: smooth noise r in [-1, 1) -- a function of (seed, member index, channel, cell), bilinear on a lattice of
+        ``scale`` cells -- added to (``mode`` "add": v + a r) or multiplied into ("mul": v (1 + a r)) ``field`` (BASE_CUR or WATER_CUR)
+        of the selected members inside ``rect`` = (x, y, w, h) (None: the whole grid), in one launch. ``amplitude``, ``lo``, ``hi``: one
+        value or one per channel (amplitude 0: channel untouched; lo / hi None: no clamp). Wall cells and non-finite values are left
+        alone. Blocks like ``statistics``."""
+        rect = (0, 0, self.X, self.Y) if rect is None else rect
+        p = _perturb_struct(field, amplitude, mode, scale, seed, wrap_x, rect, lo, hi)
+        mask = _member_mask(self.n, members)
+        self._chk(lib().wx_ensemble_perturb(self._e, C.byref(p), None if mask is None else mask.ctypes.data))
 
     def close(self):
         if getattr(self, "_e", None):

@@ -95,6 +95,39 @@ class WeatherSim:
             sf = codec.load(sf)
         return cls(sf.X, sf.Y, sf.base, sf.water, sf.wall, sf.droplets, sf.settings, **kw)
 
+    @classmethod
+    def _on_cloned_handle(cls, handle: Handle, other: "WeatherSim") -> "WeatherSim":
+        """A ``WeatherSim`` on ``handle`` (a member of a ``WeatherEnsemble``) whose engine state ALREADY is a device-side clone of
+        ``other``'s: no upload, no host arrays -- only the host state is taken over."""
+        self = cls.__new__(cls)
+        self.X, self.Y = other.X, other.Y
+        self._h = handle
+        self.verbose = False
+        self._placement_told = True  # (members never search for a placement)
+        self._take_host_state(other)
+        return self
+
+    def _take_host_state(self, other: "WeatherSim"):
+        """What a ``WeatherSim`` keeps on the host next to its engine handle: gui, sounding, clock, sun, brush."""
+        self.gui = dict(other.gui)
+        self._quad_scale, self._pass_mask, self._manual_sun = other._quad_scale, other._pass_mask, other._manual_sun
+        self._inactive_pushed = other._inactive_pushed
+        self._sounding = getattr(other, "_sounding", None)
+        self.sim_datetime = other.sim_datetime
+        self.brush = dict(other.brush)
+        self.airplane = tuple(other.airplane)
+
+    def copy_from(self, other: "WeatherSim"):
+        """This simulation becomes ``other``'s: the engine state on the device (``Handle.copy_from``: fields, droplets, iteration counter,
+        parameters -- not the engine options) and the host state that goes with it (gui, sounding, clock, sun, brush). Both go on
+        independently afterwards."""
+        if other is self:
+            return
+        if (self.X, self.Y) != (other.X, other.Y):
+            raise ValueError(f"copy_from: {other.X} x {other.Y} into {self.X} x {self.Y}")
+        self._h.copy_from(other._h)
+        self._take_host_state(other)
+
     # ---- parameters ----
     def uniforms(self) -> Dict[str, Any]:
         u = params.uniforms_from_gui(self.gui, self.Y, sun_angle_deg=self._manual_sun, quad_scale=self._quad_scale,
@@ -262,6 +295,46 @@ class WeatherEnsemble:
         for i, m in enumerate(ens.members if n else ()):
             m.handle.init_droplets(int(droplet_seed) + i)
         return ens
+
+    @classmethod
+    def from_sim(cls, sim: WeatherSim, n_members: int, overrides: Optional[Sequence[Optional[Dict[str, Any]]]] = None) -> "WeatherEnsemble":
+        """``n_members`` members cloned ON THE DEVICE from a running ``WeatherSim`` (its spun-up state: light, curl, feedback textures,
+        lightning, droplets, iteration counter -- what an upload cannot carry), no host arrays; ``overrides[i]``: guiControls entries of
+        member i on top of the simulation's. Follow with ``perturb`` to make the members differ."""
+        from .engine import Ensemble
+        if overrides is not None and len(overrides) != n_members:
+            raise ValueError("one overrides entry per member")
+        for o in overrides or ():
+            for k in o or ():
+                if k not in params.GUI_DEFAULTS:
+                    raise KeyError(k)
+        self = cls.__new__(cls)
+        self._e = Ensemble(n_members, sim.X, sim.Y, sim.handle.n_droplets)
+        self._e[0].copy_from(sim.handle)
+        self._e.broadcast(0)
+        self.members = []
+        for i in range(n_members):
+            m = WeatherSim._on_cloned_handle(self._e[i], sim)
+            if overrides is not None and overrides[i]:
+                m.set_gui(**overrides[i])
+            self.members.append(m)
+        return self
+
+    def broadcast(self, i: int, members=None):
+        """Every selected member (None: all others) becomes member ``i``: its engine state on the device (``engine.Ensemble.broadcast``)
+        and its host state (gui, sounding, clock, sun, brush)."""
+        self._e.broadcast(i, members)
+        from .engine import _member_mask
+        mask = _member_mask(len(self.members), members)
+        src = self.members[i]
+        for k, m in enumerate(self.members):
+            if k != i and (mask is None or mask[k]):
+                m._take_host_state(src)
+
+    def perturb(self, field: str, amplitude, **kw):
+        """``engine.Ensemble.perturb``: smooth device-side noise on one field of the selected members (mode, scale, seed, wrap_x, rect,
+        members, lo, hi)."""
+        self._e.perturb(field, amplitude, **kw)
 
     def __len__(self):
         return len(self.members)

@@ -675,6 +675,87 @@ int wx_ensemble_statistics(wx_ensemble *e, int field, int x, int y, int w, int h
 int wx_ens_stat_cells(int n_members, size_t n_cells, const float *const *field, const int8_t *const *wall,
                       const uint8_t *member_mask, wx_ens_stat *out);
 
+/* ---- (ABI 11, WX_HAVE_STATE_COPY) A complete device-side clone: after wx_copy_state(dst, src) dst IS src's simulation, for everything a
+ * host can observe -- every readable WX_FIELD_* (the ones made on demand included: WATER_0, BASE_DISP, EMITTED, PRECIP_FB; CURL, both
+ * light textures, LIGHTNING), the droplet pool wx_read_particles returns, wx_get_iter, wx_diagnostics, the inactive-droplet count, the
+ * parameters and sounding arrays of the last wx_set_params -- and every later wx_step(dst, n) / wx_ensemble_step yields bit for bit what
+ * the same call on src yields (droplets: as between two runs of one handle -- the pool always, everything under WX_OPT_SPLAT_ORDER 1).
+ * wx_upload cannot do this: it resets the light textures, curl, the feedback textures, the lightning state and `even`, so a handle
+ * "uploaded from" another's wx_read_rect output diverges from the first iteration. A spun-up simulation is handed to the members of an
+ * ensemble, a fuzzer or a what-if host branches a run, a checkpoint is a second handle.
+ * Which handles: two whole-domain handles (no halo) of the same X, Y and droplet count on the same device; each a lone handle or a
+ * member of any ensemble. WX_E_INVALID: a NULL argument (answered before the device is touched), a geometry or droplet-count mismatch,
+ * a slab handle, handles on different devices. WX_E_STATE: src was never uploaded, or src has no parameters (the message says which).
+ * dst == src: WX_OK, nothing done. dst may never have been uploaded.
+ * OPTIONS ARE NOT COPIED: dst goes on under its own, as if they had been set by wx_set_option mid-run; streams, profile, placement and
+ * ensemble membership stay dst's. The counters that describe a handle's own launches -- wx_fastest_velocity, wx_pair_stats, the profile
+ * accumulators, wx_ensemble_stats -- are not state: dst's read as after a fresh upload (the profile's and the ensemble's are left
+ * alone), src's are untouched. src is unchanged in every observable respect.
+ * Ordering: the two handles may be on different streams; the copy is ordered behind everything pending on both, and the call blocks
+ * like wx_sync on both. It is a place where src's pending report (an overflowed exact-path list, ...) is consumed and returned
+ * (WX_E_STATE, on both handles' wx_last_error): then nothing is copied and dst keeps its state. Device pointers obtained from
+ * wx_device_ptr(dst, ..) before the call are invalid afterwards. A device error half-way (WX_E_DEVICE / WX_E_NOMEM) leaves dst's
+ * contents undefined until it is uploaded or copied into again.
+ * wx_ensemble_broadcast(e, src_member, member_mask): the same copy from one member to every selected other member (member_mask: one
+ * byte per member, non-zero = selected, NULL = all others; the source's own byte is ignored), enqueued on the ensemble's stream with one
+ * wait at the end (the source's pending report is looked at first, as above). Members outside the mask are untouched; wx_ensemble_stats
+ * is unchanged. WX_E_INVALID: e NULL, src_member outside the ensemble; WX_E_STATE: the source was never uploaded or has no parameters. */
+#define WX_HAVE_STATE_COPY 1
+int wx_copy_state(wx_sim *dst, wx_sim *src);
+int wx_ensemble_broadcast(wx_ensemble *e, int src_member, const uint8_t *member_mask);
+
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_PERTURB) The members of an ensemble made different in one launch: smooth pseudo-random noise added to
+ * (or multiplied into) one field of every selected member, on the device. With wx_ensemble_broadcast a perturbed ensemble starts from a
+ * spun-up state without one host array: spin up, clone, perturb, step, wx_ensemble_statistics.
+ *
+ * THE PER-CELL FUNCTION (the kernel, wx_ens_perturb_cells and the tests all evaluate this definition). All integer arithmetic is
+ * wrapping uint32, all floating-point arithmetic is double with every operation rounded separately (no fused multiply-add: contraction
+ * is off inside the function in every build, so libwxsim.so, libwxsim_fast.so, the device and the host give the same bits).
+ *   Node value. hash_u32 is the shaders' integer hash (common.glsl:103-111, the one wx_init_droplets uses). For member index i (its
+ *   index in the ensemble -- in `field` for wx_ens_perturb_cells --, not its position in the mask), channel c and lattice node (gx, gy):
+ *     h = hash_u32(gx + hash_u32(gy + hash_u32(4*i + c + hash_u32(seed))));   u = ((double)(h >> 8) - 8388608.0) / 8388608.0   in [-1, 1).
+ *   Noise at the absolute cell (x, y). gx = x / scale, gy = y / scale (integer division); tx = (double)(x - gx*scale) / (double)len,
+ *   ty = (double)(y - gy*scale) / (double)scale; len = scale and the right-hand node is gx + 1 -- except with wrap_x in the last node
+ *   interval of a row, gx == (X - 1) / scale: there len = X - gx*scale (possibly shorter) and the right-hand node is node 0, so the
+ *   noise is periodic in x with the grid's width X. The upper node is gy + 1. With u00 = u(gx, gy), u10 = u(right, gy), u01 = u(gx, gy+1),
+ *   u11 = u(right, gy+1):   r = (1-ty)*((1-tx)*u00 + tx*u10) + ty*((1-tx)*u01 + tx*u11)   -- two subtractions, six products, three sums.
+ *   Application to the value v of a channel with amplitude a.  mode 0: d = (double)v + (double)a*r.  mode 1: d = (double)v * (1.0 +
+ *   (double)a*r).  o = (float)d; then the clamp: if lo[c] is not NaN and o < lo[c], o = lo[c]; then if hi[c] is not NaN and o > hi[c],
+ *   o = hi[c]. The channel becomes o.
+ *   What is left untouched, bit for bit: every channel of a cell that is a WALL cell in that member (wx_diag's test: channel 1 of its
+ *   WX_FIELD_WALL_CUR texel is 0); a channel with a == 0; a channel whose v is not finite; a channel whose o is not finite (an overflow,
+ *   a NaN amplitude, an infinite clamp).
+ * The noise is a function of absolute coordinates, member, channel and seed only -- not of the rectangle or the mask: perturbing two
+ * disjoint rectangles equals perturbing their union, and a member's noise is the same whoever else is selected.
+ *
+ * wx_ensemble_perturb: WX_E_INVALID: e or p NULL, a field other than WX_FIELD_BASE_CUR / WX_FIELD_WATER_CUR, mode not 0 or 1, scale < 1,
+ * nobody selected; WX_E_RANGE: the rectangle does not lie inside the grid (no wrap); WX_E_STATE: a selected member was never uploaded
+ * (the message names it). These checks answer before the device is touched; member_mask as for wx_ensemble_statistics. To a member's
+ * bookkeeping the perturbation is a host write through wx_device_ptr: a lazy WX_FIELD_BASE_DISP is assembled whole first and a pending
+ * WX_FIELD_WATER_0 is made first (the display-side fields keep showing the last display iteration), velocities written are looked at by
+ * the next |vx| scan, and a perturbed water field is no longer known to be water-free (wx_water_free: 0; the water-free dry kernel
+ * does not run on it). The launch is enqueued on the ensemble's stream behind everything pending, and the call then BLOCKS like
+ * wx_ensemble_statistics and, like it, consumes and returns a member's pending report ("member i: ..."; the perturbation has been
+ * applied by then). wx_profile on member 0 times the launch (kernel name "ensemble_perturb"). The kernel takes one lane per cell and
+ * member: 36 B per member-cell, DESIGN.md section 4.
+ * wx_ens_perturb_cells (host only, pure): the same function over cells the caller holds -- member i's w*h cells of the rectangle
+ * (p->x, p->y, p->w, p->h) of an X x Y grid at field[i] (4 floats per cell, rows bottom-up, changed in place) and wall[i] (4 bytes per
+ * cell). WX_E_INVALID / WX_E_RANGE as above, and for n_members < 1, a NULL table, a NULL entry of a selected member. */
+#define WX_HAVE_ENSEMBLE_PERTURB 1
+typedef struct wx_ens_perturb {
+  int32_t  field;          /* WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR (the fields wx_ensemble_statistics reads) */
+  int32_t  x, y, w, h;     /* rectangle inside the grid, no wrap (WX_E_RANGE) */
+  int32_t  mode;           /* 0: v + a*r     1: v * (1 + a*r) */
+  int32_t  scale;          /* >= 1: lattice pitch of the noise in cells; 1 = white noise */
+  int32_t  wrap_x;         /* the noise is periodic across x = 0 (for wrapHorizontally domains) */
+  uint32_t seed;
+  float    amplitude[4];   /* per channel; 0: the channel's bits are not touched */
+  float    lo[4], hi[4];   /* clamp of the result; NaN: none */
+} wx_ens_perturb;
+int wx_ensemble_perturb(wx_ensemble *e, const wx_ens_perturb *p, const uint8_t *member_mask /* n_members bytes, NULL = all */);
+int wx_ens_perturb_cells(const wx_ens_perturb *p, int X, int Y, int n_members, float *const *field, const int8_t *const *wall,
+                         const uint8_t *member_mask);
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

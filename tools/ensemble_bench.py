@@ -19,6 +19,13 @@ whole grid costs (all nine planes, host to host: the call blocks) against the ro
 WALL_CUR plus the same arithmetic in numpy, member by member in member order as include/wxsim.h defines it -- after --frame iterations;
 --repeats calls of each, the slowest and the median reported under the shape's "statistics" key, with the kernel's own time (wx_profile
 on member 0) and the bytes it reads per second (members x 20 B per cell and pass, two passes).
+--spawn (--mode ensemble): B members made from ONE stepped state (a lone handle after --frame x 5 iterations), timed two ways, host to
+host, --repeats times each: route A = wx_copy_state into member 0 + wx_ensemble_broadcast + ONE wx_ensemble_perturb (temperature, lattice
+pitch 8); route B = what a host did before -- B wx_upload calls of host arrays (the state read back once, untimed; per member numpy noise
+on the temperature of the air cells, timed). Route B does NOT make the same ensemble: an upload cannot carry the light textures, curl,
+feedback textures, lightning state and `even`, so its members are not the stepped simulation (the record says so: "route_b_carries_the_
+state": false). The shape's "spawn" key also holds the perturbation kernel's own time (wx_profile on member 0) against its 36 B per
+member-cell at --peak-gbs.
 --share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
 import argparse
 import json
@@ -41,6 +48,7 @@ def parse():
     ap.add_argument("--peak-gbs", type=float, default=8000.0, help="what the roofline fraction is quoted against [GB/s]: bench.py's HBM_PEAK_GBS")
     ap.add_argument("--droplets", type=int, default=0, help="droplets per member (0: none, precipitation off)")
     ap.add_argument("--statistics", default="", metavar="FIELD", help="time one statistics call over the whole grid against B read_rect calls + numpy (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     return ap.parse_args()
@@ -167,8 +175,67 @@ def time_statistics(a, ens, X, Y, B):
             "kernel_gb_read_per_s": round(2 * 20 * X * Y * B / (kernel_us * 1e-6) / 1e9, 1) if kernel_us > 0 else None}
 
 
+def time_spawn(a, pkg, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    E = pkg.engine
+    lone = make_members(pkg, X, Y, 1, lambda i: E.Handle(X, Y, a.droplets), a.flow, a.droplets)[0]
+    lone.step(5 * a.frame)
+    lone.sync()
+    amp, scale = (0.0, 0.0, 0.0, 0.5), 8
+
+    def route_a(seed):
+        ens[0].copy_from(lone)
+        ens.broadcast(0)
+        ens.perturb("BASE_CUR", amp, scale=scale, seed=seed)
+
+    base, water, wall = lone.read_rect("BASE_CUR"), lone.read_rect("WATER_CUR"), lone.read_rect("WALL_CUR")
+    drops = lone.read_particles() if a.droplets else None
+    air = wall[..., 1] != 0
+    rng = np.random.default_rng(1)
+
+    def route_b(seed):
+        for i in range(B):
+            b = base.copy()
+            b[..., 3] += np.where(air, rng.uniform(-amp[3], amp[3], air.shape), 0).astype(np.float32)
+            ens[i].upload(b, water, wall, drops)
+
+    route_a(0)
+    for i in range(B):  # every member shows the stepped state (route B below does not: see the docstring)
+        if ens[i].iter != lone.iter or not np.array_equal(ens[i].read_rect("LIGHT_0"), lone.read_rect("LIGHT_0")):
+            sys.exit("--spawn %dx%dx%d: member %d is not a clone of the stepped handle" % (X, Y, B, i))
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        route_a(0)
+    ens[0].profile(True)
+    t_a, t_b = [], []
+    for k in range(a.repeats):
+        t0 = time.perf_counter()
+        route_a(1 + k)
+        t_a.append(time.perf_counter() - t0)
+    kernel_ms, launches = ens[0].profile_read().get("ensemble_perturb", (0.0, 0))
+    ens[0].profile(False)
+    for k in range(a.repeats):
+        t0 = time.perf_counter()
+        route_b(1 + k)
+        t_b.append(time.perf_counter() - t0)
+    lone.close()
+    kernel_us = 1e3 * kernel_ms / max(launches, 1)
+    gbs = 36 * X * Y * B / (kernel_us * 1e-6) / 1e9 if kernel_us > 0 else None
+    ms = lambda t: round(1e3 * t, 3)
+    return {"members": B, "calls": a.repeats, "perturbed": "BASE_CUR temperature, amplitude 0.5, scale 8",
+            "route_a_broadcast_perturb_ms": {"slowest": ms(max(t_a)), "median": ms(statistics.median(t_a))},
+            "route_b_uploads_ms": {"slowest": ms(max(t_b)), "median": ms(statistics.median(t_b))},
+            "speedup_slowest": round(max(t_b) / max(t_a), 2), "route_b_carries_the_state": False,
+            "route_b_loses": "light textures, curl, feedback textures, lightning state, `even`: its members are fresh uploads, not the stepped simulation",
+            "perturb_kernel_us": round(kernel_us, 2), "kernel_launches_timed": launches, "kernel_bytes": 36 * X * Y * B,
+            "kernel_gb_per_s": round(gbs, 1) if gbs else None, "kernel_fraction_of_peak": round(gbs / a.peak_gbs, 4) if gbs else None}
+
+
 def main():
     a = parse()
+    if a.spawn and a.mode != "ensemble":
+        sys.exit("--spawn needs --mode ensemble")
     if a.statistics and (a.mode != "ensemble" or a.statistics not in ("BASE_CUR", "WATER_CUR")):
         sys.exit("--statistics BASE_CUR | WATER_CUR needs --mode ensemble")
     sys.path.insert(0, a.root)
@@ -186,6 +253,11 @@ def main():
            "shapes": {}}
     for spec in a.shapes.split(","):
         X, Y, B = (int(v) for v in spec.split("x"))
+        if a.spawn:
+            ens = E.Ensemble(B, X, Y, a.droplets)
+            out["shapes"][spec] = {"members": B, "spawn": time_spawn(a, pkg, ens, X, Y, B)}
+            ens.close()
+            continue
         if a.mode == "ensemble":
             ens = E.Ensemble(B, X, Y, a.droplets) if a.droplets else E.Ensemble(B, X, Y)
             make_members(pkg, X, Y, B, lambda i: ens[i], a.flow, a.droplets)

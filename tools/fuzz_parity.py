@@ -92,6 +92,38 @@ def draw_surface(c):
     return c
 
 
+# Clone mid-run (wx_copy_state): after one of the case's steps the handle is copied into a SECOND handle with options of its own, both go
+# on with the same calls, and the second is compared with the first after every further step -- bit for bit (droplets run under
+# WX_OPT_SPLAT_ORDER 1 on both). Drawn like draw_more_sliders, as a function of the case (recipe key "clone"; recipes without it run as
+# they always did).
+def draw_clone(c):
+    """Adds c["clone"]: None, or {"after_step": index into c["steps"], "pairs" / "bands" / "water0_on_demand": the second handle's own
+    options, "used": whether the second handle holds another state before the copy}. No draw from the case's generator."""
+    r = np.random.default_rng([int(c["data_seed"]) & 0x7FFFFFFF, 0xC10E])
+    c["clone"] = None
+    if r.random() < 0.5:
+        c["clone"] = {"after_step": int(r.integers(0, len(c["steps"]))), "pairs": int(r.random() < 0.7), "bands": int(r.choice([0, 1, 2])),
+                      "water0_on_demand": int(r.random() < 0.7), "used": bool(r.random() < 0.5)}
+    return c
+
+
+CLONE_FIELDS = ["BASE_CUR", "BASE_DISP", "WATER_0", "WATER_CUR", "WALL_CUR", "WALL_DISP", "LIGHT_0", "LIGHT_1", "CURL", "PRECIP_FB", "PRECIP_DEP", "LIGHTNING", "EMITTED"]
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f")
+
+
+def compare_clone(h2, h, nd, done):
+    """Mismatches between a clone and the handle it was copied from, after the same calls."""
+    bad = [{"field": "clone:" + f, "after_iterations": done} for f in CLONE_FIELDS if not _same_bits(h2.read_rect(f), h.read_rect(f))]
+    if nd and not _same_bits(h2.read_particles(), h.read_particles()):
+        bad.append({"field": "clone:DROPS", "after_iterations": done})
+    if h2.iter != h.iter:
+        bad.append({"field": "clone:iter", "after_iterations": done})
+    return bad
+
+
 def case_iter0(c):
     it0 = (c.get("surface") or {}).get("iter0")
     return c["iter0"] if it0 is None else it0
@@ -245,6 +277,7 @@ def case_steps(pkg, E, wx_oracle, c):
     h = E.Handle(X, Y, nd)
     o = wx_oracle.OracleSim(X, Y, nd)
     bad = []
+    cl, h2 = c.get("clone"), None
     try:
         h.upload(base, water, wall, drops)
         o.upload(base, water, wall, drops)
@@ -263,11 +296,13 @@ def case_steps(pkg, E, wx_oracle, c):
         for k_step, n in enumerate(c["steps"]):
             if c.get("brush_toggle") and c["brush"] and k_step > 0:  # mouse up / down between two steps: new parameters on both sides
                 u2 = dict(u, userInputType=(c["brush"]["type"] if k_step % 2 == 0 else -1))
-                h.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u2), u["initial_T"])
+                for hh_ in (h, h2) if h2 is not None else (h,):  # (a clone is given every call its source is given)
+                    hh_.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u2), u["initial_T"])
                 o.set_params(u2)
             if c.get("reupload") and k_step == 1 and not nd:
                 st = [o.field(f) for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR")]
-                h.upload(*st)
+                for hh_ in (h, h2) if h2 is not None else (h,):
+                    hh_.upload(*st)
                 o.upload(*st)
             pieces = [n]
             if c.get("pieces") and n > 1:  # the step cut into pieces whose all but the last skip the display-side stores (WX_OVERLAP_MORE_TO_COME)
@@ -275,8 +310,27 @@ def case_steps(pkg, E, wx_oracle, c):
                 pieces = [k1, n - k1]
             for i_p, k_p in enumerate(pieces):
                 h.step(k_p, 4 if i_p + 1 < len(pieces) else 0)
+                if h2 is not None:
+                    h2.step(k_p, 4 if i_p + 1 < len(pieces) else 0)
             o.step(n)
             yield
+            if h2 is not None:
+                bad += compare_clone(h2, h, nd, h.iter - case_iter0(c))
+            if cl and k_step == cl["after_step"] and h2 is None:  # the clone: a second handle under its own options, possibly holding an older state
+                h2 = E.Handle(X, Y, nd)
+                h2.set_option(h2.OPT_DRY_PAIRS, cl["pairs"])
+                h2.set_option(h2.OPT_ROW_BANDS, cl["bands"])
+                h2.set_option(h2.OPT_WATER0_ON_DEMAND, cl["water0_on_demand"])
+                h2.set_option(h2.OPT_KERNEL_SET, c["kernel_set"])  # (VORT and the dry kernels' stale fields differ between the kernel sets: the same one)
+                h2.set_option(h2.OPT_DRY_KERNEL, c["dry_kernel"])
+                if nd:
+                    h2.set_option(h2.OPT_SPLAT_ORDER, 1)
+                if cl["used"]:
+                    h2.upload(base, water, wall, drops)
+                    h2.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"])
+                    h2.step(3)
+                h2.copy_from(h)
+                bad += compare_clone(h2, h, nd, h.iter - case_iter0(c))
             if not c["dry"] and not np.array_equal(h.read_rect("CURL"), o.field("CURL"), equal_nan=True):
                 bad.append({"field": "CURL", "after_iterations": h.iter - case_iter0(c)})
             if c.get("subrect"):
@@ -311,6 +365,8 @@ def case_steps(pkg, E, wx_oracle, c):
     finally:
         h.close()
         o.close()
+        if h2 is not None:
+            h2.close()
     return bad, info
 
 
@@ -936,7 +992,7 @@ def main():
         print(json.dumps({"mode": a.mode, "seed": a.seed, "cases_run": ran, "mismatching_cases": n_bad, "seconds": round(time.time() - t0, 1)}))
         sys.exit(1 if n_bad else 0)
     for k in range(a.cases):
-        c = draw_surface(draw_more_sliders(draw_case(rng, a.max_cells, a.big)))
+        c = draw_clone(draw_surface(draw_more_sliders(draw_case(rng, a.max_cells, a.big))))
         if a.mode == "group":
             c = draw_group(rng, c)
         if a.mode == "script":
