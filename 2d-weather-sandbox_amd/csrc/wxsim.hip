@@ -56,11 +56,13 @@ enum KernelId {
   K_MARCH_DRY2, // TWO dry iterations per launch (wx_march2.h)
   K_ENS_STAT,   // per-cell statistics over the members of an ensemble (wx_ens_stat.h)
   K_ENS_PERTURB, // smooth noise added to / multiplied into the members of an ensemble (wx_ens_perturb.h)
+  K_ENS_QUANT,  // per-cell quantiles and ranks over the members of an ensemble (wx_ens_quant.h)
   K_COUNT
 };
 const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "boundary", "advection", "pressure", "lighting",
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
-                                           "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb"};
+                                           "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb",
+                                           "ensemble_quantiles"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -3092,3 +3094,4 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 #include "wx_state_copy.h" // (likewise)
 #include "wx_ens_stat.h" // (likewise)
 #include "wx_ens_perturb.h" // (likewise)
+#include "wx_ens_quant.h" // (likewise)

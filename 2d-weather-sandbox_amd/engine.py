@@ -45,6 +45,7 @@ EXPORTS = [
     "wx_ensemble_sync", "wx_ensemble_diagnostics", "wx_ensemble_stats", "wx_ensemble_create_droplets", "wx_ensemble_particle_stats",
     "wx_ensemble_statistics", "wx_ens_stat_cells",
     "wx_copy_state", "wx_ensemble_broadcast", "wx_ensemble_perturb", "wx_ens_perturb_cells",
+    "wx_ensemble_quantiles", "wx_ens_quant_cells", "wx_ens_quant_staged_members",
 ]
 
 
@@ -276,6 +277,76 @@ def ens_perturb_cells(fields, walls, X: int, Y: int, field, amplitude, *, mode="
     return out
 
 
+ENS_QUANT_MAX = 8
+QUANT_INTERP = {"linear": 0, "lower": 1, "higher": 2}
+
+
+class WxEnsQuant(C.Structure):
+    """``wx_ens_quant`` of include/wxsim.h, member for member: what is asked for and the caller-owned output planes (NULL = not wanted)."""
+    _fields_ = [
+        ("n_q", C.c_int32), ("interp", C.c_int32), ("p", C.c_float * ENS_QUANT_MAX), ("rank_member", C.c_int32),
+        ("q", C.c_void_p), ("count", C.c_void_p), ("n_wall", C.c_void_p), ("n_below", C.c_void_p), ("n_equal", C.c_void_p),
+    ]
+
+
+# the planes of wx_ens_quant: name, element type, channels per cell (q: n_q planes in front)
+ENS_QUANT_PLANES = (("q", np.float32, 4), ("count", np.int32, 4), ("n_wall", np.int32, 1), ("n_below", np.int32, 4), ("n_equal", np.int32, 4))
+ENS_QUANT_ALL = tuple(name for name, _, _ in ENS_QUANT_PLANES)
+
+
+def _ens_quant_struct(shape, p, interp, rank_of, want):
+    """A wx_ens_quant over fresh arrays of ``shape`` + (4,) (q: (n_q,) + ``shape`` + (4,); n_wall: ``shape``) for the planes named in
+    ``want`` (None: all that make sense -- n_below / n_equal only with ``rank_of``), and those arrays by name."""
+    if want is None:
+        want = tuple(k for k in ENS_QUANT_ALL if rank_of is not None or k not in ("n_below", "n_equal"))
+    unknown = set(want) - set(ENS_QUANT_ALL)
+    if unknown:
+        raise KeyError(f"no such plane of wx_ens_quant: {sorted(unknown)} (there are {ENS_QUANT_ALL})")
+    ps = [float(v) for v in np.asarray(p, np.float32).ravel()]
+    if len(ps) > ENS_QUANT_MAX:
+        raise ValueError(f"at most {ENS_QUANT_MAX} quantiles per call")
+    st, planes = WxEnsQuant(), {}
+    st.n_q = len(ps) if "q" in want else 0
+    st.interp = int(QUANT_INTERP.get(interp, interp))
+    st.p[:len(ps)] = ps
+    st.rank_member = -1 if rank_of is None else int(rank_of)
+    for name, dt, ch in ENS_QUANT_PLANES:
+        if name in want:
+            planes[name] = np.zeros(((st.n_q,) if name == "q" else ()) + tuple(shape) + ((ch,) if ch > 1 else ()), dt)
+            setattr(st, name, planes[name].ctypes.data)
+    return st, planes
+
+
+def _quant_mask(n: int, members, rank_of) -> Optional[np.ndarray]:
+    """The member mask of a quantile call: with ``rank_of`` and no ``members`` the selection is everybody but the ranked member."""
+    if members is None and rank_of is not None and 0 <= int(rank_of) < n:
+        mask = np.ones(n, np.uint8)
+        mask[int(rank_of)] = 0
+        return mask
+    return _member_mask(n, members)
+
+
+def ens_quant_cells(fields, walls, p, *, members=None, interp="linear", rank_of=None, want=None) -> dict:
+    """wx_ens_quant_cells: the quantile kernels' per-cell function on the CPU. ``fields[i]`` / ``walls[i]``: member i's cells, float32
+    (..., 4) and int8 (..., 4) of one common shape (what ``read_rect`` returns; an unselected member's entries may be None); ``p``: up
+    to 8 quantiles in [0, 1]. Returns ``q`` (n_q, ..., 4), ``count``, ``n_wall`` and -- with ``rank_of`` -- ``n_below``, ``n_equal``."""
+    f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in fields]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    n = len(f)
+    have = [a for a in f + wl if a is not None]
+    if n < 1 or len(wl) != n or not have or any(a.shape != have[0].shape or a.shape[-1:] != (4,) for a in have):
+        raise ValueError("one (..., 4) field and one (..., 4) wall array per member, all of one shape")
+    shape = have[0].shape[:-1]
+    st, planes = _ens_quant_struct(shape, p, interp, rank_of, want)
+    fp = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in f])
+    wp = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in wl])
+    mask = _quant_mask(n, members, rank_of)
+    rc = lib().wx_ens_quant_cells(n, int(np.prod(shape, dtype=np.int64)), fp, wp, None if mask is None else mask.ctypes.data, C.byref(st))
+    if rc != 0:
+        raise WxError(rc, "wx_ens_quant_cells: bad quantiles, interpolation or rank member, an absent member, or no member selected")
+    return planes
+
+
 def build(force: bool = False, fast: bool = False) -> str:
     """Compile libwxsim.so (``fast``: the tolerance build libwxsim_fast.so) for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -426,6 +497,10 @@ def lib() -> C.CDLL:
     L.wx_ensemble_broadcast.argtypes = [vp, i32, vp]
     L.wx_ensemble_perturb.argtypes = [vp, C.POINTER(WxEnsPerturb), vp]
     L.wx_ens_perturb_cells.argtypes = [C.POINTER(WxEnsPerturb), i32, i32, i32, vp, vp, vp]
+    L.wx_ensemble_quantiles.argtypes = [vp, i32, i32, i32, i32, i32, vp, C.POINTER(WxEnsQuant)]
+    L.wx_ens_quant_cells.argtypes = [i32, C.c_size_t, vp, vp, vp, C.POINTER(WxEnsQuant)]
+    L.wx_ens_quant_staged_members.argtypes = []
+    L.wx_ens_quant_staged_members.restype = i32
     _lib = L
     return L
 
@@ -1011,6 +1086,22 @@ class Ensemble:
         st, planes = _ens_stat_struct((max(h, 0), max(w, 0)), threshold, want)
         mask = _member_mask(self.n, members)
         self._chk(lib().wx_ensemble_statistics(self._e, FIELD_IDS[field], int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data, C.byref(st)))
+        return planes
+
+    QUANT_STAGED_MEMBERS = 64  # wx_ens_quant_staged_members(): the largest selection the LDS path of ``quantiles`` takes
+
+    def quantiles(self, field: str, p, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, *, members=None,
+                  interp="linear", rank_of=None, want=None) -> dict:
+        """wx_ensemble_quantiles: per cell of the rectangle, over the selected members, the quantiles ``p`` (up to 8 numbers in [0, 1];
+        ``interp`` "linear", "lower" or "higher") as ``q`` (n_q, h, w, 4) float32, ``count`` (h, w, 4) and ``n_wall`` (h, w); with
+        ``rank_of`` = r, a member outside the selection (``members`` None: everybody but r), also ``n_below`` / ``n_equal`` (h, w, 4):
+        how many entered values lie below / equal member r's (-1 where r's cell is wall or its value not finite). ``want``: the planes
+        to compute (default: all of these). ``field``: BASE_CUR or WATER_CUR. One launch on the device; blocks like ``sync``."""
+        w = self.X - x if w is None else w
+        h = self.Y - y if h is None else h
+        st, planes = _ens_quant_struct((max(h, 0), max(w, 0)), p, interp, rank_of, want)
+        mask = _quant_mask(self.n, members, rank_of)
+        self._chk(lib().wx_ensemble_quantiles(self._e, FIELD_IDS[field], int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data, C.byref(st)))
         return planes
 
     def broadcast(self, src: int, members=None):

@@ -376,6 +376,15 @@ class WeatherEnsemble:
             out["probability"] = np.where(n > 0, out["n_above"].astype(np.float64) / n, np.nan)
         return out
 
+    def quantiles(self, field: str, p, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, **kw) -> dict:
+        """``engine.Ensemble.quantiles`` over the members: ``q`` (n_q, h, w, 4), ``count``, ``n_wall`` and, with ``rank_of``, ``n_below`` /
+        ``n_equal`` (members, interp, rank_of, want)."""
+        return self._e.quantiles(field, p, x, y, w, h, **kw)
+
+    def median(self, field: str, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, **kw) -> np.ndarray:
+        """The per-cell median over the members, (h, w, 4): ``quantiles(field, (0.5,))["q"][0]``."""
+        return self.quantiles(field, (0.5,), x, y, w, h, **kw)["q"][0]
+
     @property
     def engine(self):
         return self._e

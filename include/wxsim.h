@@ -756,6 +756,64 @@ int wx_ensemble_perturb(wx_ensemble *e, const wx_ens_perturb *p, const uint8_t *
 int wx_ens_perturb_cells(const wx_ens_perturb *p, int X, int Y, int n_members, float *const *field, const int8_t *const *wall,
                          const uint8_t *member_mask);
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_QUANTILES) Order statistics over the members: per cell of a rectangle up to WX_ENS_QUANT_MAX quantiles
+ * of the members' values -- the median, the 10 / 90 % band, the inter-quartile range -- and the RANK of one member's value among the
+ * others' (rank histograms, spread-skill), computed on the device in one launch. A call of its own next to wx_ensemble_statistics:
+ * wx_ens_stat and its planes are unchanged.
+ *
+ * THE PER-CELL FUNCTION (the kernels, wx_ens_quant_cells and the tests all evaluate this definition). For cell (x, y) and channel c:
+ *   Which values enter. Exactly as in wx_ensemble_statistics: a selected member in which the cell is a WALL cell (channel 1 of its
+ *   WX_FIELD_WALL_CUR texel is 0) counts into n_wall and contributes nothing; of the remaining values the FINITE ones enter, and
+ *   `count` = n counts them. An entered -0.0 is taken as +0.0. v(0) <= v(1) <= ... <= v(n-1) are the entered values in ascending order.
+ *   Quantile p (a float in [0, 1]). h = (double)p * (double)(n - 1), one rounded product; k = floor(h), g = h - k (exact),
+ *   k1 = min(k + 1, n - 1).
+ *     WX_QUANT_LOWER:  v(k).
+ *     WX_QUANT_HIGHER: g > 0 ? v(k1) : v(k).
+ *     WX_QUANT_LINEAR: (float)((double)v(k) + g * ((double)v(k1) - (double)v(k))) -- the difference, the product and the sum are
+ *     rounded to double separately (no fused multiply-add: contraction is off inside the function in every build, so libwxsim.so,
+ *     libwxsim_fast.so, the device and the host give the same bits), the conversion to float happens once. This is not numpy's lerp.
+ *     n = 0: NaN.
+ *   Rank. t = the value of member `rank_member` in that cell and channel. If the cell is a wall cell in that member, or t is not
+ *   finite: n_below = n_equal = -1. Otherwise n_below = the number of entered values with v < t, n_equal = the number with v == t
+ *   (float compare: -0.0 == 0.0). Rank histograms and the breaking of ties are left to the host: integers are exact.
+ * NO SUM IN MEMBER ORDER OCCURS ANYWHERE: unlike wx_ensemble_statistics the result does not depend on the order of the members --
+ * the same members uploaded in another order give the same bits.
+ *
+ * wx_ensemble_quantiles. Answered before the device is touched -- WX_E_INVALID: e or out NULL; a field other than WX_FIELD_BASE_CUR /
+ * WX_FIELD_WATER_CUR; n_q outside 0 .. WX_ENS_QUANT_MAX; n_q > 0 with q == NULL; a p that is NaN or outside [0, 1]; an unknown interp;
+ * nobody selected; rank_member outside the ensemble (other than -1) or selected by the mask (the ranked member does not enter: mask it
+ * out); n_below or n_equal non-NULL with rank_member == -1. WX_E_RANGE: the rectangle does not lie inside the grid (no wrap).
+ * WX_E_STATE: a selected member, or rank_member, was never uploaded (the message names it). Everything else as for
+ * wx_ensemble_statistics: member_mask has one byte per member (NULL = all), the work is enqueued on the ensemble's stream behind
+ * everything pending with the members' pointers taken at the time of the call, the call then BLOCKS like wx_ensemble_sync and consumes
+ * and returns a member's pending report ("member i: ..."), it changes nothing, its device buffers belong to the ensemble and go with
+ * wx_ensemble_destroy, and wx_profile on member 0 times the launch (kernel name "ensemble_quantiles"). Up to
+ * wx_ens_quant_staged_members() selected members the kernel reads every member once, through LDS, and sorts in registers; beyond that
+ * (up to all 65535) a streaming kernel selects the order statistics in 33 passes over the members: slow, correct.
+ * wx_ens_quant_cells (host only, pure): the same function over n_cells cells the caller holds, member i's cells at field[i] (4 floats
+ * per cell) / wall[i] (4 bytes per cell), rank_member an index into these tables; outputs as above with w*h = n_cells. WX_E_INVALID
+ * as above, and for n_members < 1, a NULL table or output struct, a NULL entry of a selected member or of rank_member. */
+#define WX_HAVE_ENSEMBLE_QUANTILES 1
+#define WX_ENS_QUANT_MAX 8
+#define WX_QUANT_LINEAR 0
+#define WX_QUANT_LOWER  1
+#define WX_QUANT_HIGHER 2
+typedef struct wx_ens_quant {
+  int32_t  n_q;                    /* 0 .. WX_ENS_QUANT_MAX */
+  int32_t  interp;                 /* WX_QUANT_* */
+  float    p[WX_ENS_QUANT_MAX];    /* each finite, in [0, 1] */
+  int32_t  rank_member;            /* -1: none; else a member that is NOT selected */
+  float   *q;                      /* n_q planes of w*h*4, plane j = quantile p[j]; NULL: not wanted */
+  int32_t *count;                  /* w*h*4, as wx_ens_stat.count */
+  int32_t *n_wall;                 /* w*h,   as wx_ens_stat.n_wall */
+  int32_t *n_below, *n_equal;      /* w*h*4, only with rank_member >= 0 */
+} wx_ens_quant;
+int wx_ensemble_quantiles(wx_ensemble *e, int field, int x, int y, int w, int h,
+                          const uint8_t *member_mask /* n_members bytes, NULL = all */, wx_ens_quant *out);
+int wx_ens_quant_cells(int n_members, size_t n_cells, const float *const *field, const int8_t *const *wall,
+                       const uint8_t *member_mask, wx_ens_quant *out);
+int wx_ens_quant_staged_members(void);  /* largest number of selected members the LDS path takes */
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

@@ -19,6 +19,12 @@ whole grid costs (all nine planes, host to host: the call blocks) against the ro
 WALL_CUR plus the same arithmetic in numpy, member by member in member order as include/wxsim.h defines it -- after --frame iterations;
 --repeats calls of each, the slowest and the median reported under the shape's "statistics" key, with the kernel's own time (wx_profile
 on member 0) and the bytes it reads per second (members x 20 B per cell and pass, two passes).
+--quantiles FIELD (BASE_CUR or WATER_CUR; --mode ensemble): what ONE wx_ensemble_quantiles call over the whole grid costs (p = 0.1, 0.5,
+0.9, linear, with count and n_wall; host to host) against the route it replaces -- B read_rect pairs, np.sort along the member axis
+and the definition's arithmetic in numpy -- after --frame iterations, --repeats calls of each; under the shape's "quantiles" key with
+the kernel's own time (wx_profile on member 0) and, from the same run, the time of the ensemble_statistics kernel with the variance
+wanted (two passes over the members). Without --shapes: the two shapes the statistics were measured at and one on the streaming path
+(more members than wx_ens_quant_staged_members()): 100x100x64, 2500x300x8, 100x100x96.
 --spawn (--mode ensemble): B members made from ONE stepped state (a lone handle after --frame x 5 iterations), timed two ways, host to
 host, --repeats times each: route A = wx_copy_state into member 0 + wx_ensemble_broadcast + ONE wx_ensemble_perturb (temperature, lattice
 pitch 8); route B = what a host did before -- B wx_upload calls of host arrays (the state read back once, untimed; per member numpy noise
@@ -40,7 +46,7 @@ def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["ensemble", "handles"], default="ensemble")
     ap.add_argument("--root", default=ROOT, help="checkout to load the package and the library from (the parent commit for the baseline)")
-    ap.add_argument("--shapes", default="100x100x64,2500x300x8,16000x500x2")
+    ap.add_argument("--shapes", default=None, help="XxYxB,... (default 100x100x64,2500x300x8,16000x500x2; with --quantiles 100x100x64,2500x300x8,100x100x96)")
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--frame", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
@@ -48,10 +54,14 @@ def parse():
     ap.add_argument("--peak-gbs", type=float, default=8000.0, help="what the roofline fraction is quoted against [GB/s]: bench.py's HBM_PEAK_GBS")
     ap.add_argument("--droplets", type=int, default=0, help="droplets per member (0: none, precipitation off)")
     ap.add_argument("--statistics", default="", metavar="FIELD", help="time one statistics call over the whole grid against B read_rect calls + numpy (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--quantiles", default="", metavar="FIELD", help="time one quantile call over the whole grid against B read_rect calls + np.sort (BASE_CUR or WATER_CUR)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.shapes is None:
+        a.shapes = "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x64,2500x300x8,16000x500x2"
+    return a
 
 
 def make_members(pkg, X, Y, B, make, flow=0.2, droplets=0):
@@ -175,6 +185,84 @@ def time_statistics(a, ens, X, Y, B):
             "kernel_gb_read_per_s": round(2 * 20 * X * Y * B / (kernel_us * 1e-6) / 1e9, 1) if kernel_us > 0 else None}
 
 
+QUANTILES_P = (0.1, 0.5, 0.9)
+
+
+def numpy_quantiles(fields, walls, p):
+    """The per-cell function of include/wxsim.h (WX_QUANT_LINEAR) in numpy: np.sort along the member axis, then the definition's float64
+    arithmetic, one operation per rounded operation (what a host does today)."""
+    import numpy as np
+    v = np.stack(fields)
+    is_wall = np.stack([wl[..., 1] == 0 for wl in walls])
+    take = ~is_wall[..., None] & np.isfinite(v)
+    n = take.sum(0).astype(np.int32)
+    with np.errstate(all="ignore"):
+        s = np.sort(np.where(take, np.where(v == 0, np.float32(0), v), np.float32(np.inf)), axis=0)
+        q = []
+        for pj in p:
+            h = np.float64(np.float32(pj)) * (n - 1).astype(np.float64)
+            k = np.floor(h)
+            g = h - k
+            ki = np.clip(k.astype(np.int64), 0, None)
+            k1 = np.clip(np.minimum(ki + 1, n - 1), 0, None)
+            vk, vk1 = np.take_along_axis(s, ki[None], 0)[0].astype(np.float64), np.take_along_axis(s, k1[None], 0)[0].astype(np.float64)
+            d = vk1 - vk
+            gd = g * d
+            q.append(np.where(n > 0, (vk + gd).astype(np.float32), np.float32(np.nan)))
+    return {"q": np.stack(q), "count": n, "n_wall": is_wall.sum(0).astype(np.int32)}
+
+
+def time_quantiles(a, pkg, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    field, p = a.quantiles, QUANTILES_P
+    staged = B <= pkg.engine.lib().wx_ens_quant_staged_members()
+
+    def device():
+        return ens.quantiles(field, p)
+
+    def reads():
+        return [m.read_rect(field) for m in ens.members], [m.read_rect("WALL_CUR") for m in ens.members]
+
+    ens.step(a.frame)
+    ens.sync()
+    got, want = device(), numpy_quantiles(*reads(), p)
+    differ = [k for k in want if not np.array_equal(got[k], want[k], equal_nan=got[k].dtype.kind == "f")]
+    if differ:  # two routes that disagree are not two timings of one thing
+        sys.exit("--quantiles %s %dx%dx%d: wx_ensemble_quantiles and the read_rect route disagree in %s" % (field, X, Y, B, ", ".join(differ)))
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        device()
+    ens[0].profile(True)
+    t_dev, t_read, t_host = [], [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        device()
+        t_dev.append(time.perf_counter() - t0)
+    kernel_ms, launches = ens[0].profile_read().get("ensemble_quantiles", (0.0, 0))
+    for _ in range(a.repeats):  # the comparison: k_ens_stat with the variance wanted reads every member twice
+        ens.statistics(field, want=("mean", "variance", "count", "n_wall"))
+    stat_ms, stat_launches = ens[0].profile_read().get("ensemble_statistics", (0.0, 0))
+    ens[0].profile(False)
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        r = reads()
+        t1 = time.perf_counter()
+        numpy_quantiles(*r, p)
+        t_read.append(t1 - t0)
+        t_host.append(time.perf_counter() - t0)
+    kernel_us, stat_us = 1e3 * kernel_ms / max(launches, 1), 1e3 * stat_ms / max(stat_launches, 1)
+    ms = lambda t: round(1e3 * t, 3)
+    return {"field": field, "members": B, "p": list(p), "interp": "linear", "path": "staged (LDS)" if staged else "streaming", "calls": a.repeats, "same_numbers": True,
+            "quantiles_call_ms": {"slowest": ms(max(t_dev)), "median": ms(statistics.median(t_dev))},
+            "read_rect_route_ms": {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))},
+            "speedup_slowest": round(max(t_host) / max(t_dev), 2),
+            "kernel_us": round(kernel_us, 2), "kernel_launches_timed": launches,
+            "kernel_gb_read_per_s": round(20 * X * Y * B / (kernel_us * 1e-6) / 1e9, 1) if kernel_us > 0 and staged else None,
+            "statistics_kernel_with_variance_us": round(stat_us, 2), "statistics_kernel_launches_timed": stat_launches,
+            "quantiles_kernel_over_statistics_kernel": round(kernel_us / stat_us, 3) if stat_us > 0 else None}
+
+
 def time_spawn(a, pkg, ens, X, Y, B):
     import statistics
     import numpy as np
@@ -238,6 +326,8 @@ def main():
         sys.exit("--spawn needs --mode ensemble")
     if a.statistics and (a.mode != "ensemble" or a.statistics not in ("BASE_CUR", "WATER_CUR")):
         sys.exit("--statistics BASE_CUR | WATER_CUR needs --mode ensemble")
+    if a.quantiles and (a.mode != "ensemble" or a.quantiles not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--quantiles BASE_CUR | WATER_CUR needs --mode ensemble")
     sys.path.insert(0, a.root)
     if a.share > 0:
         if "debug" not in os.environ.get("WXSIM_LIB", ""):
@@ -279,6 +369,10 @@ def main():
 
         if a.statistics:
             out["shapes"][spec] = {"members": B, "statistics": time_statistics(a, ens, X, Y, B)}
+            close()
+            continue
+        if a.quantiles:
+            out["shapes"][spec] = {"members": B, "quantiles": time_quantiles(a, pkg, ens, X, Y, B)}
             close()
             continue
 
