@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/wxsim.h"
+#include "wx_rounded.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define WXP_HD __host__ __device__
@@ -23,17 +24,7 @@ WXP_HD inline uint32_t f32_bits(float v)
 }
 WXP_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
 
-// A product that feeds a sum is a value of its own. The contraction pragma below is what says so to the compiler's front end; a device
-// build with -ffp-contract=fast (libwxsim_fast.so) also lets the code generator fuse ANY multiply with a dependent add, pragma or not,
-// so on the device the product additionally passes through an empty statement the code generator cannot look through: it is rounded
-// to double before the sum sees it, in every build.
-WXP_HD inline double rounded(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm("" : "+v"(x));
-#endif
-  return x;
-}
+using wxr::rounded; // (wx_rounded.h: a product that feeds a sum is a value of its own, in every build)
 
 // the shaders' integer hash (common.glsl:103-111; wx_kernels.h hash_u32), here for the host as well
 WXP_HD inline uint32_t hash32(uint32_t x)

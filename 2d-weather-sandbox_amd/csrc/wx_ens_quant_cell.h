@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <vector>
 #include "../../include/wxsim.h"
+#include "wx_rounded.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define WXQ_HD __host__ __device__
@@ -56,14 +57,7 @@ WXQ_HD inline bool key_entered(uint32_t key) { return key < KEY_PAD; }
 // one member's value of a cell and channel; wall_dist = channel 1 of its WX_FIELD_WALL_CUR texel
 WXQ_HD inline uint32_t cell_key(float v, int wall_dist) { return wall_dist == 0 ? (uint32_t)KEY_WALL : (f32_finite(v) ? key_of(v) : (uint32_t)KEY_NONFINITE); }
 
-// A product that feeds a sum or a difference is a value of its own, in every build (wx_ens_perturb_cell.h: rounded).
-WXQ_HD inline double rounded(double x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm("" : "+v"(x));
-#endif
-  return x;
-}
+using wxr::rounded; // (wx_rounded.h: a product that feeds a sum or a difference is a value of its own, in every build)
 
 // where quantile p lies among n >= 1 ascending values: v(k), v(k1) and the weight g of the second
 struct Position {

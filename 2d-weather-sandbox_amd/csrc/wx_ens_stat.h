@@ -8,10 +8,13 @@
 // tests' Python loop -- walks the members 0 first.
 //
 // THE per-cell function is cell_add / spread_add / the *_of finishers below, __host__ __device__: the kernel and the host entry point
-// run the same program text. Floating-point contraction is switched off inside every function that rounds (the pragma at the head of
-// its body), so libwxsim.so (-ffp-contract=off) and libwxsim_fast.so (-ffp-contract=fast) give the same bits: Q += d * d is a rounded
-// product and a rounded sum, never an FMA. Double division, int -> double and double -> float conversions are correctly rounded on
-// the device and on the host alike.
+// run the same program text. libwxsim.so (-ffp-contract=off) and libwxsim_fast.so (-ffp-contract=fast) give the same bits, on the
+// host and on the device: Q += d * d is a rounded product and a rounded sum, never an FMA. Two things guarantee that. The contraction
+// pragma at the head of every function that rounds tells the front end, which is enough for the host; the device code generator of a
+// -ffp-contract=fast build fuses a multiply with a dependent add all the same, so there the one product that feeds a sum (`product`
+// below) passes through an opaque register-constraint asm first. tests/test_ensemble_statistics_gpu.py runs the tolerance build on
+// the device over cells on which a fused Q changes the float32 variance (tools/find_variance_separators.py found them). Double
+// division, int -> double and double -> float conversions are correctly rounded on the device and on the host alike.
 //
 // The kernel: one lane per cell of the rectangle; the 64 lanes of a wave take 64 consecutive x of one row (a member's float4 load is
 // 16 B per lane, 1 KiB per wave, contiguous; its wall texel 4 B per lane), waves grid-stride over the (row, 64-column chunk) pairs.
@@ -32,6 +35,7 @@
 #include <limits>
 #include "../../include/wxsim.h"
 #include "wx_diag.h"
+#include "wx_rounded.h"
 
 namespace wxe {
 
@@ -91,6 +95,19 @@ __host__ __device__ inline void spread_init(Spread &s, const Cell &a)
   }
 }
 
+// A product that feeds a sum. In the tolerance build (-ffp-contract=fast) the device code generator fuses d * d into the add that
+// follows, whatever the pragma says (k_ens_stat was the one kernel in which it did), so there the product passes
+// through wx_rounded.h's opaque value first. The default build never contracts (-ffp-contract=off) and is left exactly as it
+// was: an opaque value in the middle of the member group moves its waits (profiles/ensemble_statistics_isa.txt).
+__host__ __device__ inline double product(double x)
+{
+#if defined(WX_FAST_ARITH) && WX_FAST_ARITH
+  return wxr::rounded(x);
+#else
+  return x;
+#endif
+}
+
 __host__ __device__ inline void spread_add(Spread &s, const float v[4], int wall_dist)
 {
 #pragma clang fp contract(off)
@@ -99,7 +116,7 @@ __host__ __device__ inline void spread_add(Spread &s, const float v[4], int wall
   for (int c = 0; c < 4; c++) {
     const bool take = air && wxd::f32_finite(v[c]);
     const double d = (double)v[c] - s.m[c];
-    const double dd = d * d;
+    const double dd = product(d * d);
     const double q1 = s.Q[c] + dd;
     s.Q[c] = take ? q1 : s.Q[c];
   }

@@ -8,6 +8,7 @@ import os
 import re
 import subprocess
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -63,12 +64,46 @@ def reference(fields, walls, members=None, p=P8, interp="linear", rank_of=None):
     return out
 
 
+# SEPARATING CELLS of the linear interpolation: two values on which fma(g, d, v(k)) -- what a build computes that contracts the
+# product into the sum -- gives ANOTHER float32 quantile than the definition's rounded g * d and rounded sum. The two doubles differ
+# by one ulp, which the conversion shows only on a float32 rounding boundary (2^-29 per ulp for random data), and only if g * d is
+# inexact at all: two values of like magnitude never separate. Printed by `python tools/find_variance_separators.py --seed 1`
+# (numpy and exact rational arithmetic, no build of the library), not searched for at test time. n = 2, so h = g = P_SEP -- a
+# quantile of its own: with the short fractions of P8 the result lies on a lattice on which the two evaluations never differ.
+# (cell of `planted`; float32 bits of v(0) and v(1); float32 bits of the quantile by the definition; by the fused evaluation.)
+# Member 1 holds v(1), member 2 holds v(0), every other member NaN: a cell is complete in every selection that holds members 1 and 2.
+P_SEP = float(np.float32(0.3141592))
+SEPARATING_CELLS = [
+    (20, 0xBFEAD0FF, 0x33E593EA, 0xBFA10BF2, 0xBFA10BF1),  # fused above
+    (21, 0xBFEAD11F, 0x33BA4FEC, 0xBFA10C08, 0xBFA10C07),  # fused above
+    (22, 0xBFEAD42B, 0x33964E1D, 0xBFA10E1E, 0xBFA10E1F),  # fused below
+    (23, 0xBFEAD49A, 0x33FEE024, 0xBFA10E6A, 0xBFA10E6B),  # fused below
+]
+
+
+def separating_cells_in(B, members=None):
+    """The separating cells that are complete in a selection of planted(B)'s members 0 .. B - 1."""
+    return SEPARATING_CELLS if B >= 3 and {1, 2} <= set(range(B) if members is None else members) else []
+
+
+def two_quantiles(v0, v1, p):
+    """(defined, fused) float32 linear quantile p of the two ascending values, one Python float operation per rounded operation."""
+    h = float(np.float32(p)) * 1.0
+    k = float(np.floor(h))
+    g = h - k
+    assert k == 0.0
+    d = v1 - v0
+    gd = g * d
+    return np.float32(v0 + gd), np.float32(float(Fraction(g) * Fraction(d) + Fraction(v0)))
+
+
 def planted(B, n_cells=64):
     """`hand_built` of the statistics test for B + 1 members -- random float bit patterns, random walls, and its planted cells: all
     equal (0), subnormals with FLT_MAX (2), one NaN / +Inf / -Inf among finite values (3), every member non-finite (4), every member
     wall (5), wall in some members only (6), -0.0 against +0.0 (7), ties (8) -- plus, in cells 11 .. 14: n = 1, n = 2, ties across k /
     k1 around the median, -0.0 and +0.0 in one cell. Member B is the one that is RANKED: in the planted cells its values lie below all,
-    above all, equal to several, on a wall, and are NaN."""
+    above all, equal to several, on a wall, and are NaN. Cells 15 .. 19 are hand_built's separating cells of the variance, 20 .. 23 the separating
+    cells of the linear interpolation (SEPARATING_CELLS above)."""
     f, w = hand_built(B + 1, n_cells)
     for i in range(B):
         w[i][11, 1] = 7 if i == 0 else 0                                  # 11: one member's value enters
@@ -87,6 +122,11 @@ def planted(B, n_cells=64):
     r[14] = np.float32([-0.0, 0.0, 1e-45, np.nan])  # a zero of either sign equals the zeros of both signs
     w[B][1, 1] = 0                                # on a wall
     r[2] = np.float32([np.nan, FLT_MAX, -FLT_MAX, 0.0])
+    for cell, v0, v1, _, _ in SEPARATING_CELLS:   # 20 .. 23: the separating cells, the same values in all four channels
+        if cell < n_cells:
+            for i in range(B + 1):
+                f[i][cell] = np.uint32({1: v1, 2: v0}.get(i, 0x7FC00000)).view(np.float32) if i < B else np.float32(np.nan)
+                w[i][cell, 1] = 5
     return f, w
 
 
@@ -200,6 +240,37 @@ def test_the_definition_on_values_worked_by_hand(pkg):
     assert r == np.float32(1.0 + (p01 * 2.0) * 3.0) and 1.6 < float(r) < 1.6001
     g = reference([np.full((1, 4), x, np.float32) for x in (1e-45, FLT_MAX)], air[:2], None, (0.75,), "linear")["q"][0, 0, 0]
     assert g == np.float32(np.float64(np.float32(1e-45)) + 0.75 * (np.float64(FLT_MAX) - np.float64(np.float32(1e-45))))
+
+
+def test_separating_cells_separate(pkg):
+    """Every committed cell, by exact arithmetic: the definition and the fused evaluation give the committed, DIFFERENT float32
+    quantiles, in both directions; in planted's data `reference` gives the definition's value in exactly the complete cells; and
+    the default library's host function equals `reference` at that p under every interpolation."""
+    u32 = lambda x: int(np.float32(x).view(np.uint32))  # noqa: E731
+    above = below = 0
+    for cell, v0, v1, defined, fused in SEPARATING_CELLS:
+        lo, hi = (float(np.uint32(b).view(np.float32)) for b in (v0, v1))
+        a, b = two_quantiles(lo, hi, P_SEP)
+        assert lo < hi and (u32(a), u32(b)) == (defined, fused) and defined != fused, (cell, hex(u32(a)), hex(u32(b)))
+        assert abs(defined - fused) == 1  # neighbouring floats
+        above, below = above + (b > a), below + (b < a)
+    assert len(SEPARATING_CELLS) >= 2 and above >= 1 and below >= 1
+    seen = 0
+    for B, members in CASES[:6]:
+        f, w = planted(B)
+        for interp in INTERPS:
+            want = reference(f, w, members, (P_SEP,), interp, B)
+            check(pkg.engine.ens_quant_cells(f, w, (P_SEP,), members=members, interp=interp, rank_of=B), want, ("separating", B, interp))
+        want = reference(f, w, members, (P_SEP, 0.0, 1.0), "linear", B)
+        here = separating_cells_in(B, members)
+        for cell, v0, v1, defined, fused in here:
+            assert (want["q"][0, cell].view(np.uint32) == defined).all() and (want["count"][cell] == 2).all(), (B, cell)
+            assert (want["q"][1, cell].view(np.uint32) == v0).all() and (want["q"][2, cell].view(np.uint32) == v1).all(), (B, cell)
+            assert (want["n_below"][cell] == -1).all()  # (the ranked member holds a NaN there)
+        for cell, _, _, _, _ in SEPARATING_CELLS:
+            assert here or (want["count"][cell] < 2).all(), (B, cell)
+        seen += len(here)
+    assert seen == 3 * len(SEPARATING_CELLS)  # B = 3, 7 and 70 masked
 
 
 @pytest.mark.parametrize("interp", INTERPS)
@@ -342,6 +413,12 @@ def test_the_tolerance_build_gives_the_same_bits(pkg, tmp_path):
             got = dict(np.load(dst))
             check(got, pkg.engine.ens_quant_cells(f, w, P8, members=members, interp=interp, rank_of=B), ("fast vs exact", B, interp))
             check(got, reference(f, w, members, P8, interp, B), ("fast vs definition", B, interp))
+        src, dst = str(tmp_path / f"in{B}_sep.npz"), str(tmp_path / f"out{B}_sep.npz")  # the separating cells' own quantile
+        np.savez(src, f=np.stack(f), w=np.stack(w), mask=mask, p=np.float32([P_SEP]), interp=0, rank=B)
+        subprocess.check_call([sys.executable, "-c", leg, fast, src, dst], timeout=120)
+        got = dict(np.load(dst))
+        check(got, reference(f, w, members, (P_SEP,), "linear", B), ("fast vs definition, separating", B))
+        assert all((got["q"][0, cell].view(np.uint32) == defined).all() for cell, _, _, defined, _ in SEPARATING_CELLS)
 
 
 def test_host_function_under_the_sanitizers(tmp_path):

@@ -15,7 +15,7 @@ import pytest
 import impulse_scenes as I
 from test_ensemble_droplets_gpu import _order1, _precip64, pool_of
 from test_ensemble_gpu import FIELDS, Twins, same_bits, same_diag
-from test_ensemble_quantiles_cpu import INTERPS, P8, PLANES, check, reference
+from test_ensemble_quantiles_cpu import INTERPS, P8, P_SEP, PLANES, SEPARATING_CELLS, check, planted, reference
 from test_ensemble_statistics_gpu import EARLY, STAT_FIELDS, Stepped, make_ensemble, member_specs, rectangles
 
 pytestmark = pytest.mark.gpu
@@ -232,6 +232,19 @@ def test_members_with_droplets(pkg, golden):
         ens.close()
 
 
+PX, PY = 57, 9  # the grid `planted` is laid out on: its cell i is (y, x) = divmod(i, PX)
+
+
+def uploaded_planted(pkg, B):
+    """planted(B, 57 * 9) -- its planted cells and the separating cells in front (row 0), random float bit patterns and random walls
+    behind -- uploaded as BASE and as WATER of B + 1 members (member B is the ranked one); nothing is stepped."""
+    f, w = planted(B, PX * PY)
+    ens = pkg.engine.Ensemble(B + 1, PX, PY, 0)
+    for i in range(B + 1):
+        ens[i].upload(f[i].reshape(PY, PX, 4), f[i].reshape(PY, PX, 4), w[i].reshape(PY, PX, 4))
+    return ens
+
+
 _FAST_LEG = r"""
 import sys
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
@@ -249,6 +262,14 @@ for B in (6, pkg.engine.lib().wx_ens_quant_staged_members() + 2):  # the staged 
     for f in ("BASE_CUR", "WATER_CUR"):
         for k, v in ens.quantiles(f, T.P8, rank_of=B - 1).items():
             out[f"{B}_{f}_{k}"] = v
+    ens.close()
+for B in (7, pkg.engine.lib().wx_ens_quant_staged_members() + 1):  # planted uploads, the separating cells among them, at their own quantile
+    ens = T.uploaded_planted(pkg, B)
+    for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR"):
+        out[f"u{B}_{f}"] = np.stack([m.read_rect(f) for m in ens.members])
+    for f in ("BASE_CUR", "WATER_CUR"):
+        for k, v in ens.quantiles(f, (T.P_SEP, 0.5), rank_of=B).items():
+            out[f"u{B}_{f}_{k}"] = v
     ens.close()
 np.savez(sys.argv[2], **out)
 """
@@ -272,6 +293,18 @@ def test_the_tolerance_build_on_the_device(pkg, tmp_path):
             check(got, pkg.engine.ens_quant_cells(fields, walls, P8, rank_of=B - 1), (B, f, "fast device vs exact host"))
             check(got, reference(fields, walls, None, P8, "linear", B - 1), (B, f, "fast device vs definition"))
             assert np.isfinite(got["q"]).any() and (got["q"][3] != got["q"][4]).any()
+    # planted uploads on the staged and on the streaming path: the separating cells are the only data on which a g * d that the code
+    # generator fused into the sum would show in the float32 quantile
+    for B in (7, staged_limit(pkg) + 1):
+        walls = list(d[f"u{B}_WALL_CUR"])
+        for f in STAT_FIELDS:
+            fields = list(d[f"u{B}_{f}"])
+            assert all(a.view(np.uint32).tobytes() == b.reshape(PY, PX, 4).view(np.uint32).tobytes() for a, b in zip(fields, planted(B, PX * PY)[0]))
+            got = {k: d[f"u{B}_{f}_{k}"] for k in PLANES}
+            check(got, pkg.engine.ens_quant_cells(fields, walls, (P_SEP, 0.5), rank_of=B), (B, f, "planted: fast device vs exact host"))
+            check(got, reference(fields, walls, None, (P_SEP, 0.5), "linear", B), (B, f, "planted: fast device vs definition"))
+            for cell, _, _, defined, fused in SEPARATING_CELLS:
+                assert (got["q"][0, 0, cell].view(np.uint32) == defined).all() and defined != fused and (got["count"][0, cell] == 2).all(), (B, f, cell)
 
 
 def test_refusals(pkg):

@@ -8,6 +8,7 @@ import os
 import re
 import subprocess
 import sys
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -30,9 +31,19 @@ def same_bits(a, b):
     return bool(np.array_equal(na, nb) and np.array_equal(a.view(bits)[~na], b.view(bits)[~nb]))
 
 
-def reference(fields, walls, members=None, threshold=(0, 0, 0, 0)):
+def _fma(a, b, c, where):
+    """fma(a, b, c) element by element in exact rational arithmetic, rounded once (Python 3.10 has no math.fma); c where not `where`."""
+    out = np.array(c, np.float64)
+    for i in np.argwhere(where):
+        i = tuple(i)
+        out[i] = float(Fraction(float(a[i])) * Fraction(float(b[i])) + Fraction(float(c[i])))
+    return out
+
+
+def reference(fields, walls, members=None, threshold=(0, 0, 0, 0), fused=False):
     """The per-cell function of include/wxsim.h, straight from its definition. fields[i]: float32 (..., 4), walls[i]: int8 (..., 4);
-    members: the selected member indices (None: all). Returns the nine planes."""
+    members: the selected member indices (None: all). Returns the nine planes. fused: NOT the definition -- Q = fma(d, d, Q), what a
+    build computes that contracts the product into the sum; the separating cells below are where the two differ."""
     shape = fields[0].shape
     sel = sorted(range(len(fields)) if members is None else members)  # member order, 0 first
     thr = np.asarray(threshold, np.float32)
@@ -60,6 +71,9 @@ def reference(fields, walls, members=None, threshold=(0, 0, 0, 0)):
         Q = np.zeros(shape, np.float64)
         for i in sel:
             d = fields[i].astype(np.float64) - m
+            if fused:
+                Q = _fma(d, d, Q, enters[i])
+                continue
             dd = d * d
             Q = np.where(enters[i], Q + dd, Q)
         var = np.where(n > 0, Q / n.astype(np.float64), np.nan).astype(np.float32)
@@ -71,6 +85,46 @@ def reference(fields, walls, members=None, threshold=(0, 0, 0, 0)):
 
 THRESHOLD = (0.5, -1.0, float("nan"), 1e-40)  # channel 2: a NaN threshold (n_above is 0 there); channel 3: a subnormal one
 ORDER_VALUES = np.array([1e30, 1.0, -1e30, 1.0], np.float32)
+
+# SEPARATING CELLS: sets of members on which Q = fma(d, d, Q) -- what a build computes that contracts the product into the sum -- gives
+# ANOTHER float32 variance than the definition's rounded product and rounded sum. The two Q differ by an ulp or two of a double, which
+# the conversion to float32 shows only where Q / n lies that close to a float32 rounding boundary: about B * 2^-29 per cell of random
+# data, so no other data of this suite can tell the two apart. Printed by `python tools/find_variance_separators.py --seed 1` (a
+# directed search in numpy and exact rational arithmetic; no build of the library is asked), not searched for at test time.
+# (cell of hand_built; float32 bits of members 1, 2, ... of that cell; which of them is a WALL member, if any; the float32 bits of
+# the variance by the definition; by the fused evaluation.) 0x7FC00000 is a NaN member: it does not enter, like the wall member.
+# Members 0 and those behind the list hold NaN, so a cell is complete in every selection that holds members 1 .. len(bits).
+SEPARATING_CELLS = [
+    (15, [0x35C6BC5A, 0x3FB514E6, 0x30B54871, 0xBF8237EA, 0x40050901, 0x3FDE1EE1], None, 0x3F9E22D1, 0x3F9E22D2),  # 6 enter, fused above
+    (16, [0x4042BDD0, 0x35ECB6FA, 0x405BA7DB, 0x401A6133, 0x30A282A6, 0x3FACC464], None, 0x3FEF3677, 0x3FEF3676),  # 6 enter, fused below
+    (17, [0x3087B2EF, 0x3FDFF5E3, 0x35A3CA88, 0x7FC00000, 0x40726A7C, 0xC00A839B], None, 0x407DA828, 0x407DA829),  # 5 enter, a NaN member among them
+    (18, [0x3FAFF34E, 0xC05221B2, 0x35A4AD17, 0xC0656B63, 0x4054539A, 0x30A9C8DA, 0xC00BD290, 0xC07F80DD, 0xBFBCEFD7], None,
+     0x40AD1760, 0x40AD1761),                                                                                     # 9 enter: a group of 8 and a remainder
+    (19, [0xC04FEFF8, 0x30BCF5C1, 0x40134D70, 0xC03A68D0, 0x401598E1, 0x42F60000, 0x3FDC66F0, 0xC06B3A30, 0xC0395A4C, 0x35C95242], 5,
+     0x40B24FDA, 0x40B24FD9),                                                                                     # 9 enter, a wall member (123.0) among them
+]
+
+
+def separating_cells_in(B, members=None):
+    """The separating cells that are complete in a selection of hand_built(B)'s members."""
+    sel = set(range(B) if members is None else members)
+    return [s for s in SEPARATING_CELLS if set(range(1, 1 + len(s[1]))) <= sel and len(s[1]) < B]
+
+
+def two_variances(values):
+    """(defined, fused) float32 variance of the values that enter, in member order, one Python float operation per rounded operation."""
+    n = float(len(values))
+    S = 0.0
+    for v in values:
+        S = S + v
+    m = S / n
+    Q = Qf = 0.0
+    for v in values:
+        d = v - m
+        dd = d * d
+        Q = Q + dd
+        Qf = float(Fraction(d) * Fraction(d) + Fraction(Qf))
+    return np.float32(Q / n), np.float32(Qf / n)
 
 
 def hand_built(B, n_cells=64, seed=2024):
@@ -113,10 +167,23 @@ def hand_built(B, n_cells=64, seed=2024):
         t = np.float32(THRESHOLD[c] if THRESHOLD[c] == THRESHOLD[c] else 1.0)
         put(9, [t, np.nextafter(t, np.float32(np.inf)), np.nextafter(t, np.float32(-np.inf))], c)
     put(10, [1e30, -1e30, 3.0, 0.0], 2)                                         # 10: values of any size under the NaN threshold of channel 2
+    # (11 .. 14 are the cells the quantiles' `planted` writes.) 15 .. 19: the separating cells, the same values in all four channels.
+    # The quantile tests build `planted` on this function, so they inherit these five cells as well (there: six or nine finite values
+    # of mixed magnitude among NaN members, one cell with a wall member); 20 .. 23 are `planted`'s own separating cells
+    for cell, bits, wall_at, _, _ in SEPARATING_CELLS:
+        if cell < n_cells:
+            f[:, cell, :] = np.float32(np.nan)
+            w[:, cell, 1] = 5
+            for k, b in enumerate(bits[:B - 1]):
+                f[1 + k, cell, :] = np.uint32(b).view(np.float32)
+            if wall_at is not None and 1 + wall_at < B:
+                w[1 + wall_at, cell, 1] = 0
     return [np.ascontiguousarray(f[i]) for i in range(B)], [np.ascontiguousarray(w[i]) for i in range(B)]
 
 
 CASES = [(7, None), (1, None), (70, [i for i in range(70) if i not in (0, 33, 69)])]
+# 8, 9 and 16 selected members of 16: one full group of the kernel's member loop (UNROLL = 8) and no remainder, a group and one, two groups
+N_SEL_CASES = [(16, list(range(1, 9))), (16, list(range(1, 10))), (16, None)]
 
 
 def check(got, want, where):
@@ -182,6 +249,40 @@ def test_the_order_case_pins_the_order():
     f, w = hand_built(7)
     r = reference(f, w, threshold=THRESHOLD)
     assert r["mean"][1, 0] == np.float32(1.0 / 7.0) and r["count"][1, 0] == 7
+
+
+def test_separating_cells_separate(pkg):
+    """Every committed cell, by exact arithmetic: the definition and the fused evaluation give the committed, DIFFERENT float32 variances;
+    in hand_built's data `reference` and its fused variant differ in exactly these cells' variance and in no other plane; and the
+    default library's host function gives the definition's value."""
+    u32 = lambda x: int(np.float32(x).view(np.uint32))  # noqa: E731
+    n_entered, above, below, interrupted = [], 0, 0, 0
+    for cell, bits, wall_at, defined, fused in SEPARATING_CELLS:
+        vals = np.array(bits, np.uint32).view(np.float32)
+        enters = [k != wall_at and np.isfinite(v) for k, v in enumerate(vals)]
+        a, b = two_variances([float(v) for v, e in zip(vals, enters) if e])
+        assert (u32(a), u32(b)) == (defined, fused) and defined != fused, (cell, hex(u32(a)), hex(u32(b)))
+        assert abs(defined - fused) == 1  # neighbouring floats: the two Q are an ulp or two of a double apart
+        n_entered.append(sum(enters))
+        above, below = above + (b > a), below + (b < a)
+        interrupted += not all(enters) and enters[0] and enters[-1]
+    assert len(SEPARATING_CELLS) >= 4 and above >= 1 and below >= 1 and max(n_entered) >= 9 and interrupted >= 1
+    assert any(wall_at is not None for _, _, wall_at, _, _ in SEPARATING_CELLS)
+    complete = [[15, 16, 17], [], [15, 16, 17, 18, 19], [15, 16, 17], [15, 16, 17, 18], [15, 16, 17, 18, 19]]
+    for (B, members), cells in zip(CASES + N_SEL_CASES, complete):
+        f, w = hand_built(B)
+        want, other = reference(f, w, members, THRESHOLD), reference(f, w, members, THRESHOLD, fused=True)
+        here = separating_cells_in(B, members)
+        differ = np.zeros((64, 4), bool)
+        for cell, _, _, defined, fused in here:
+            assert (want["variance"][cell].view(np.uint32) == defined).all() and (other["variance"][cell].view(np.uint32) == fused).all(), (B, cell)
+            differ[cell] = True
+        assert np.array_equal(want["variance"].view(np.uint32) != other["variance"].view(np.uint32), differ) and np.isfinite(want["variance"][differ]).all(), B
+        for k in PLANES:
+            assert k == "variance" or same_bits(want[k], other[k]), (B, k)
+        got = pkg.engine.ens_stat_cells(f, w, members=members, threshold=THRESHOLD)
+        check(got, want, ("separating", B))
+        assert [s[0] for s in here] == cells, (B, members)
 
 
 @pytest.mark.parametrize("B,members", CASES, ids=["7", "1", "70-masked"])

@@ -3,6 +3,10 @@ and the definition of include/wxsim.h, written down as the explicit member loop 
 every plane, both supported fields, whole grids and ragged rectangles, masks, non-finite and wall cells, members with droplets; the call
 is ordered behind pending steps, changes nothing, and refuses what the header says it refuses. Every comparison is `==` on bits (NaNs
 compared as positions)."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -10,7 +14,7 @@ import impulse_scenes as I
 import surface_scenes as S
 from test_ensemble_droplets_gpu import _order1, _precip64, pool_of
 from test_ensemble_gpu import FIELDS, Twins, _slider_uniforms, same_bits, same_diag
-from test_ensemble_statistics_cpu import PLANES, check, reference
+from test_ensemble_statistics_cpu import CASES, N_SEL_CASES, PLANES, THRESHOLD, check, hand_built, reference, separating_cells_in
 
 pytestmark = pytest.mark.gpu
 
@@ -167,6 +171,131 @@ def test_nonfinite_and_wall_cells(pkg):
         assert (got["count"].sum(-1) + 4 * got["n_wall"] + np.isin(np.arange(X * Y).reshape(Y, X), [y * X + x for (y, x, _, _) in bad]) == 20).all()
     finally:
         ens.close()
+
+
+PX, PY = 57, 9  # the grid the definition's planted cases are laid out on: cell i of hand_built is (y, x) = divmod(i, PX)
+
+
+def uploaded_hand_built(pkg, B):
+    """hand_built(B, 57 * 9) -- the planted cases and the separating cells in front (row 0), random float bit patterns and random walls
+    behind -- uploaded as BASE and as WATER of B members; nothing is stepped, and an upload keeps every bit pattern."""
+    f, w = hand_built(B, PX * PY)
+    f, w = [a.reshape(PY, PX, 4) for a in f], [a.reshape(PY, PX, 4) for a in w]
+    ens = pkg.engine.Ensemble(B, PX, PY, 0)
+    for i in range(B):
+        ens[i].upload(f[i], f[i], w[i])
+    return ens, f, w
+
+
+@pytest.mark.parametrize("B,members", CASES + N_SEL_CASES, ids=["7", "1", "70-masked", "n_sel=8", "n_sel=9", "n_sel=16"])
+def test_planted_cases_on_the_device(pkg, B, members):
+    """The cases of the definition that `hand_built` plants -- the fixed-order sum, subnormals with FLT_MAX, zeros of both signs, ties,
+    values at / above / below a threshold, a subnormal and a NaN threshold, all-wall and all-non-finite cells -- and the separating
+    cells, through k_ens_stat: the float compares of the device and the select-written cell_add meet them here."""
+    ens, f, w = uploaded_hand_built(pkg, B)
+    try:
+        sel = list(range(B)) if members is None else list(members)
+        walls = [m.read_rect("WALL_CUR") for m in ens.members]
+        assert all(np.array_equal(a, b) for a, b in zip(walls, w))
+        for field in STAT_FIELDS:
+            fields = [m.read_rect(field) for m in ens.members]
+            assert all(a.view(np.uint32).tobytes() == b.view(np.uint32).tobytes() for a, b in zip(fields, f))  # (NaN payloads too)
+            want = reference(fields, walls, members, THRESHOLD)
+            check(pkg.engine.ens_stat_cells(fields, walls, members=members, threshold=THRESHOLD), want, (field, B, "host function"))
+            for (x, y, rw, rh) in rectangles(PX, PY):
+                got = ens.statistics(field, x, y, rw, rh, threshold=THRESHOLD, members=members)
+                check(got, cut(want, x, y, rw, rh), (field, B, (x, y, rw, rh)))
+            got = ens.statistics(field, threshold=THRESHOLD, members=members)
+            row = {k: v[0] for k, v in got.items()}  # the planted cells, by value
+            n_sel, zero = len(sel), np.float32(0).view(np.uint32)
+            S = np.float64(0)
+            for i in sel:  # 1: the sum in member order
+                S = S + np.float64((list(np.float32([1e30, 1.0, -1e30, 1.0])) + [np.float32(0)] * 3)[i % 7])
+            assert row["mean"][1, 0] == np.float32(S / np.float64(n_sel)) and row["count"][1, 0] == n_sel
+            if B == 7:
+                assert S == 1.0 and row["mean"][1, 0] == np.float32(1.0 / 7.0)  # 1, not the 0 of a sorted or pairwise sum
+                assert row["n_above"][9].tolist() == [2, 2, 0, 2] and row["count"][9].tolist() == [7, 7, 7, 7]
+                assert np.isfinite(row["mean"][2]).all() and row["max"][2, 0] == np.float32(3.4028234663852886e38)
+                assert row["n_wall"][6] == 3 and row["count"][6, 0] == 4 and row["argmin"][6, 0] == 5 and row["argmax"][6, 0] == 2
+                assert row["argmin"][7, 0] == 0 and row["argmax"][7, 1] == 0 and row["argmax"][7, 2] == 0 and row["argmin"][7, 3] == 1
+            assert (row["variance"][0].view(np.uint32) == zero).all() and (row["mean"][0] == 1.5).all()
+            assert (row["count"][4] == 0).all() and row["n_wall"][4] == 0 and np.isnan(row["max"][4]).all() and np.isnan(row["variance"][4]).all()
+            assert row["n_wall"][5] == n_sel and (row["count"][5] == 0).all() and np.isnan(row["mean"][5]).all() and (row["argmin"][5] == -1).all()
+            assert row["max"][7, 2].view(np.uint32) == zero  # the maximum is a -0.0 (member 0, 3, ...): reported as +0.0
+            assert (row["n_above"][:, 2] == 0).all() and row["count"][10, 2] == n_sel  # the NaN threshold
+            tied = [i for i in sel if i % 7 in (2, 5)]
+            if tied:  # 8: the tie is held by the smaller member index
+                assert row["argmin"][8, 0] == tied[0] and row["argmax"][8, 1] == tied[0] and row["min"][8, 0] == -7.0 and row["max"][8, 1] == 9.0
+            here = separating_cells_in(B, members)
+            assert bool(here) == (B > 1)
+            for cell, _, _, defined, _ in here:
+                assert (row["variance"][cell].view(np.uint32) == defined).all(), (field, B, cell)
+    finally:
+        ens.close()
+
+
+FAST_STEPPED = [(6, None), CASES[2]]
+FAST_UPLOADED = [CASES[0], CASES[2], N_SEL_CASES[2]]
+
+
+def fast_leg_threshold(tag, field):
+    return THRESHOLDS[field] if tag[0] == "s" else THRESHOLD
+
+
+_FAST_LEG = r"""
+import sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import numpy as np
+import wxpkg
+pkg = wxpkg.load_package()
+assert pkg.engine.lib().wx_arith() == 1, "not the tolerance build"
+import test_ensemble_statistics_gpu as T
+out = {}
+def record(tag, ens, members):
+    out[tag + "_WALL_CUR"] = np.stack([m.read_rect("WALL_CUR") for m in ens.members])
+    for f in T.STAT_FIELDS:
+        out[f"{tag}_{f}"] = np.stack([m.read_rect(f) for m in ens.members])
+        for k, v in ens.statistics(f, threshold=T.fast_leg_threshold(tag, f), members=members).items():
+            out[f"{tag}_{f}_{k}"] = v
+    ens.close()
+for B, members in T.FAST_STEPPED:
+    ens = T.make_ensemble(pkg, T.member_specs(pkg, 57, 9, B))
+    ens.step(T.EARLY)
+    record(f"s{B}", ens, members)
+for B, members in T.FAST_UPLOADED:
+    record(f"u{B}", T.uploaded_hand_built(pkg, B)[0], members)
+np.savez(sys.argv[2], **out)
+"""
+
+
+def test_the_tolerance_build_on_the_device(pkg, tmp_path):
+    """libwxsim_fast.so in a process of its own (a process holds one libwxsim): its k_ens_stat gives what THIS process's host function
+    and the definition give on the values the members held. Stepped members (the simulation steps of the two builds differ, the
+    statistics of what they hold do not), and uploaded members that hold hand_built's data: among them the separating cells, the only
+    data on which a Q += d * d that the code generator fused into an FMA shows in the float32 variance."""
+    fast = pkg.engine.FAST_LIB_PATH
+    assert os.path.exists(fast), "libwxsim_fast.so is not built"
+    dst = str(tmp_path / "fast.npz")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.check_call([sys.executable, "-c", _FAST_LEG, root, dst], env=dict(os.environ, WXSIM_LIB=fast), timeout=300)
+    d = np.load(dst)
+    for tag, cases in (("s", FAST_STEPPED), ("u", FAST_UPLOADED)):
+        for B, members in cases:
+            walls = list(d[f"{tag}{B}_WALL_CUR"])
+            for f in STAT_FIELDS:
+                thr = fast_leg_threshold(tag, f)
+                fields = list(d[f"{tag}{B}_{f}"])
+                got = {k: d[f"{tag}{B}_{f}_{k}"] for k in PLANES}
+                check(got, pkg.engine.ens_stat_cells(fields, walls, members=members, threshold=thr), (tag, B, f, "fast device vs exact host"))
+                check(got, reference(fields, walls, members, thr), (tag, B, f, "fast device vs definition"))
+                assert (got["variance"][got["count"] > 1] > 0).any()
+                if tag == "u":  # the members held hand_built's bits, the separating cells among them
+                    want = hand_built(B, PX * PY)[0]
+                    assert all(a.view(np.uint32).tobytes() == b.view(np.uint32).tobytes() for a, b in zip(fields, want))
+                    here = separating_cells_in(B, members)
+                    assert len(here) >= 3
+                    for cell, _, _, defined, fused in here:
+                        assert (got["variance"][0, cell].view(np.uint32) == defined).all() and defined != fused, (B, f, cell)
 
 
 def test_masks(pkg, stepped):
