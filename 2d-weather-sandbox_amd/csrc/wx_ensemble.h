@@ -249,8 +249,8 @@ int wx_ensemble_step(wx_ensemble *e, int n_iter)
         sl.ka.iterNum = wi.iter;
         sl.ka.in = wi.in;
         sl.ka.out = wi.out;
-        sl.ka.fix[0] = sl.ka.fix[1] = fix;
-        sl.ka.n_strips = sl.ka.n_strips_all = sl.ka.split_at = w.n_strips; // the whole width, one strip range, no order (launch_march_wet's defaults)
+        sl.ka.fix = fix;
+        sl.ka.n_strips = sl.ka.n_strips_all = sl.ka.split_at = w.n_strips; // the whole width, one strip range, no priority (launch_march_wet's defaults)
         sl.ka.segs = w.segs;
         sl.ka.vx = vx_track(m);
         sl.overflow = &m->state->fix_overflow;

@@ -79,7 +79,7 @@ __device__ __forceinline__ void march_fence() { __syncthreads(); }
 // QUIET: no brush input, no airplane event in this iteration (see advection_cell)
 template <bool WRITE_DISP, bool WRITE_WALL, bool QUIET>
 __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni u_arg, const FullCtx *__restrict__ ctx, DryIn in, DryOut out, int n_strips, int seg_rows,
-                                                                     int n_full, int n_half, int band_h, int n_seg, int strip_lo, int split_at, int strip_lo2, StripOrder order, VxTrack vx
+                                                                     int n_full, int n_half, int band_h, int n_seg, int strip_lo, int split_at, int strip_lo2, VxTrack vx
 #ifdef WX_MARCH_TIMING
                                                                      , unsigned long long *cycles
 #endif
@@ -102,26 +102,12 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
   // 128-byte lines they share (2 halo columns each side; 60-column strips are not line aligned) are fetched into ONE L2
   // instead of two. Measured FETCH_SIZE: 1.22x -> 1.00x of the bytes the strips need; 32768x4096: 1.39 -> 1.11 ms.
   const int total = n_strips * n_seg, k = blockIdx.x & 7, j = blockIdx.x >> 3;
-  int seg, strip;
-  bool is_edge = false; // (a split iteration's edge strip: waits for the ghost columns / reports when it is done)
-  if (order.mode == 0 || order.mode == 3) {
-    const int first = (int)(((long long)k * total) >> 3), count = (int)(((long long)(k + 1) * total) >> 3) - first;
-    if (j >= count) return;
-    const int item = first + j;
-    seg = item / n_strips;
-    const int sidx = item - seg * n_strips;
-    strip = sidx < split_at ? strip_lo + sidx : strip_lo2 + (sidx - split_at); // (two strip ranges in one launch: the edges of a slab)
-    if (order.mode == 3) is_edge = strip < order.nl || strip >= order.nr0; // (a shape without row bands: the hand-offs without the dispatch order)
-  } else {
-    // One launch over ALL strips of a slab (row bands: n_seg is a multiple of 8 and XCD k owns the segments [k * n_seg / 8, (k + 1) * n_seg / 8)),
-    // the edge strips of all its segments first (or last) in the XCD's dispatch order (StripOrder, wx_tile.h)
-    const int spx = n_seg >> 3;
-    StripPick pk;
-    if (!strip_order_pick(order, 0, n_strips, spx, 1, 0, j, seg, pk)) return;
-    seg += k * spx;
-    strip = pk.strip;
-    is_edge = pk.is_edge;
-  }
+  const int first = (int)(((long long)k * total) >> 3), count = (int)(((long long)(k + 1) * total) >> 3) - first;
+  if (j >= count) return;
+  const int item = first + j;
+  const int seg = item / n_strips;
+  const int sidx = item - seg * n_strips;
+  const int strip = sidx < split_at ? strip_lo + sidx : strip_lo2 + (sidx - split_at); // (two strip ranges in one launch: the edges of a slab)
   const int c_out = strip * MOUT + lane - 2;         // output column of this lane (may be >= X in the last strip)
   const int col = wrapmod(c_out, X);                 // column this lane loads / computes
   const bool lane_out = lane >= 2 && lane <= 61 && c_out < X;
@@ -134,16 +120,11 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
     const int t1 = sl - n_full, t2 = t1 - n_half, h2 = seg_rows >> 1, h4 = seg_rows >> 2, y0 = bnd * band_h;
     y_lo = y0 + (t1 < 0 ? sl * seg_rows : (t2 < 0 ? n_full * seg_rows + t1 * h2 : n_full * seg_rows + n_half * h2 + t2 * h4));
     y_hi = min(y_lo + (t1 < 0 ? seg_rows : (t2 < 0 ? h2 : h4)), y0 + band_h);
-    if (y_lo >= y_hi) {
-      if (is_edge && order.arrive != nullptr) strip_order_arrive(order, lane, false); // (an empty segment still counts as an edge item that is done)
-      return;
-    }
+    if (y_lo >= y_hi) return;
   } else {
     y_lo = seg * seg_rows;
     y_hi = min(y_lo + seg_rows, Y);
   }
-  if (is_edge && order.epoch != nullptr) strip_order_wait(order); // the ghost columns this strip reads are being written by the exchange
-  if (is_edge) strip_order_prio(order.prio);
   const unsigned lo4 = (unsigned)col * 4u, lo16 = (unsigned)col * 16u;                      // byte offsets of the loaded column
   const unsigned so4 = lane_out ? (unsigned)c_out * 4u : 0u, so16 = so4 * 4u;              // ... of the stored column
 
@@ -267,7 +248,6 @@ __global__ __launch_bounds__(64, WX_MARCH_MINWAVES) void k_march_dry(Geo g, Uni 
     if (WRITE_DISP) st_row_v(out.base_disp + e, so16, st_ab);
   }
   vx_track_commit(vx, vx_seen, lane, strip);
-  if (is_edge && order.arrive != nullptr) strip_order_arrive(order, lane, true); // the halo exchange may pack this strip's columns
 #ifdef WX_MARCH_TIMING
   if (lane == 0) {
     cycles[2 * ((size_t)seg * n_strips + strip)] = t_begin;
@@ -311,16 +291,12 @@ inline int march_dry_strips(const Geo &g) { return (g.X + MOUT - 1) / MOUT; }
 // A launch covers the strips [strip_lo, strip_lo + strip_count) (strip_count < 0: all of them): the whole width normally, the edge
 // strips and the interior separately where a slab overlaps its halo exchange with compute (cf. launch_march_wet). The row
 // segmentation is the one of the whole width, so that every strip is cut the same way whichever launch computes it.
-// order (split iterations of a slab, StripOrder): the launch covers all strips, the edge strips first / last in dispatch order where the
-// shape has row bands (else in the plain order: the device-side hand-offs work either way). Returns the number of edge items of the launch
-// (= the arrivals a gate kernel has to wait for), 0 without an order.
-inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, const DryIn &in, const DryOut &out, bool write_disp, bool write_wall,
-                             hipStream_t stream, int strip_lo = 0, int strip_count = -1, int strip_lo2 = 0, int strip_count2 = 0, const StripOrder *order = nullptr,
-                             const VxTrack *vx = nullptr)
+inline void launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, const DryIn &in, const DryOut &out, bool write_disp, bool write_wall,
+                             hipStream_t stream, int strip_lo = 0, int strip_count = -1, int strip_lo2 = 0, int strip_count2 = 0, const VxTrack *vx = nullptr)
 {
   const int n_strips_all = march_dry_strips(g), n_first = strip_count < 0 ? n_strips_all : strip_count;
   const int n_strips = n_first + (strip_count2 > 0 ? strip_count2 : 0);
-  if (n_strips <= 0) return 0;
+  if (n_strips <= 0) return;
   int seg_rows = march_seg_rows(n_strips_all, g.Y);
   int n_seg = (g.Y + seg_rows - 1) / seg_rows, n_full = n_seg, n_half = 0, band_h = 0;
   if (g.Y % 8 == 0) {
@@ -340,18 +316,11 @@ inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, cons
       n_seg = 8 * (n_full + 2 * n_half);
     }
   }
-  StripOrder ord{};
-  if (order && order->mode != 0) {
-    ord = *order;
-    if (band_h == 0) ord.mode = 3;
-  }
-  const int edge_items = ord.mode != 0 ? (ord.nl + (n_strips_all - ord.nr0)) * n_seg : 0;
   VxTrack vt = vx ? *vx : VxTrack{nullptr, nullptr, 0.0f, 0, 0};
   if (vx && vx->zone_l < vx->zone_r) { // the watched zone arrives in COLUMNS: this kernel's strips are MOUT columns wide
     vt.zone_l = (vx->zone_l + MOUT - 1) / MOUT;
     vt.zone_r = vx->zone_r / MOUT;
   }
-  // (an ordered launch groups edge and interior strips separately: with one wave per workgroup the count is the same)
   const dim3 grid(8 * ((n_strips * n_seg + 7) / 8));
   static bool dbg = wx_tune_env("WX_MARCH_DEBUG") != nullptr;
   if (dbg) {
@@ -361,10 +330,10 @@ inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, cons
 #ifdef WX_MARCH_TIMING
   static unsigned long long *cyc = nullptr;
   static int calls = 0;
-  if (!cyc && hipMalloc((void **)&cyc, 16 * (size_t)n_strips_all * n_seg) != hipSuccess) return 0;
-#define WX_LAUNCH_M(D, W, Q) hipLaunchKernelGGL((k_march_dry<D, W, Q>), grid, dim3(64), 0, stream, g, u, ctx, in, out, n_strips, seg_rows, n_full, n_half, band_h, n_seg, strip_lo, n_first, strip_lo2, ord, vt, cyc)
+  if (!cyc && hipMalloc((void **)&cyc, 16 * (size_t)n_strips_all * n_seg) != hipSuccess) return;
+#define WX_LAUNCH_M(D, W, Q) hipLaunchKernelGGL((k_march_dry<D, W, Q>), grid, dim3(64), 0, stream, g, u, ctx, in, out, n_strips, seg_rows, n_full, n_half, band_h, n_seg, strip_lo, n_first, strip_lo2, vt, cyc)
 #else
-#define WX_LAUNCH_M(D, W, Q) hipLaunchKernelGGL((k_march_dry<D, W, Q>), grid, dim3(64), 0, stream, g, u, ctx, in, out, n_strips, seg_rows, n_full, n_half, band_h, n_seg, strip_lo, n_first, strip_lo2, ord, vt)
+#define WX_LAUNCH_M(D, W, Q) hipLaunchKernelGGL((k_march_dry<D, W, Q>), grid, dim3(64), 0, stream, g, u, ctx, in, out, n_strips, seg_rows, n_full, n_half, band_h, n_seg, strip_lo, n_first, strip_lo2, vt)
 #endif
   const bool quiet = !(u.userInputType >= 1) && !(u.airplaneValues[3] < 0.0f || u.airplaneValues[3] > 0.9f);
 #define WX_LAUNCH_MQ(D, W) \
@@ -397,7 +366,6 @@ inline int launch_march_dry(const Geo &g, const Uni &u, const FullCtx *ctx, cons
     }
   }
 #endif
-  return edge_items;
 }
 
 } // namespace wx

@@ -128,7 +128,6 @@ int wx_copy_state(wx_sim *dst, wx_sim *src)
     dst->err = "wx_copy_state: src: " + src->err;
     return rc;
   }
-  settle_edges(dst);
   if (dst->comm_stream) HIPCHK(dst, hipStreamSynchronize(dst->comm_stream));
   HIPCHK(dst, hipStreamSynchronize(dst->stream));
   StateCopyPlan plan;

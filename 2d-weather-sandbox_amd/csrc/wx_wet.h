@@ -426,11 +426,11 @@ struct WetKArgs {
   float iterNum;
   WetIn in;
   WetOut out;
-  WetFixList fix[2]; // [1]: the edge strips' own list in a split iteration (StripOrder::edge_list)
+  WetFixList fix;
   int n_strips, strip_lo, n_strips_all;
   WetSegs segs;
   int split_at, strip_lo2;
-  StripOrder order;
+  int edge_prio; // issue priority of the waves (edge_wave_prio, wx_tile.h): != 0 only in the edge group of a split iteration
   VxTrack vx;
 };
 // one member's slot of an ensemble's device table
@@ -443,8 +443,8 @@ static_assert(sizeof(WetEnsSlot) % 16 == 0, "table slots keep the 16-byte alignm
 // QUIET: no brush input and no airplane event in this iteration (the host looks at the uniforms): advection_cell without those sections.
 template <bool OPT_OUT, bool HAS_FB, bool QUIET>
 __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(const FullCtx *__restrict__ ctx, float iterNum, WetIn in_arg, WetOut out_arg,
-                                                                    WetFixList fix_arg, WetFixList fix_edge_arg, int n_strips, int strip_lo,
-                                                                    int n_strips_all, WetSegs segs, int split_at, int strip_lo2, StripOrder order_arg, VxTrack vx_arg)
+                                                                    WetFixList fix_arg, int n_strips, int strip_lo,
+                                                                    int n_strips_all, WetSegs segs, int split_at, int strip_lo2, int edge_prio_arg, VxTrack vx_arg)
 {
   typedef WetKArgs KArgs; // layout of the kernel-argument segment (the parameter list as a struct)
   // The ~22 plane pointers are read from the kernel-argument segment (constant address space) where they are used: separate
@@ -468,7 +468,7 @@ __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet(
 // copy in front of the launch), read through the constant address space exactly as the lone kernel reads its kernel-argument segment:
 // the row loop keeps its scalar loads where it has them, and the scalars the body names directly come from the same slot. gridDim.x is a
 // multiple of 8 (blockIdx.x & 7 is still the XCD) sized for the member with the most segments; the surplus workgroups of the others
-// exit at once. Whole-domain members, no split order. HAS_FB as on a lone handle: the members of a launch all hand in feedback textures
+// exit at once. Whole-domain members, no edge group. HAS_FB as on a lone handle: the members of a launch all hand in feedback textures
 // (their droplets ran in the iteration before) or none does -- the driver partitions by it.
 template <bool OPT_OUT, bool HAS_FB, bool QUIET>
 __global__ __launch_bounds__(64 * WX_WET_WPB, WX_WET_MINWAVES) void k_march_wet_ens(const WetEnsSlot *__restrict__ table)
@@ -658,11 +658,11 @@ __global__ __launch_bounds__(256) void k_wet_fix_ens(const WetEnsSlot *__restric
   // handing it pointers into the table instead changes ITS code -- and with it the lone kernel's)
   const WetIn in = sl.ka.in;
   const WetOut out = sl.ka.out;
-  int *__restrict__ count = sl.ka.fix[0].count;
-  const int2 *__restrict__ cells = sl.ka.fix[0].cells;
-  const int cap = sl.ka.fix[0].cap;
+  int *__restrict__ count = sl.ka.fix.count;
+  const int2 *__restrict__ cells = sl.ka.fix.cells;
+  const int cap = sl.ka.fix.cap;
   int *__restrict__ overflow = sl.overflow;
-  int *__restrict__ hint = sl.ka.fix[0].hint;
+  int *__restrict__ hint = sl.ka.fix.hint;
 #include "wx_wet_fix_body.h"
 }
 
@@ -872,25 +872,16 @@ inline WetLaunch wet_shape_halved(const WetLaunch &w)
   return h;
 }
 
-// order (split iterations of a slab, StripOrder): returns the number of edge items of the launch (= the arrivals a gate kernel waits for)
-inline int launch_march_wet(const WetLaunch &w, float iterNum, const FullCtx *ctx, const WetIn &in, const WetOut &out, const WetFixList &fix,
+// edge_prio: the issue priority of the launch's waves (the edge group of a split iteration, edge_wave_prio; 0: none)
+inline void launch_march_wet(const WetLaunch &w, float iterNum, const FullCtx *ctx, const WetIn &in, const WetOut &out, const WetFixList &fix,
                              bool opt_out, bool quiet, hipStream_t stream, int strip_lo = 0, int strip_count = -1, int strip_lo2 = 0, int strip_count2 = 0,
-                             const StripOrder *order = nullptr, const WetFixList *fix_edge = nullptr, const VxTrack *vx = nullptr)
+                             int edge_prio = 0, const VxTrack *vx = nullptr)
 {
   // (strip_count2 > 0: a second strip range in the same launch -- the two edges of a slab)
   const int ns1 = strip_count < 0 ? w.n_strips : strip_count, ns = ns1 + (strip_count2 > 0 ? strip_count2 : 0);
-  if (ns <= 0) return 0;
-  StripOrder ord{};
-  if (order && order->mode != 0) ord = *order; // (an ordered launch covers the whole width: strip_lo 0, all strips)
+  if (ns <= 0) return;
   // 8 XCDs x (workgroups of the largest column block) x segments; surplus workgroups / waves exit at once
-  int groups = ((w.segs.bands ? ns : (ns + 7) / 8) + WX_WET_WPB - 1) / WX_WET_WPB;
-  if (ord.mode != 0 && ord.mode != 4) { // edge and interior strips are grouped into workgroups separately: up to one more group per XCD
-    groups = 0;
-    for (int k = 0; k < 8; k++) {
-      const int a = w.segs.bands ? 0 : (k * ns) >> 3, b = w.segs.bands ? ns : ((k + 1) * ns) >> 3;
-      groups = std::max(groups, strip_order_groups(ord, a, b, WX_WET_WPB));
-    }
-  }
+  const int groups = ((w.segs.bands ? ns : (ns + 7) / 8) + WX_WET_WPB - 1) / WX_WET_WPB;
   const dim3 grid(8 * groups * w.segs.n_seg);
   static bool dbg = wx_tune_env("WX_MARCH_DEBUG") != nullptr;
   if (dbg) {
@@ -899,14 +890,13 @@ inline int launch_march_wet(const WetLaunch &w, float iterNum, const FullCtx *ct
     dbg = false;
   }
   const bool has_fb = in.fb != nullptr;
-  const WetFixList fe = fix_edge ? *fix_edge : fix;
   VxTrack vt = vx ? *vx : VxTrack{nullptr, nullptr, 0.0f, 0, 0};
   if (vx && vx->zone_l < vx->zone_r) { // the watched zone arrives in COLUMNS: this kernel's strips are WOUT columns wide
     vt.zone_l = (vx->zone_l + WOUT - 1) / WOUT;
     vt.zone_r = vx->zone_r / WOUT;
   }
 #define WX_LAUNCH_W(O, F, Q) \
-  hipLaunchKernelGGL((k_march_wet<O, F, Q>), grid, dim3(64 * WX_WET_WPB), 0, stream, ctx, iterNum, in, out, fix, fe, ns, strip_lo, w.n_strips, w.segs, ns1, strip_lo2, ord, vt)
+  hipLaunchKernelGGL((k_march_wet<O, F, Q>), grid, dim3(64 * WX_WET_WPB), 0, stream, ctx, iterNum, in, out, fix, ns, strip_lo, w.n_strips, w.segs, ns1, strip_lo2, edge_prio, vt)
 #define WX_LAUNCH_WQ(O, F) \
   do { if (quiet) WX_LAUNCH_W(O, F, true); else WX_LAUNCH_W(O, F, false); } while (0)
   if (opt_out) {
@@ -916,7 +906,6 @@ inline int launch_march_wet(const WetLaunch &w, float iterNum, const FullCtx *ct
   }
 #undef WX_LAUNCH_WQ
 #undef WX_LAUNCH_W
-  return (ord.mode != 0 && ord.mode != 4) ? (ord.nl + (w.n_strips - ord.nr0)) * w.segs.n_seg * (w.segs.bands ? 8 : 1) : 0;
 }
 
 // the fix pass of a launch group: every list entry recomputed exactly, spread over the chip (exits at once while the list is empty)

@@ -3,9 +3,8 @@
 // address space; ctx, iterNum, n_strips, strip_lo, n_strips_all, segs, split_at, strip_lo2 (kernel arguments, or read from the block).
   const __attribute__((address_space(4))) WetIn &in = *(const __attribute__((address_space(4))) WetIn *)(ka_c + offsetof(KArgs, in));
   const __attribute__((address_space(4))) WetOut &out = *(const __attribute__((address_space(4))) WetOut *)(ka_c + offsetof(KArgs, out));
-  // (the split-iteration order likewise: read where it is used -- prologue and epilogue --, nothing of it lives in the row loop)
-  const __attribute__((address_space(4))) StripOrder &order_c = *(const __attribute__((address_space(4))) StripOrder *)(ka_c + offsetof(KArgs, order));
-#define WX_ORDER() (StripOrder{order_c.mode, order_c.nl, order_c.nr0, order_c.arrive, order_c.epoch, order_c.epoch_want, order_c.edge_list, order_c.prio})
+  // (the edge group's issue priority likewise: read where it is used -- the prologue --, nothing of it lives in the row loop)
+  const int edge_prio = *(const __attribute__((address_space(4))) int *)(ka_c + offsetof(KArgs, edge_prio));
   __shared__ WetRing rings[WX_WET_WPB];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   WetRing &rg = rings[wave];
@@ -27,29 +26,14 @@
   const int n_seg = segs.n_seg, k = blockIdx.x & 7, j = blockIdx.x >> 3;
   const bool bands = segs.bands != 0;
   const int sk0 = bands ? 0 : (k * n_strips) >> 3, nk = bands ? n_strips : (((k + 1) * n_strips) >> 3) - sk0, gk = (nk + WX_WET_WPB - 1) / WX_WET_WPB;
-  int seg, strip;
-  bool is_edge = false; // (wave-uniform) a split iteration's edge strip: waits for the ghost columns / reports when it is done
-  bool sig_edge = false, edge_list = false;
-  const int order_mode = WX_ORDER().mode;
-  if (order_mode == 0 || order_mode == 4) {
-    if (j >= gk * n_seg) return;
-    seg = j / gk;
-    const int sloc = (j - seg * gk) * WX_WET_WPB + wave;
-    if (sloc >= nk) return;
-    // (a launch may cover two strip ranges -- the left and the right edge strips of a slab: the first split_at strips start at strip_lo,
-    // the others at strip_lo2)
-    const int sidx = sk0 + sloc;
-    strip = sidx < split_at ? strip_lo + sidx : strip_lo2 + (sidx - split_at);
-    is_edge = order_mode == 4; // (the edge group of the two-launch protocol: every strip of the launch is an edge strip -- issue priority only)
-  } else { // one launch over ALL strips, the edge strips first (or last) in dispatch order (StripOrder, wx_tile.h)
-    const StripOrder order = WX_ORDER();
-    StripPick pk;
-    if (!strip_order_pick(order, sk0, sk0 + nk, n_seg, WX_WET_WPB, wave, j, seg, pk)) return;
-    strip = pk.strip;
-    is_edge = pk.is_edge;
-    sig_edge = is_edge && order.arrive != nullptr;
-    edge_list = is_edge && order.edge_list != 0;
-  }
+  if (j >= gk * n_seg) return;
+  const int seg = j / gk;
+  const int sloc = (j - seg * gk) * WX_WET_WPB + wave;
+  if (sloc >= nk) return;
+  // (a launch may cover two strip ranges -- the left and the right edge strips of a slab: the first split_at strips start at strip_lo,
+  // the others at strip_lo2)
+  const int sidx = sk0 + sloc;
+  const int strip = sidx < split_at ? strip_lo + sidx : strip_lo2 + (sidx - split_at);
   const int item = ((bands ? k * n_seg : 0) + seg) * n_strips_all + strip;
   const int band_lo = bands ? (int)(((long long)k * g.Y) >> 3) : 0, band_hi = bands ? (int)(((long long)(k + 1) * g.Y) >> 3) : g.Y;
   const int c_out = strip * WOUT + lane - WLO; // output column of this lane (may be >= X in the last strip, < 0 in the first)
@@ -59,15 +43,8 @@
   unsigned lo12 = (unsigned)col * 12u; // (feedback texels)
   unsigned so4 = lane_out ? (unsigned)c_out * 4u : 0u, so8 = so4 * 2u, so16 = so4 * 4u;    // ... of the stored column
   const int y_lo = band_lo + segs.start[seg], y_hi = min(band_lo + segs.start[seg + 1], band_hi);
-  if (y_lo >= y_hi) { // (an empty segment of a clipped band still counts as an edge item that is done)
-    if (sig_edge) strip_order_arrive(WX_ORDER(), lane, false);
-    return;
-  }
-  if (is_edge) { // the ghost columns this strip reads are being written by the exchange
-    const StripOrder order = WX_ORDER();
-    if (order.epoch != nullptr) strip_order_wait(order);
-    strip_order_prio(order.prio);
-  }
+  if (y_lo >= y_hi) return; // (an empty segment of a clipped band)
+  edge_wave_prio(edge_prio); // (!= 0 only in the edge group of a split iteration, wx_tile.h)
 #define WX_WALL_RAW (reinterpret_cast<const int *>(in.wall))
   (void)item;
 
@@ -349,10 +326,8 @@
 #ifdef WX_ABL_NOFIX // (timing-only ablation builds produce garbage velocities: keep them from flooding the exact path)
           n_add = 0;
 #endif
-          // (the list: read from the kernel-argument segment HERE, in the rare branch -- nothing of it is live in the loop; the edge strips
-          // of a split iteration have a list of their own, consumed on the comm stream before the halo is packed)
-          const __attribute__((address_space(4))) WetFixList &fix =
-              *(const __attribute__((address_space(4))) WetFixList *)(ka_c + offsetof(KArgs, fix) + (edge_list ? sizeof(WetFixList) : 0));
+          // (the list: read from the kernel-argument segment HERE, in the rare branch -- nothing of it is live in the loop)
+          const __attribute__((address_space(4))) WetFixList &fix = *(const __attribute__((address_space(4))) WetFixList *)(ka_c + offsetof(KArgs, fix));
           if (fix.fastest) atomicMax(fix.fastest, __float_as_int(m)); // (m >= 0.9, +Inf for a NaN or Inf component: the bit patterns of positive floats order like ints)
           if (n_add) {
             int at = atomicAdd(fix.count, n_add);
@@ -483,8 +458,6 @@
     const __attribute__((address_space(4))) VxTrack &vc = *(const __attribute__((address_space(4))) VxTrack *)(ka_c + offsetof(KArgs, vx));
     vx_track_commit(VxTrack{vc.max_bits, vc.violation, vc.limit, vc.zone_l, vc.zone_r, vc.limit_in}, vx_seen, lane, strip);
   }
-  if (sig_edge) strip_order_arrive(WX_ORDER(), lane, true); // the halo exchange may pack this strip's columns
-#undef WX_ORDER
 #ifdef WX_WET_TIMING
   if (lane == 0) {
     out.cycles[2 * (size_t)item] = t_begin;

@@ -30,7 +30,7 @@
 using namespace wx;
 
 #ifndef WX_SPLIT_PRIO
-#define WX_SPLIT_PRIO 0 // s_setprio level of the edge waves of a split iteration (StripOrder::prio)
+#define WX_SPLIT_PRIO 0 // s_setprio level of the edge waves of a split iteration (edge_wave_prio, wx_tile.h)
 #endif
 
 namespace {
@@ -136,7 +136,6 @@ struct Options {
   int check_launches = 0;     // WX_OPT_CHECK_LAUNCHES: synchronise and check after every kernel launch of wx_step (debugging)
   int pool_exact = 0;    // WX_OPT_POOL_EXACT
   bool exchange_in_order = false; // WX_OPT_EXCHANGE_OVERLAP 0: the library's transport keeps the exchange on the compute stream
-  int split_launch = 0;          // WX_OPT_SPLIT_LAUNCH: 0 (default) = the two launch groups of rounds 2-4; 1 = one ordered launch (round 5: measured, not faster)
   bool lazy_water0 = true;       // WX_OPT_WATER0_ON_DEMAND (see RunState::water0_pending)
 };
 
@@ -190,29 +189,17 @@ struct Water0 {
 
 // Split iterations and the overlap of the halo exchange with compute (wx_set_comm_stream / wx_step_overlap). Iterations change most of
 // this; none of it is snapshotted by the placement search.
+// The iteration before an exchange and the one after it run as two launch groups, edge strips / interior. The groups read the same
+// inputs and write disjoint columns, so the edge group -- a handful of strips that cannot fill the chip -- runs on a high-priority
+// stream of its own NEXT TO the interior group instead of in front of it (in order it cost a 2132-column slab +0.045 ms per iteration,
+// profiles/r04_slab_protocol_cost.txt). Events alone order the streams: ev_fork / ev_join put the edge stream behind, and the compute
+// stream behind, both groups; the comm stream packs behind ev_edges; whoever reads ghost columns first waits for ev_unpacked.
 struct Split {
-  hipEvent_t ev_edges = nullptr, ev_unpacked = nullptr; // edge strips of the last iteration done (compute stream) / ghosts written (comm stream)
+  hipEvent_t ev_edges = nullptr, ev_unpacked = nullptr; // edge strips of the last iteration done (edge stream) / ghosts written (comm stream)
   bool edges_recorded = false;   // ev_edges was recorded behind the edge strips of the latest iteration
   bool unpack_pending = false;   // ghost columns were unpacked on the comm stream since the compute stream last waited
-  // Split iterations (edge strips / interior, wx_step_overlap): the two launch groups read the same inputs and write disjoint columns,
-  // so the edge group -- a handful of strips that cannot fill the chip -- runs on a stream of its own NEXT TO the interior group
-  // instead of in front of it (in order it cost a 2132-column slab +0.045 ms per iteration, profiles/r04_slab_protocol_cost.txt)
   hipStream_t edge_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // Round 5: a split iteration as ONE ordered launch with device-side hand-offs (StripOrder, wx_tile.h) instead of two launch groups on two
-  // streams: sync_words[0] = arrivals of edge items (cumulative; a gate kernel on the comm stream waits for arrive_target),
-  // sync_words[1] = the ghost epoch (bumped on the comm stream behind every unpack; edge strips dispatched last poll for epoch_host)
-  unsigned *sync_words = nullptr;
-  unsigned arrive_target = 0, epoch_host = 0;
-  bool gate_pending = false;     // the latest iteration's edge strips report through sync_words[0]; their exact-path list (edge_fix) is still
-                                 // to be consumed -- by the halo pack on the comm stream, else by settle_edges on the compute stream
-  bool gate_wet = false;         // ... and it was the wet kernel (there is a list to consume)
-  bool check = false;            // a split iteration ran since the give-up flag (sync_words[2]) was last looked at
-  bool gate_passed = false;      // the comm stream already holds the gate of the latest iteration: a further pack of the same exchange is ordered behind it
-  WetIn gate_in{};
-  WetOut gate_out{};
-  float gate_iter = 0.f;
-  bool gate_opt_out = false;
   FixList edge_fix;              // the edge group's own list of exact-path cells (the groups run concurrently)
 };
 
@@ -779,47 +766,11 @@ static void wait_unpacked(wx_sim *s)
   s->split.unpack_pending = false;
 }
 
-// the edge strips' own exact-path list (wet kernel; created by the first split iteration): a few strips' worth of cells
-static int edge_list_create(wx_sim *s, const char *whose)
-{
-  const size_t cap = std::min<size_t>(std::max<size_t>((size_t)s->Y * 8 * 64, 1u << 14), 1u << 20);
-  if (!s->split.edge_fix.create(s->stream, cap, 4, 0, false)) return fail(s, WX_E_NOMEM, "wx_step: the edge %s exact-path cell list", whose);
-  return WX_OK;
-}
-// device words of the ordered split launch + the edge strips' own exact-path list (created by the first split iteration)
-static int split_launch_ready(wx_sim *s, bool need_fix_list)
-{
-  if (!s->split.sync_words) {
-    if (hipMalloc((void **)&s->split.sync_words, 4 * sizeof(unsigned)) != hipSuccess || hipMemsetAsync(s->split.sync_words, 0, 4 * sizeof(unsigned), s->stream) != hipSuccess)
-      return fail(s, WX_E_NOMEM, "wx_step: the split launch's device words");
-    s->split.arrive_target = s->split.epoch_host = 0;
-  }
-  if (need_fix_list && !s->split.edge_fix.cells) {
-    if (int rc = edge_list_create(s, "strips'")) return rc;
-  }
-  return WX_OK;
-}
-// The edge strips of the latest split iteration left exact-path cells on their own list and nobody has packed the halo since (a host
-// that asked for WX_OVERLAP_EDGES_FIRST and then did something else): consume the list on the compute stream -- it is ordered behind
-// the whole launch, so no gate is needed -- before anything looks at those cells.
-static void settle_edges(wx_sim *s)
-{
-  if (!s->split.gate_pending) return;
-  if (s->split.gate_wet)
-    launch_wet_fix(s->split.gate_iter, s->full_ctx, s->split.gate_in, s->split.gate_out, s->split.edge_fix.wet(&s->state->fastest_bits), &s->state->fix_overflow, s->split.gate_opt_out,
-                   s->stream, 64);
-  s->split.gate_pending = false;
-}
-// comm stream: the ghost columns (and whatever else an exchange writes) are in place -- the event for the compute stream's stream-ordered
-// consumers, the epoch word for edge strips that are already resident and polling
+// comm stream: the ghost columns (and whatever else an exchange writes) are in place -- the event for the compute stream's consumers
 static int mark_unpacked(wx_sim *s, hipStream_t st)
 {
   HIPCHK(s, hipEventRecord(s->split.ev_unpacked, st));
   s->split.unpack_pending = true;
-  if (s->split.sync_words) {
-    s->split.epoch_host += 1;
-    hipLaunchKernelGGL(k_strip_epoch, dim3(1), dim3(1), 0, st, s->split.sync_words + 1, s->split.epoch_host);
-  }
   return WX_OK;
 }
 
@@ -844,8 +795,10 @@ static int edge_stream_ready(wx_sim *s, bool need_fix_list)
     HIPCHK(s, hipEventCreateWithFlags(&s->split.ev_fork, hipEventDisableTiming));
     HIPCHK(s, hipEventCreateWithFlags(&s->split.ev_join, hipEventDisableTiming));
   }
-  if (need_fix_list && !s->split.edge_fix.cells)
-    if (int rc = edge_list_create(s, "group's")) return rc;
+  if (need_fix_list && !s->split.edge_fix.cells) { // (wet kernel: a few strips' worth of cells)
+    const size_t cap = std::min<size_t>(std::max<size_t>((size_t)s->Y * 8 * 64, 1u << 14), 1u << 20);
+    if (!s->split.edge_fix.create(s->stream, cap, 4, 0, false)) return fail(s, WX_E_NOMEM, "wx_step: the edge group's exact-path cell list");
+  }
   return WX_OK;
 }
 
@@ -853,68 +806,32 @@ static int edge_stream_ready(wx_sim *s, bool need_fix_list)
 // strips; 1 = edge strips first, event, interior (last iteration before an exchange); 2 = interior first, wait for the unpack event,
 // edge strips (first iteration after an exchange); 3 = a one-iteration period: both. The edge strips -- [0, nl) and [nr0, n_strips) --
 // are every output column wx_halo_pack reads ([halo, 2*halo) and its mirror) and every strip that reads ghost columns.
-// launch(stream, lo0, cnt0, lo1, cnt1, order, edge_group) enqueues the kernel over one strip range or two (cnt0 < 0: all strips) and returns
-// the number of edge items an ordered launch (order != NULL) will report. edge_list: the kernel records exact-path cells (the wet kernel):
-// the edge strips then have a list of their own (Split::edge_fix), which the launch of an edge group or of an ordered launch fills.
-template <class Launch> int split_iteration(wx_sim *s, int edge_mode, int nl, int nr0, int n_strips, bool edge_list, Launch &&launch)
+// launch(stream, lo0, cnt0, lo1, cnt1, edge_group) enqueues the kernel over one strip range or two (cnt0 < 0: all strips).
+// need_fix_list: the kernel records exact-path cells (the wet kernel): the edge group then has a list of its own (Split::edge_fix).
+template <class Launch> int split_iteration(wx_sim *s, int edge_mode, int nl, int nr0, int n_strips, bool need_fix_list, Launch &&launch)
 {
   Split &sp = s->split;
   if (edge_mode == 0 || s->halo == 0 || nl >= nr0) {
     if (edge_mode & 2) wait_unpacked(s);
-    launch(s->stream, 0, -1, 0, 0, nullptr, false);
-  } else if (s->opt.split_launch) {
-    // ONE launch over all strips (round 5): the edge strips first in dispatch order when an exchange follows (they report on a device
-    // word the comm stream's gate kernel polls), last when one precedes (they poll the epoch word the comm stream bumps behind the
-    // unpack). No second stream, no join events, one fix pass on this stream; the edge strips' own exact-path list is consumed on the
-    // comm stream in front of the pack (halo_pack_impl) -- B's strips next to them are ordered behind that through the epoch too.
-    if (int rc = split_launch_ready(s, edge_list)) return rc;
-    StripOrder ord{};
-    ord.mode = (edge_mode & 1) ? 1 : 2;
-    ord.nl = nl;
-    ord.nr0 = nr0;
-    if (edge_mode == 3) wait_unpacked(s); // (a one-iteration period: the whole launch behind the unpack, the edge strips first all the same)
-    if ((edge_mode & 2) && sp.unpack_pending) {
-      ord.epoch = sp.sync_words + 1;
-      ord.epoch_want = sp.epoch_host;
-      // (the interior strips bordering the edge strips read four of their columns -- cells the comm stream's fix pass may still be
-      // rewriting: they wait with the edges)
-      if (edge_list && ord.nl + 1 < ord.nr0 - 1) {
-        ord.nl += 1;
-        ord.nr0 -= 1;
-      }
-      sp.unpack_pending = false; // (this launch waits on the device; everything behind it on the stream is ordered behind it)
-    }
-    if (edge_mode & 1) {
-      ord.arrive = sp.sync_words;
-      ord.edge_list = edge_list ? 1 : 0;
-    }
-    ord.prio = WX_SPLIT_PRIO;
-    if (const char *e = wx_tune_env("WX_SPLIT_PRIO")) ord.prio = atoi(e);
-    sp.check = true;
-    const int items = launch(s->stream, 0, -1, 0, 0, &ord, false);
-    if (edge_mode & 1) {
-      sp.arrive_target += (unsigned)items;
-      sp.gate_pending = true;
-      sp.gate_wet = edge_list;
-    }
+    launch(s->stream, 0, -1, 0, 0, false);
   } else {
-    // (rounds 2-4, WX_OPT_SPLIT_LAUNCH 0) The edge group on its own stream, the interior group on the compute stream, side by side: the edge stream starts behind
+    // The edge group on its own stream, the interior group on the compute stream, side by side: the edge stream starts behind
     // everything the compute stream holds so far (and behind the unpack where the ghosts are still in flight), the compute stream
     // goes on behind both groups. What the comm stream waits for before it packs (ev_edges) is the edge group alone.
-    if (int rc = edge_stream_ready(s, edge_list)) return rc;
+    if (int rc = edge_stream_ready(s, need_fix_list)) return rc;
     hipEventRecord(sp.ev_fork, s->stream);
     hipStreamWaitEvent(sp.edge_stream, sp.ev_fork, 0);
     if ((edge_mode & 2) && sp.unpack_pending) {
       hipStreamWaitEvent(sp.edge_stream, sp.ev_unpacked, 0);
       sp.unpack_pending = false; // (the compute stream joins the edge stream below)
     }
-    launch(sp.edge_stream, 0, nl, nr0, n_strips - nr0, nullptr, true); // (both edges in one launch)
+    launch(sp.edge_stream, 0, nl, nr0, n_strips - nr0, true); // (both edges in one launch)
     if (edge_mode & 1) {
       hipEventRecord(sp.ev_edges, sp.edge_stream);
       sp.edges_recorded = true;
     }
     hipEventRecord(sp.ev_join, sp.edge_stream);
-    launch(s->stream, nl, nr0 - nl, 0, 0, nullptr, false);
+    launch(s->stream, nl, nr0 - nl, 0, 0, false);
     hipStreamWaitEvent(s->stream, sp.ev_join, 0);
   }
   return WX_OK;
@@ -1026,32 +943,17 @@ int march_wet_launch(wx_sim *s, const WetIter &wi, int edge_mode)
     // one launch group: marching kernel over a strip range (or two, both in ONE launch) -> the fix pass over what it recorded (leaves the
     // list empty). A wave records -- and the fix pass rewrites -- only output cells of its own strip: the groups of a split iteration never
     // write each other's columns, and the edge group (on its own stream, half-height segments: done before the interior) has its own list
-    auto launch = [&](hipStream_t st, int lo0, int cnt0, int lo1, int cnt1, const StripOrder *ord, bool edge_group) {
-      if (ord) { // one ordered launch: both lists, one fix pass on this stream; the edge strips' list is consumed in front of the halo pack
-        const WetFixList fix2 = s->split.edge_fix.wet(&s->state->fastest_bits);
-        const int items = launch_march_wet(shape, iter, s->full_ctx, in, out, fix, opt_out, quiet, st, lo0, cnt0, lo1, cnt1, ord, &fix2, &vt);
-        launch_wet_fix(iter, s->full_ctx, in, out, fix, &s->state->fix_overflow, opt_out, st, 0);
-        if (ord->arrive) { // ... by whoever passes the gate (halo_pack_impl, settle_edges), with the arguments of this iteration
-          s->split.gate_in = in;
-          s->split.gate_out = out;
-          s->split.gate_iter = iter;
-          s->split.gate_opt_out = opt_out;
-        }
-        return items;
-      }
+    auto launch = [&](hipStream_t st, int lo0, int cnt0, int lo1, int cnt1, bool edge_group) {
       bool halved = edge_group;
-      StripOrder eo{}; // the edge group of the two-launch protocol: its waves may get a higher issue priority (StripOrder::prio; mode 4)
-      if (halved) {
-        eo.mode = 4;
-        eo.prio = WX_SPLIT_PRIO;
-        if (const char *e = wx_tune_env("WX_SPLIT_PRIO")) eo.prio = atoi(e);
+      int edge_prio = 0; // the edge group's waves may get a higher issue priority (edge_wave_prio, wx_tile.h)
+      if (edge_group) {
+        edge_prio = WX_SPLIT_PRIO;
+        if (const char *e = wx_tune_env("WX_SPLIT_PRIO")) edge_prio = atoi(e);
         if (const char *e = wx_tune_env("WX_SPLIT_HALVE")) halved = atoi(e) != 0;
-        if (eo.prio == 0) eo.mode = 0;
       }
       const WetFixList fl = edge_group ? s->split.edge_fix.wet(&s->state->fastest_bits) : fix;
-      launch_march_wet(halved ? wet_shape_halved(shape) : shape, iter, s->full_ctx, in, out, fl, opt_out, quiet, st, lo0, cnt0, lo1, cnt1, eo.mode ? &eo : nullptr, nullptr, &vt);
+      launch_march_wet(halved ? wet_shape_halved(shape) : shape, iter, s->full_ctx, in, out, fl, opt_out, quiet, st, lo0, cnt0, lo1, cnt1, edge_prio, &vt);
       launch_wet_fix(iter, s->full_ctx, in, out, fl, &s->state->fix_overflow, opt_out, st, halved ? 64 : 0);
-      return 0;
     };
     const int nl = s->halo > 0 ? (2 * s->halo - 1) / WOUT + 1 : 0, nr0 = s->halo > 0 ? (s->X - 2 * s->halo) / WOUT : shape.n_strips;
     if (int rc = split_iteration(s, edge_mode, nl, nr0, shape.n_strips, true, launch)) return rc;
@@ -1138,8 +1040,8 @@ int iterate_dry(wx_sim *s, bool write_disp, int edge_mode = 0)
     const int n_strips = march_dry_strips(s->geo);
     const int nl = s->halo > 0 ? (2 * s->halo - 1) / MOUT + 1 : 0, nr0 = s->halo > 0 ? (s->X - 2 * s->halo) / MOUT : n_strips;
     const VxTrack vt = vx_track(s);
-    auto launch = [&](hipStream_t st, int lo0, int cnt0, int lo1, int cnt1, const StripOrder *ord, bool) {
-      return launch_march_dry(s->geo, s->uni, s->full_ctx, in, out, write_disp, !wall_const, st, lo0, cnt0, lo1, cnt1, ord, &vt);
+    auto launch = [&](hipStream_t st, int lo0, int cnt0, int lo1, int cnt1, bool) {
+      launch_march_dry(s->geo, s->uni, s->full_ctx, in, out, write_disp, !wall_const, st, lo0, cnt0, lo1, cnt1, &vt);
     };
     if (int rc = split_iteration(s, edge_mode, nl, nr0, n_strips, false, launch)) return rc;
     LAUNCH_CHECK(s, "march_dry");
@@ -1384,7 +1286,6 @@ void wx_destroy(wx_sim *s)
   s->fix.destroy();
   s->split.edge_fix.destroy();
   s->pair.destroy();
-  hipFree(s->split.sync_words);
   hipFree(s->emitted);
   hipFree(s->fb_rgba);
   hipFree(s->diag_table);
@@ -1636,7 +1537,6 @@ static bool step_runs_march_wet(const wx_sim *s) { return s->opt.fused && (s->p.
 // What a step settles before its first iteration -- wx_step_overlap, and wx_ensemble_step for the members it batches.
 static int step_begin(wx_sim *s, bool dry)
 {
-  settle_edges(s); // (the previous call ended with an edges-first iteration that no halo pack followed)
   if (s->copy_in_flight) { // a streamed frame still reads the display fields: order this step after it (device-side wait)
     HIPCHK(s, hipStreamWaitEvent(s->stream, s->ev_copy_done, 0));
     s->copy_in_flight = false;
@@ -1653,7 +1553,6 @@ static int step_begin(wx_sim *s, bool dry)
 static void step_begin_iterations(wx_sim *s, int n_iter)
 {
   s->split.edges_recorded = false;
-  if (n_iter > 0) s->split.gate_passed = false;
   if (n_iter > 0) s->run.water0_pending = false; // (the inputs of the previous step's last iteration are about to be overwritten)
 }
 // ... and what it leaves behind its last one
@@ -1864,10 +1763,6 @@ int wx_set_option(wx_sim *s, int option, int value)
     if (int rc = materialize_water0(s)) return rc;
     s->opt.lazy_water0 = value != 0;
     return WX_OK;
-  case WX_OPT_SPLIT_LAUNCH: // split iterations (wx_step_overlap): 1 = one ordered launch + device-side hand-offs, 0 = two launch groups on two streams
-    if (int rc = wx_sync(s)) return rc;
-    s->opt.split_launch = value != 0;
-    return WX_OK;
   case WX_OPT_EXCHANGE_OVERLAP: // (takes effect at the next wx_slab_step / wx_exchange / wx_group_step: transport_prepare)
     s->opt.exchange_in_order = value == 0;
     return WX_OK;
@@ -1920,18 +1815,6 @@ static int validate_ghost_flag(wx_sim *s)
                                  "faster than the margin of wx_slab_set_vx_bound allows, ghost columns were consumed faster than assumed and the slab may differ "
                                  "from the undecomposed run since (a velocity of 2 * halo - 8 = %d cells / iteration and more is reported wherever it occurs: from three halo widths "
                                  "inside the slab it reaches the ghost columns)", v, s->vx.cone - 5, s->vx.cone, std::max(1, 2 * s->halo - 8));
-    }
-  }
-  if (s->split.sync_words && s->split.check) { // did a device-side hand-off of a split iteration give up polling?
-    unsigned w[4] = {0, 0, 0, 0};
-    HIPCHK(s, hipMemcpyAsync(w, s->split.sync_words, 16, hipMemcpyDeviceToHost, s->stream));
-    HIPCHK(s, hipStreamSynchronize(s->stream));
-    s->split.check = false;
-    if (w[2]) {
-      HIPCHK(s, hipMemsetAsync(s->split.sync_words + 2, 0, 8, s->stream));
-      return fail(s, WX_E_STATE, "a device-side hand-off of a split iteration (edge strips <-> halo exchange) was not answered within its poll limit (%s; arrivals %u of %u "
-                                 "(gate wanted %u), epoch %u of %u): the exchange did not run or a peer is gone; the results since are invalid",
-                  w[2] == 1 ? "the gate kernel waiting for the edge strips" : "an edge strip waiting for the ghost columns", w[0], s->split.arrive_target, w[3], w[1], s->split.epoch_host);
     }
   }
   if (s->run.fix_check) { // did a marching iteration find more cells with |v| >= 0.9 than the exact-path list holds?
@@ -2311,7 +2194,6 @@ int wx_slab_vx_take(wx_sim *s, float *vmax)
   if (!s || !vmax) return WX_E_INVALID;
   DeviceScope dev_scope(s);
   if (!s->uploaded) return fail(s, WX_E_STATE, "wx_slab_vx_take before wx_upload");
-  settle_edges(s);
   wait_unpacked(s);
   if (s->vx.stale || s->vx.untracked) vx_scan_enqueue(s, s->stream, !s->vx.stale);
   int bits = 0;
@@ -2327,7 +2209,6 @@ int wx_sync(wx_sim *s)
 {
   if (!s) return WX_E_INVALID;
   DeviceScope dev_scope(s);
-  settle_edges(s);
   if (s->comm_stream) HIPCHK(s, hipStreamSynchronize(s->comm_stream));
   HIPCHK(s, hipStreamSynchronize(s->stream));
   return validate_ghost_flag(s);
@@ -2494,7 +2375,6 @@ int wx_read_rect(wx_sim *s, int field, int x, int y, int w, int h, void *dst, in
     HIPCHK(s, hipStreamSynchronize(s->stream));
     return WX_OK;
   }
-  settle_edges(s);
   wait_unpacked(s); // ghost columns written on the comm stream are part of what a readback sees
   if (int rc = validate_ghost_flag(s)) return rc;
   if (field == WX_FIELD_EMITTED) {
@@ -2566,7 +2446,6 @@ static int diag_enqueue(wx_sim *s)
   if (!s->uploaded) return fail(s, WX_E_STATE, "wx_diag_collect before wx_upload");
   if ((unsigned long long)s->Xg * (unsigned long long)s->Y >= 0xFFFFFFFFull)
     return fail(s, WX_E_INVALID, "wx_diag_collect: %d x %d cells: global cell indices are 32 bits wide", s->Xg, s->Y);
-  settle_edges(s);
   wait_unpacked(s); // (ghost columns are not read, but the droplet pool and a split iteration's edge strips are)
   if (int rc = validate_ghost_flag(s)) return rc;
   const size_t bytes = (size_t)wxd::SHARDS * wxd::T_WORDS * sizeof(unsigned long long);
@@ -2658,7 +2537,6 @@ int wx_stream_frame(wx_sim *s, int x, int y, int w, int h, void *host_dst)
     HIPCHK(s, hipEventCreateWithFlags(&s->ev_fields_ready, hipEventDisableTiming));
     HIPCHK(s, hipEventCreateWithFlags(&s->ev_copy_done, hipEventDisableTiming));
   }
-  settle_edges(s);
   wait_unpacked(s); // ghost columns written on the comm stream are part of what a frame shows
   const void *ptr[6];
   size_t texel[6];
@@ -2712,8 +2590,6 @@ int wx_set_comm_stream(wx_sim *s, void *hip_stream)
   if (s->ens) return fail(s, WX_E_STATE, "wx_set_comm_stream: the handle is a member of an ensemble (whole-domain members have no halo exchange)");
   DeviceScope dev_scope(s);
   HIPCHK(s, hipStreamSynchronize(s->stream));
-  settle_edges(s);
-  HIPCHK(s, hipStreamSynchronize(s->stream));
   if (s->comm_stream) HIPCHK(s, hipStreamSynchronize(s->comm_stream));
   s->comm_stream = (hipStream_t)hip_stream;
   s->split.edges_recorded = s->split.unpack_pending = false;
@@ -2721,16 +2597,12 @@ int wx_set_comm_stream(wx_sim *s, void *hip_stream)
     HIPCHK(s, hipEventCreateWithFlags(&s->split.ev_edges, hipEventDisableTiming));
     HIPCHK(s, hipEventCreateWithFlags(&s->split.ev_unpacked, hipEventDisableTiming));
   }
-  // (the epoch word has to exist before the first unpack on a side stream: an edge strip polls it for exactly that unpack)
-  if (hip_stream)
-    if (int rc = split_launch_ready(s, false)) return rc;
   return WX_OK;
 }
 
 void *wx_device_ptr(wx_sim *s, int field)
 {
   if (!s) return nullptr;
-  settle_edges(s);
   wait_unpacked(s); // whatever the caller enqueues on the compute stream next sees the unpacked ghost columns (and the exchanged lightning state)
   if (field == WX_FIELD_LIGHTNING) return s->state->lightning;
   if (field == WX_FIELD_EMITTED) return emitted_rect(s, 0, 0, s->X, s->Y) == WX_OK ? s->emitted : nullptr; // (whole grid, computed now)
@@ -2795,34 +2667,13 @@ static int halo_pack_impl(wx_sim *s, void *const dev_buf[2])
   HaloPtrs f{s->base[0], s->water[1], s->light[0], s->light[1], s->run.light_planar ? s->lp[0] : none, s->run.light_planar ? s->lp[1] : none, s->wall[0],
              s->pool.remote ? s->fb : nullptr, s->pool.remote ? s->dep : nullptr};
   hipStream_t st = exchange_stream(s);
-  if (st != s->stream && s->split.gate_pending && s->split.gate_wet) {
-    // ONE ordered launch of the WET kernel: its edge strips left exact-path cells on their own list. Consuming it HERE, on the comm
-    // stream, behind a gate kernel would let the pack start while the interior still marches -- built and measured in round 5, and
-    // withdrawn: k_wet_fix needs 652 bytes of scratch per lane, which the runtime hands out per dispatch ("use once") only when the
-    // queue can be given it -- seen to stall for SECONDS while the next iteration's edge strips were resident and polling for this very
-    // exchange (the poll limit turned the deadlock into an error; profiles/r05_slab_protocol_cost.txt). So the list is consumed on the
-    // compute stream behind the whole launch, and the pack waits for that: no overlap inside this iteration, none lost in the next.
-    settle_edges(s);
-    HIPCHK(s, hipEventRecord(s->split.ev_edges, s->stream));
-    s->split.edges_recorded = true;
-    HIPCHK(s, hipStreamWaitEvent(st, s->split.ev_edges, 0));
-    s->split.gate_passed = true;
-  } else if (st != s->stream && s->split.gate_pending) {
-    // the latest iteration was ONE ordered launch whose edge strips report on a device word: a one-wave gate kernel waits for them (the
-    // interior strips are still marching), then the pack may read (dry stencil: no exact-path list, every kernel here is scratch-free)
-    hipLaunchKernelGGL(k_strip_gate, dim3(1), dim3(64), 0, st, s->split.sync_words, s->split.arrive_target);
-    s->split.gate_pending = false;
-    s->split.gate_passed = true;
-  } else if (st != s->stream && s->split.gate_passed) {
-    // (the other side of the same exchange, packed by a call of its own: the gate is earlier in this stream)
-  } else if (st != s->stream) { // the packed columns are final behind ev_edges (or, without an edge-first step, behind everything enqueued so far)
+  if (st != s->stream) { // the packed columns are final behind ev_edges (or, without an edge-first step, behind everything enqueued so far)
     if (!s->split.edges_recorded) {
       HIPCHK(s, hipEventRecord(s->split.ev_edges, s->stream));
       s->split.edges_recorded = true;
     }
     HIPCHK(s, hipStreamWaitEvent(st, s->split.ev_edges, 0));
   }
-  settle_edges(s); // (an in-order pack: the edge strips' exact-path cells on the compute stream)
   ProfScope ps(s, K_HALO);
   int slots = 0;
   const HaloBufs hb = halo_bufs(s, dev_buf, true, &slots);

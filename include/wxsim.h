@@ -243,12 +243,7 @@ int wx_sync(wx_sim *s);
  *   needs precipitation's feedback texture); 0 = everything in order on the compute stream -- same results bit for bit (tests), and
  *   what the exact particle mode always does. */
 #define WX_OPT_EXCHANGE_OVERLAP 8
-/* WX_OPT_SPLIT_LAUNCH (slab handles with a comm stream): how wx_step_overlap runs a split iteration. 0 (DEFAULT) = the edge strips and the
- *   interior as two launch groups on two streams joined by events (rounds 2-4: measured faster, profiles/r05_slab_protocol_cost.txt).
- *   1 (experimental, round 5) = ONE launch over all strips whose dispatch order puts the edge strips first / last, with device-side
- *   hand-offs: the edge strips report on a device word that a one-wave gate kernel on the comm stream polls before the halo is packed, and
- *   poll an epoch word the comm stream bumps behind the unpack -- no second stream, no join events on the compute stream. Same results. */
-#define WX_OPT_SPLIT_LAUNCH 9
+/* 9: retired, was the one-launch split iteration; not reused */
 /* WX_OPT_DRY_PAIRS (round 5; default 1): the water-free dry stencil (pass_mask WX_PASS_DRY, no water anywhere, no brush, wall texture
  *   constant) runs TWO iterations per launch wherever two are left in a wx_step call and neither is a split iteration -- the second
  *   iteration's input never leaves the wavefront (csrc/wx_march2.h): 18 instead of 36 bytes per cell-step, 0.71 instead of 0.86 ms per
@@ -355,11 +350,13 @@ int wx_halo_unpack_both(wx_sim *s, const void *dev_left, const void *dev_right);
  * side HIP stream"). After wx_set_comm_stream(s, stream) the pack / unpack kernels run on `stream` -- the stream the host also
  * issues its send / recv on -- fenced against the handle's compute stream by events inside the library:
  *   wx_step_overlap(s, n, WX_OVERLAP_EDGES_FIRST): in the LAST iteration of the call the edge strips (every column
- *     wx_halo_pack reads) are launched first and an event is recorded behind them; wx_halo_pack waits for that event only,
- *     so packing and sending run while the interior strips of that iteration still compute;
- *   wx_step_overlap(s, n, WX_OVERLAP_EDGES_LAST): in the FIRST iteration the interior strips are launched first; the compute
- *     stream then waits for the event wx_halo_unpack recorded on the comm stream and launches the edge strips, the only ones
- *     that read ghost columns.
+ *     wx_halo_pack reads) are a launch group of their own, on a high-priority stream of the handle next to the interior strips'
+ *     group, and an event is recorded behind them; wx_halo_pack waits for that event only, so packing and sending run while the
+ *     interior strips of that iteration still compute;
+ *   wx_step_overlap(s, n, WX_OVERLAP_EDGES_LAST): in the FIRST iteration the interior strips start at once; the edge strips'
+ *     group, the only one that reads ghost columns, waits for the event wx_halo_unpack recorded on the comm stream.
+ * The compute stream goes on behind both groups. This is the one form of a split iteration (a one-launch form with device-side
+ * hand-offs was built, measured not faster and retired: DESIGN.md section 6).
  * Both flags may be combined. The split needs a row-marching kernel (default kernel set; all grid passes on, or the water-free
  * dry iteration; particles off) and a slab wide enough to have interior strips; otherwise the call degrades to the in-order exchange: wx_halo_pack waits
  * for everything enqueued on the compute stream, the next wx_step waits for the unpack. wx_step(s, n) == wx_step_overlap(s, n, 0). */

@@ -56,6 +56,7 @@ CHILD = textwrap.dedent('''
     must_fail("step negative", L.wx_step(hp, -1))
     must_fail("set_option unknown", L.wx_set_option(hp, 12345, 1))
     must_fail("set_option negative cap", L.wx_set_option(hp, 6, -1))
+    assert L.wx_set_option(hp, 9, 1) == -1  # (WX_E_INVALID: 9 is retired -- it was the one-launch split iteration -- like any unknown option)
     must_fail("upload NULL", L.wx_upload(hp, None, None, None, None))
     must_fail("set_params NULL", L.wx_set_params(hp, None, None, None, None, None))
     must_fail("create zero", L.wx_create(0, 0, 0, C.byref(C.c_void_p())))

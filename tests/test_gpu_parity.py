@@ -937,8 +937,6 @@ def test_slab_handles_equal_whole_domain(pkg, E, fused, nslab, halo):
 def _run_overlapped(E, slabs, comm, bufs, per, n_iter):
     """n_iter iterations on N slab handles of one GPU with the halo exchange on per-handle comm streams (device-to-device copies
     stand in for send / recv), edge / interior split launches, no host synchronisation between the steps."""
-    import torch
-    nslab = len(slabs)
     done, exchanged = 0, False
     while done < n_iter:
         k = min(per, n_iter - done)
@@ -948,47 +946,40 @@ def _run_overlapped(E, slabs, comm, bufs, per, n_iter):
         done += k
         if k < per:
             break
-        packed = []
-        for r, h in enumerate(slabs):  # pack on each handle's comm stream (the library waits for the edge-strip event only)
-            h.halo_pack(0, bufs[r][0].data_ptr())
-            h.halo_pack(1, bufs[r][1].data_ptr())
-            ev = torch.cuda.Event()
-            ev.record(comm[r])
-            packed.append(ev)
-        for r, h in enumerate(slabs):  # "recv": a handle's unpack may start once BOTH neighbours have packed
-            comm[r].wait_event(packed[(r - 1) % nslab])
-            comm[r].wait_event(packed[(r + 1) % nslab])
-            h.halo_unpack(0, bufs[(r - 1) % nslab][1].data_ptr())
-            h.halo_unpack(1, bufs[(r + 1) % nslab][0].data_ptr())
-        # a neighbour's NEXT pack overwrites the buffers this handle's unpack reads: fence the comm streams among themselves
-        unpacked = []
-        for r in range(nslab):
-            ev = torch.cuda.Event()
-            ev.record(comm[r])
-            unpacked.append(ev)
-        for r in range(nslab):
-            comm[r].wait_event(unpacked[(r - 1) % nslab])
-            comm[r].wait_event(unpacked[(r + 1) % nslab])
+        _exchange_overlapped(slabs, comm, bufs)
         exchanged = True
 
 
-@pytest.mark.parametrize("nslab,halo,X,bands,split", [(2, 12, 1024, None, 1), (4, 24, 4096, None, 1), (2, 6, 128, None, 1), (2, 12, 1024, "2", 1),
-                                                      (4, 24, 4096, "2", 1), (2, 12, 1024, None, 0), (4, 24, 4096, "2", 0)])
-def test_slab_overlapped_exchange_equals_whole_domain(pkg, E, monkeypatch, nslab, halo, X, bands, split):
-    """The exchange / compute overlap (wx_set_comm_stream + wx_step_overlap): N slab handles on one GPU, each with its own compute
-    stream and its own comm stream, nothing synchronised on the host between the steps -- the edge strips of the last iteration
-    run first, pack + copy + unpack proceed on the comm streams while the interior strips compute, the edge strips of the next
-    iteration wait for the unpack. Ten exchange periods, bit for bit the undecomposed handle. (A slab too narrow to have
-    interior strips, the third case, degrades to the in-order exchange through the same calls.) `split` = WX_OPT_SPLIT_LAUNCH: 1 (the
-    default since round 5) runs a split iteration as ONE launch whose dispatch order puts the edge strips first / last, with device-side
-    hand-offs (arrival word + gate kernel, epoch word); 0 = the two launch groups on two streams of rounds 2-4. The velocities
-    (sigma 0.2) put a few dozen cells per iteration on the exact path, also in edge strips: their own list, consumed on the comm stream."""
+def _exchange_overlapped(slabs, comm, bufs):
+    """One halo exchange of _run_overlapped, on the comm streams."""
     import torch
-    monkeypatch.setenv("WX_FUSED", "2")
-    if bands:  # the row-band launch shape of wide slabs (e.g. two ranks on 32768 columns), forced onto this small grid
-        monkeypatch.setenv("WX_WET_BANDS", bands)
-    Y = 64
-    per, n_iter = halo // 6, 10 * (halo // 6) + 1
+    nslab = len(slabs)
+    packed = []
+    for r, h in enumerate(slabs):  # pack on each handle's comm stream (the library waits for the edge-strip event only)
+        h.halo_pack(0, bufs[r][0].data_ptr())
+        h.halo_pack(1, bufs[r][1].data_ptr())
+        ev = torch.cuda.Event()
+        ev.record(comm[r])
+        packed.append(ev)
+    for r, h in enumerate(slabs):  # "recv": a handle's unpack may start once BOTH neighbours have packed
+        comm[r].wait_event(packed[(r - 1) % nslab])
+        comm[r].wait_event(packed[(r + 1) % nslab])
+        h.halo_unpack(0, bufs[(r - 1) % nslab][1].data_ptr())
+        h.halo_unpack(1, bufs[(r + 1) % nslab][0].data_ptr())
+    # a neighbour's NEXT pack overwrites the buffers this handle's unpack reads: fence the comm streams among themselves
+    unpacked = []
+    for r in range(nslab):
+        ev = torch.cuda.Event()
+        ev.record(comm[r])
+        unpacked.append(ev)
+    for r in range(nslab):
+        comm[r].wait_event(unpacked[(r - 1) % nslab])
+        comm[r].wait_event(unpacked[(r + 1) % nslab])
+
+
+def _wet_overlap_scene(pkg, E, nslab, halo, X, Y):
+    """The scene of the overlapped wet tests, whole and as slab handles with their own compute and comm streams."""
+    import torch
     base, water, wall = pkg.synth.terrain_grid(X, Y)
     rng = np.random.default_rng(2)
     air = wall[..., 1] != 0
@@ -1010,13 +1001,31 @@ def test_slab_overlapped_exchange_equals_whole_domain(pkg, E, monkeypatch, nslab
         comm.append(torch.cuda.Stream())
         h.set_stream(main[r].cuda_stream)
         h.set_comm_stream(comm[r].cuda_stream)
-        h.set_option(E.Handle.OPT_SPLIT_LAUNCH, split)
         slabs.append(h)
         bufs.append([torch.empty(h.halo_bytes(), dtype=torch.uint8, device="cuda") for _ in range(2)])
-    _run_overlapped(E, slabs, comm, bufs, per, n_iter)
     whole = E.Handle(X, Y, 0)
     whole.upload(base, water, wall)
     whole.set_params(p, u["initial_T"])
+    return slabs, comm, bufs, main, whole
+
+
+@pytest.mark.parametrize("nslab,halo,X,bands", [(2, 12, 1024, None), (4, 24, 4096, None), (2, 6, 128, None), (2, 12, 1024, "2"), (4, 24, 4096, "2")])
+def test_slab_overlapped_exchange_equals_whole_domain(pkg, E, monkeypatch, nslab, halo, X, bands):
+    """The exchange / compute overlap (wx_set_comm_stream + wx_step_overlap): N slab handles on one GPU, each with its own compute
+    stream and its own comm stream, nothing synchronised on the host between the steps -- the edge strips of the last iteration
+    run as a launch group of their own next to the interior strips, pack + copy + unpack proceed on the comm streams while the
+    interior computes, the edge strips of the next iteration wait for the unpack. Ten exchange periods, bit for bit the undecomposed
+    handle. (A slab too narrow to have interior strips, the third case, degrades to the in-order exchange through the same calls.)
+    The velocities (sigma 0.2) put a few dozen cells per iteration on the exact path, also in edge strips: the edge group has its own
+    list and its own fix pass, which the pack waits for."""
+    monkeypatch.setenv("WX_FUSED", "2")
+    if bands:  # the row-band launch shape of wide slabs (e.g. two ranks on 32768 columns), forced onto this small grid
+        monkeypatch.setenv("WX_WET_BANDS", bands)
+    Y = 64
+    per, n_iter = halo // 6, 10 * (halo // 6) + 1
+    slabs, comm, bufs, _main, whole = _wet_overlap_scene(pkg, E, nslab, halo, X, Y)
+    xo = X // nslab
+    _run_overlapped(E, slabs, comm, bufs, per, n_iter)
     whole.step(n_iter)
     for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR", "LIGHT_0", "LIGHT_1"):
         ref = whole.read_rect(f)
@@ -1024,6 +1033,35 @@ def test_slab_overlapped_exchange_equals_whole_domain(pkg, E, monkeypatch, nslab
             assert np.array_equal(h.read_rect(f, halo, 0, xo, Y), ref[:, r * xo:(r + 1) * xo]), (f, r)
     for h in slabs:
         h.close()
+
+
+def test_slab_read_between_edges_first_step_and_pack(pkg, E, monkeypatch):
+    """A host that steps a period with OVERLAP_EDGES_FIRST and then, BEFORE it packs the halo, reads the state back and asks for a
+    device pointer: both are ordered behind the edge group and its fix pass by the streams alone (the compute stream joins the edge
+    stream behind every split iteration), and the exchange that follows still packs final columns. The read shows the undecomposed
+    handle's period, and so do the owned columns after the exchange and one more period -- bit for bit."""
+    monkeypatch.setenv("WX_FUSED", "2")
+    nslab, halo, X, Y = 2, 12, 1024, 64
+    per, xo = halo // 6, X // nslab
+    slabs, comm, bufs, _main, whole = _wet_overlap_scene(pkg, E, nslab, halo, X, Y)
+    for h in slabs:
+        h.step(per, E.Handle.OVERLAP_EDGES_FIRST)
+    whole.step(per)
+    ref = whole.read_rect("BASE_CUR")
+    for r, h in enumerate(slabs):
+        assert np.array_equal(h.read_rect("BASE_CUR")[:, halo:halo + xo], ref[:, r * xo:(r + 1) * xo]), r
+        assert h.device_ptr("BASE_CUR")
+    _exchange_overlapped(slabs, comm, bufs)
+    for h in slabs:
+        h.step(per, E.Handle.OVERLAP_EDGES_LAST)
+    whole.step(per)
+    for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR", "LIGHT_0", "LIGHT_1"):
+        ref = whole.read_rect(f)
+        for r, h in enumerate(slabs):
+            assert np.array_equal(h.read_rect(f, halo, 0, xo, Y), ref[:, r * xo:(r + 1) * xo]), (f, r)
+    for h in slabs:
+        h.close()
+    whole.close()
 
 
 def _dry_uniforms(pkg, Y):
@@ -1055,15 +1093,14 @@ def _dry_slabs(pkg, E, X, Y, nslab, halo, base, water, wall, u, assert_free):
     return slabs, comm, bufs, free
 
 
-@pytest.mark.parametrize("nslab,halo,X,wet_rank,Y,split", [(2, 12, 1024, None, 96, 1), (4, 24, 4096, None, 96, 1), (2, 12, 1024, 1, 96, 1), (4, 12, 2048, 2, 96, 1),
-                                                           (4, 24, 4096, None, 576, 1), (2, 12, 1024, None, 96, 0), (4, 24, 4096, None, 576, 0)])
-def test_dry_slab_overlapped_exchange_equals_whole_domain(pkg, E, nslab, halo, X, wet_rank, Y, split):
+@pytest.mark.parametrize("nslab,halo,X,wet_rank,Y", [(2, 12, 1024, None, 96), (4, 24, 4096, None, 96), (2, 12, 1024, 1, 96), (4, 12, 2048, 2, 96), (4, 24, 4096, None, 576)])
+def test_dry_slab_overlapped_exchange_equals_whole_domain(pkg, E, nslab, halo, X, wet_rank, Y):
     """BASELINE's north-star stencil (pass_mask DRY) on slabs with the exchange overlapped: the water-free row-marching kernel takes
     strip ranges like the wet one (edge strips / interior). It may only run when NO slab carries water -- the hosts agree on that
     once per upload (wx_water_free -> all-reduce MIN -> wx_slab_assert_water_free), so no step ever reads a flag back. With water in
     ONE rank's slab (wet_rank) every handle falls back to the water-carrying kernel; both ways the owned columns equal the
-    undecomposed handle bit for bit over ten exchange periods. Y = 576 gives the row-band launch shape (72-row bands), whose split
-    iterations are ONE launch with the edge strips first / last in every XCD's dispatch order (`split` = WX_OPT_SPLIT_LAUNCH, see the wet test)."""
+    undecomposed handle bit for bit over ten exchange periods. Y = 576 gives the row-band launch shape (72-row bands): the edge group
+    and the interior group of a split iteration are then cut into the same bands and segments as the whole width."""
     per, n_iter = halo // 6, 10 * (halo // 6) + 1
     base, water, wall = pkg.synth.dry_grid(X, Y, flow_sigma=0.2 if Y < 200 else 0.12)  # (the taller grid's eddies are faster: |v| < 1 is the precondition of the fixed period)
     rng = np.random.Generator(np.random.Philox(77))
@@ -1077,7 +1114,6 @@ def test_dry_slab_overlapped_exchange_equals_whole_domain(pkg, E, nslab, halo, X
     slabs, comm, bufs, free = _dry_slabs(pkg, E, X, Y, nslab, halo, base, water, wall, u, None)
     assert free == [r != wet_rank for r in range(nslab)]
     for h in slabs:
-        h.set_option(E.Handle.OPT_SPLIT_LAUNCH, split)
         h.profile(True)
     _run_overlapped(E, slabs, comm, bufs, per, n_iter)
     for h in slabs:

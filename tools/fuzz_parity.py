@@ -683,6 +683,8 @@ def draw_group(rng, c):
         halo = int(rng.choice([h for h in (6, 12, 18, 24, 42, 48, 64) if h >= lo]))
         xo = max(halo, -(-c["X"] // n))
     c["X"] = n * xo
+    # ("split" chose between two forms of the split iteration while there were two. Still drawn and recorded, so that a seed's cases and
+    # their recipes stay what they were; nothing applies it any more)
     c.update(nslab=n, halo=halo, overlap=int(rng.random() < 0.6), split=int(rng.random() < 0.25), pool_exact=1, kernel_set=int(rng.random() < 0.9))
     c["steps"] = [int(v) for v in rng.integers(1, 2 * max(1, halo // 6) + 3, size=int(rng.integers(1, 4)))]
     return c
@@ -690,7 +692,8 @@ def draw_group(rng, c):
 
 def run_group_case(pkg, E, c):
     """N slabs on this one GPU (wx_group_*: the library's own halo exchange, device-to-device copies) against the undecomposed handle, bit
-    for bit -- SURVEY 8e's determinism check on random scenes, slab counts, halo widths, call boundaries, overlap / split-launch modes."""
+    for bit -- SURVEY 8e's determinism check on random scenes, slab counts, halo widths, call boundaries, overlap modes. (The "split" key of a
+    recipe is from the time a split iteration had a second form: ignored.)"""
     X, Y = c["X"], c["Y"]
     base, water, wall, u, drops = build_case(pkg, c)
     nd = 0 if drops is None else len(drops)
@@ -713,7 +716,6 @@ def run_group_case(pkg, E, c):
             g.set_option(k, v)
             whole.set_option(k, v)
         g.set_option(E.Handle.OPT_EXCHANGE_OVERLAP, c["overlap"])
-        g.set_option(E.Handle.OPT_SPLIT_LAUNCH, c["split"])
         if nd:
             g.set_option(E.Handle.OPT_POOL_EXACT, c["pool_exact"])
         fields = ["BASE_CUR", "WATER_CUR", "WALL_CUR"] + ([] if c["dry"] else ["LIGHT_0", "LIGHT_1", "BASE_DISP", "WATER_0"]) + (["PRECIP_DEP"] if nd else [])
@@ -1031,7 +1033,7 @@ def main():
             bad = []
         tag = "MISMATCH" if bad else ("reported: " + info["error"][:60] if info.get("error") else "ok")
         print(f"case {k:4d} {c['X']:5d}x{c['Y']:<5d} {'dry' if c['dry'] else 'wet'} sigma {c['sigma']:.2f} steps {c['steps']} drops {c['drops']:4d} brush "
-              f"{c['brush']['type'] if c['brush'] else '-':>2} pairs {c['pairs']} bands {c['bands']} set {c['kernel_set']}{c['dry_kernel']}{' slabs %d halo %d overlap %d split %d' % (c['nslab'], c['halo'], c['overlap'], c['split']) if a.mode == 'group' else ''} fastest {info.get('fastest')}{' terrain columns differing %s' % info.get('terrain_columns_differing') if a.mode == 'setup' else ''}  {time.time() - t1:.1f}s  {tag}", flush=True)
+              f"{c['brush']['type'] if c['brush'] else '-':>2} pairs {c['pairs']} bands {c['bands']} set {c['kernel_set']}{c['dry_kernel']}{' slabs %d halo %d overlap %d' % (c['nslab'], c['halo'], c['overlap']) if a.mode == 'group' else ''} fastest {info.get('fastest')}{' terrain columns differing %s' % info.get('terrain_columns_differing') if a.mode == 'setup' else ''}  {time.time() - t1:.1f}s  {tag}", flush=True)
         if bad:
             failures.append({"case": k, "recipe": c, "mismatches": bad})
             print(json.dumps(failures[-1]), flush=True)

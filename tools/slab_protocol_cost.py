@@ -48,8 +48,8 @@ import ctypes  # noqa: E402
 
 class SelfExchange:
     """ONE handle (one placement of the planes: handles of one process differ by +-8 % from the placement alone, section 4 of LABNOTES) run in
-    four modes: no exchange at all (`plain`: what a slab's kernels cost), the overlapped protocol as one ordered launch per split iteration
-    (round 5) or as two launch groups on two streams (rounds 2-4), and the protocol in order on the compute stream."""
+    four modes: no exchange at all (`plain`: what a slab's kernels cost), the overlapped protocol (`two`: the split iterations' two launch
+    groups on two streams; `two_a`: only the iteration before an exchange split), and the protocol in order on the compute stream."""
 
     def __init__(self):
         self.h = E.Handle(XO, Y, 0, X_global=XO, x0=0, halo=HALO)
@@ -65,19 +65,17 @@ class SelfExchange:
         self.ipe = max(1, self.h.slab_period)
         self.mode = None
 
-    def set_mode(self, mode):  # "plain" | "one" | "two" | "inorder"
+    def set_mode(self, mode):  # "plain" | "two" | "two_a" | "inorder"
         self.h.sync()
         torch.cuda.synchronize()
-        self.h.set_comm_stream(self.comm.cuda_stream if mode in ("one", "two", "two_a") else 0)
-        if mode in ("one", "two", "two_a"):
-            self.h.set_option(E.Handle.OPT_SPLIT_LAUNCH, 1 if mode == "one" else 0)
+        self.h.set_comm_stream(self.comm.cuda_stream if mode in ("two", "two_a") else 0)
         self.mode, self.exchanged, self.since = mode, False, 0
 
     def step(self, n):
         if self.mode == "plain":
             self.h.step(n)
             return
-        overlap = self.mode in ("one", "two", "two_a")
+        overlap = self.mode in ("two", "two_a")
         b_split = 0 if self.mode == "two_a" else 2  # (two_a: only the iteration BEFORE an exchange is split; the one after it waits for the unpack)
         done = 0
         while done < n:
@@ -113,7 +111,7 @@ def timed(mode, iters=210, frame=7):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
-MODES = {"plain": "plain (no exchange)", "one": "protocol, overlapped: ONE ordered launch (r5)", "two": "protocol, overlapped: two launch groups (r4)",
+MODES = {"plain": "plain (no exchange)", "two": "protocol, overlapped: two launch groups",
          "two_a": "  the same, only the iteration BEFORE split",
          "inorder": "protocol, in order"}
 for m in MODES:
