@@ -1190,7 +1190,20 @@ static inline const float *texfetch4(const float *tex, int X, int Y, float u, fl
 typedef struct {
   float *acc; /* 5 floats per anchor: mass, heat, vapor | rain, snow */
   float count, light[4];
+  /* wxo_splat_audit (NULL: off): per anchor and channel the deposits added in double, their magnitudes, and how many were non-zero */
+  double *ex, *mag, lightd[4];
+  int32_t *cnt;
 } anchors_t;
+
+static double *audit_exact, *audit_bound, *audit_least;
+static int32_t *audit_count;
+void wxo_splat_audit(double *exact, double *bound, int32_t *count, double *least)
+{
+  audit_exact = exact;
+  audit_bound = bound;
+  audit_count = count;
+  audit_least = least;
+}
 
 static void splat(const wxo_params *p, float gposx, float gposy, float size, const float *feedback,
                   const float *deposition, float *fb, float *dep, anchors_t *an)
@@ -1221,12 +1234,25 @@ static void splat(const wxo_params *p, float gposx, float gposy, float size, con
       if (i0 == 0)
         an->count += feedback[0];
       else
-        for (int c = 0; c < 4; c++) an->light[c] += feedback[c];
+        for (int c = 0; c < 4; c++) {
+          an->light[c] += feedback[c];
+          if (an->ex) an->lightd[c] += (double)feedback[c];
+        }
       return;
     }
     const int q = i0 + 6, r = j0 + 6;
     if (q < 0 || q > X || r < 0 || r > Y) return;
     float *a = an->acc + 5 * ((size_t)r * (X + 1) + q);
+    if (an->ex) {
+      const size_t k = 5 * ((size_t)r * (X + 1) + q);
+      const float d[5] = {feedback[0], feedback[1], feedback[2], deposition[0], deposition[1]};
+      for (int c = 0; c < 5; c++) {
+        an->ex[k + c] += (double)d[c];
+        an->mag[k + c] += fabs((double)d[c]);
+        an->cnt[k + c] += d[c] != 0.0f;
+        if (audit_least && d[c] != 0.0f && fabs((double)d[c]) < audit_least[c]) audit_least[c] = fabs((double)d[c]);
+      }
+    }
     a[0] += feedback[0];
     a[1] += feedback[1];
     a[2] += feedback[2];
@@ -1302,6 +1328,31 @@ static void box_sum_anchors(const wxo_params *p, const anchors_t *an, float *fb,
   for (int c = 0; c < 4; c++) C4(fb, 1, 0)[c] += an->light[c];
 }
 
+/* wxo_splat_audit: the box sum of box_sum_anchors repeated in double, and the bound of the fp32 one (see wx_oracle.h) */
+static void box_sum_audit(const wxo_params *p, const anchors_t *an, double *exact, double *bound)
+{
+  const int X = p->X, Y = p->Y, AP = X + 1;
+  const double u = 1.0 / 16777216.0;
+#pragma omp parallel for schedule(static)
+  for (int j = 0; j < Y; j++)
+    for (int i = 0; i < X; i++)
+      for (int c = 0; c < 5; c++) {
+        double e = 0.0, b = 0.0;
+        for (int r = j - 5; r <= j + 6; r++)
+          for (int q = i - 5; q <= i + 6; q++) {
+            if (r < 0 || r > Y || q < 0 || q > X) continue;
+            const size_t k = 5 * ((size_t)r * AP + q) + c;
+            const double n = (double)an->cnt[k] + 7.0;
+            e += an->ex[k];
+            b += n * u / (1.0 - n * u) * an->mag[k];
+          }
+        exact[5 * ((size_t)j * X + i) + c] = e;
+        bound[5 * ((size_t)j * X + i) + c] = b;
+      }
+  exact[0] += (double)an->count; /* (an integer below 2^24: the float count is exact) */
+  for (int c = 0; c < 3; c++) exact[5 + c] += an->lightd[c];
+}
+
 void wxo_precipitation(const wxo_params *p, float iterNum, int n_drops, const float *drops_in,
                        const float *base_in, const float *water_in, const float *lightning_in,
                        float *drops_out, float *fb, float *dep)
@@ -1310,10 +1361,17 @@ void wxo_precipitation(const wxo_params *p, float iterNum, int n_drops, const fl
   const int X = p->X, Y = p->Y;
   const float resX = (float)X, resY = (float)Y;
   const float initalMass = 0.15f;
-  anchors_t an_store = {NULL, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}}, *an = NULL;
+  anchors_t an_store = {NULL, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}, NULL, NULL, {0.0, 0.0, 0.0, 0.0}, NULL}, *an = NULL;
   if (p->splat_order == 1) {
     an_store.acc = (float *)calloc((size_t)(X + 1) * (Y + 1) * 5, 4);
     an = &an_store;
+    if (audit_exact && audit_bound && audit_count) {
+      an_store.ex = (double *)calloc((size_t)(X + 1) * (Y + 1) * 5, 8);
+      an_store.mag = (double *)calloc((size_t)(X + 1) * (Y + 1) * 5, 8);
+      an_store.cnt = audit_count;
+      memset(audit_count, 0, (size_t)(X + 1) * (Y + 1) * 5 * sizeof(int32_t));
+      for (int c = 0; audit_least && c < 5; c++) audit_least[c] = HUGE_VAL;
+    }
   }
 
   for (int i = 0; i < n_drops; i++) {
@@ -1479,7 +1537,10 @@ void wxo_precipitation(const wxo_params *p, float iterNum, int n_drops, const fl
   }
   if (an) {
     box_sum_anchors(p, an, fb, dep);
+    if (an->ex) box_sum_audit(p, an, audit_exact, audit_bound);
     free(an->acc);
+    free(an->ex);
+    free(an->mag);
   }
 }
 

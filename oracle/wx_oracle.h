@@ -88,6 +88,17 @@ void wxo_precipitation(const wxo_params *p, float iterNum, int n_drops, const fl
                        const float *base_in, const float *water_in, const float *lightning_in,
                        float *drops_out, float *fb, float *dep);
 void wxo_lightning_location(const wxo_params *p, float iterNum, const float *fb, float *lightning);
+/* Audit of the splat_order 1 summation (opt-in; changes no output of wxo_precipitation): until it is called again with NULLs, every
+ * order-1 particle pass of this process also fills the caller's buffers --
+ *   exact [Y][X][5] (mass, heat, vapor | rain, snow): the box sum of the deposits as floats, added in double (anchor sums and the
+ *                   144-anchor box alike); texel (0,0) channel 0 includes the inactive count, texel (1,0) channels 0..2 the requests;
+ *   bound [Y][X][5]: sum over the box's anchors of gamma(n_a + 7) * S_a, gamma(k) = k u / (1 - k u), u = 2^-24, S_a the sum of the
+ *                   magnitudes of the anchor's deposits, n_a their number: what any fp32 summation order of the deposits followed by
+ *                   the two tree12 passes may differ from ``exact`` by (the mailbox texels' one more addition is left to the caller);
+ *   count [Y+1][X+1][5]: n_a, the NON-ZERO deposits per anchor and channel (adding a zero is exact and rounds nothing);
+ *   least [5] (may be NULL): the smallest magnitude of a non-zero deposit per channel, HUGE_VAL where there was none.
+ * The pass that fills them must have the grid size the buffers were made for. */
+void wxo_splat_audit(double *exact, double *bound, int32_t *count, double *least);
 
 /* hash known-answer entry points (common.glsl:103-137) */
 uint32_t wxo_hash(uint32_t x);

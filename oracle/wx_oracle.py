@@ -88,6 +88,7 @@ def lib() -> C.CDLL:
         L.wxo_lighting_mrt.argtypes = [PP, fp, fp, i8p, fp, fp, C.c_void_p]
         L.wxo_precipitation.argtypes = [PP, C.c_float, C.c_int, fp, fp, fp, fp, fp, fp, fp]
         L.wxo_lightning_location.argtypes = [PP, C.c_float, fp, fp]
+        L.wxo_splat_audit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.wxo_hash.argtypes = [C.c_uint32]
         L.wxo_hash.restype = C.c_uint32
         L.wxo_random2d.argtypes = [C.c_float, C.c_float]
@@ -134,6 +135,26 @@ def make_params(u: Dict[str, Any], X: int, Y: int, X_global: Optional[int] = Non
 
 def _vp(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class SplatAudit:
+    """wxo_splat_audit as a context manager: inside it every splat_order 1 particle pass on an X x Y grid also fills ``exact`` and
+    ``bound`` (float64, [Y, X, 5]: mass, heat, vapor | rain, snow) and ``count`` (int32, [Y + 1, X + 1, 5]: non-zero deposits per anchor
+    and channel) and ``least`` (float64, [5]: the smallest non-zero |deposit| per channel, inf without one) -- see wx_oracle.h. The arrays hold the LAST such pass; no output of the oracle changes."""
+
+    def __init__(self, X: int, Y: int):
+        self.exact = np.zeros((Y, X, 5), np.float64)
+        self.bound = np.zeros((Y, X, 5), np.float64)
+        self.count = np.zeros((Y + 1, X + 1, 5), np.int32)
+        self.least = np.full(5, np.inf)
+
+    def __enter__(self):
+        lib().wxo_splat_audit(_vp(self.exact), _vp(self.bound), _vp(self.count), _vp(self.least))
+        return self
+
+    def __exit__(self, *exc):
+        lib().wxo_splat_audit(None, None, None, None)
+        return False
 
 
 class OracleSim:
