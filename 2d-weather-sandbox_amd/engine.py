@@ -46,6 +46,7 @@ EXPORTS = [
     "wx_ensemble_statistics", "wx_ens_stat_cells",
     "wx_copy_state", "wx_ensemble_broadcast", "wx_ensemble_perturb", "wx_ens_perturb_cells",
     "wx_ensemble_quantiles", "wx_ens_quant_cells", "wx_ens_quant_staged_members",
+    "wx_ensemble_assimilate", "wx_ens_assim_cells",
 ]
 
 
@@ -277,6 +278,79 @@ def ens_perturb_cells(fields, walls, X: int, Y: int, field, amplitude, *, mode="
     return out
 
 
+ENS_OBS_MAX = 256
+
+
+class WxEnsObs(C.Structure):
+    """``wx_ens_obs`` of include/wxsim.h: one scalar observation of one channel of one cell."""
+    _fields_ = [("field", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("channel", C.c_int32), ("value", C.c_float), ("error_var", C.c_float)]
+
+
+class WxEnsObsResult(C.Structure):
+    """``wx_ens_obs_result`` of include/wxsim.h: what the call says about one observation."""
+    _fields_ = [("applied", C.c_int32), ("pad", C.c_int32), ("prior_mean", C.c_double), ("prior_var", C.c_double), ("innovation", C.c_double),
+                ("alpha", C.c_double)]
+
+
+class WxEnsAssim(C.Structure):
+    """``wx_ens_assim`` of include/wxsim.h, member for member."""
+    _fields_ = [
+        ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("wrap_x", C.c_int32), ("loc_x", C.c_float), ("loc_y", C.c_float),
+        ("gain_base", C.c_float * 4), ("gain_water", C.c_float * 4),
+        ("lo_base", C.c_float * 4), ("hi_base", C.c_float * 4), ("lo_water", C.c_float * 4), ("hi_water", C.c_float * 4),
+    ]
+
+
+def _assim_struct(rect, loc, wrap_x, gain_base, gain_water, lo_base, hi_base, lo_water, hi_water) -> WxEnsAssim:
+    a = WxEnsAssim()
+    a.x, a.y, a.w, a.h = [int(v) for v in rect]
+    a.wrap_x = 1 if wrap_x else 0
+    a.loc_x, a.loc_y = float(loc[0]), float(loc[1])
+    a.gain_base[:], a.gain_water[:] = _four(gain_base, 0.0), _four(gain_water, 0.0)
+    nan = float("nan")
+    a.lo_base[:], a.hi_base[:], a.lo_water[:], a.hi_water[:] = _four(lo_base, nan), _four(hi_base, nan), _four(lo_water, nan), _four(hi_water, nan)
+    return a
+
+
+def _obs_array(observations):
+    """``(field, x, y, channel, value, error_var)`` tuples (field: a name or a WX_FIELD_* number) as an array of wx_ens_obs."""
+    obs = (WxEnsObs * max(len(observations), 1))()
+    for j, (field, x, y, channel, value, error_var) in enumerate(observations):
+        obs[j].field, obs[j].x, obs[j].y, obs[j].channel = int(FIELD_IDS.get(field, field)), int(x), int(y), int(channel)
+        obs[j].value, obs[j].error_var = float(value), float(error_var)
+    return obs
+
+
+def _obs_results(res, n: int) -> list:
+    return [{"applied": bool(r.applied), "prior_mean": r.prior_mean, "prior_var": r.prior_var, "innovation": r.innovation, "alpha": r.alpha}
+            for r in res[:n]]
+
+
+def ens_assim_cells(bases, waters, walls, X: int, Y: int, observations, *, loc=(0.0, 0.0), rect=None, members=None, wrap_x=False,
+                    gain_base=(0, 0, 0, 1), gain_water=0.0, lo_base=None, hi_base=None, lo_water=None, hi_water=None):
+    """wx_ens_assim_cells: the serial ensemble square-root filter of include/wxsim.h on the CPU, literally as defined. ``bases[i]`` /
+    ``waters[i]`` / ``walls[i]``: member i's WHOLE grid, float32 (Y, X, 4) and int8 (Y, X, 4); an unselected member's entries may be
+    None. ``observations``: ``(field, x, y, channel, value, error_var)`` tuples, taken in order. Returns (new bases, new waters, one
+    result dict per observation); the arguments are not changed."""
+    rect = (0, 0, int(X), int(Y)) if rect is None else tuple(int(v) for v in rect)
+    n = len(bases)
+    mask = _member_mask(n, members)
+    shape = (int(Y), int(X), 4)
+    nb = [None if a is None else np.array(a, np.float32, order="C") for a in bases]
+    nw = [None if a is None else np.array(a, np.float32, order="C") for a in waters]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    if n < 1 or len(nw) != n or len(wl) != n or any(a is not None and a.shape != shape for a in nb + nw + wl):
+        raise ValueError(f"one {shape} base, water and wall array per member")
+    ptrs = lambda arrs: (C.c_void_p * max(n, 1))(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
+    a = _assim_struct(rect, loc, wrap_x, gain_base, gain_water, lo_base, hi_base, lo_water, hi_water)
+    obs, res = _obs_array(observations), (WxEnsObsResult * max(len(observations), 1))()
+    rc = lib().wx_ens_assim_cells(C.byref(a), len(observations), obs, res, int(X), int(Y), n, ptrs(nb), ptrs(nw), ptrs(wl),
+                                  None if mask is None else mask.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_ens_assim_cells: bad descriptor or observation, rectangle or observation outside the grid, or fewer than two members selected")
+    return nb, nw, _obs_results(res, len(observations))
+
+
 ENS_QUANT_MAX = 8
 QUANT_INTERP = {"linear": 0, "lower": 1, "higher": 2}
 
@@ -501,6 +575,8 @@ def lib() -> C.CDLL:
     L.wx_ens_quant_cells.argtypes = [i32, C.c_size_t, vp, vp, vp, C.POINTER(WxEnsQuant)]
     L.wx_ens_quant_staged_members.argtypes = []
     L.wx_ens_quant_staged_members.restype = i32
+    L.wx_ensemble_assimilate.argtypes = [vp, C.POINTER(WxEnsAssim), i32, vp, vp, vp]
+    L.wx_ens_assim_cells.argtypes = [C.POINTER(WxEnsAssim), i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1123,6 +1199,21 @@ class Ensemble:
         p = _perturb_struct(field, amplitude, mode, scale, seed, wrap_x, rect, lo, hi)
         mask = _member_mask(self.n, members)
         self._chk(lib().wx_ensemble_perturb(self._e, C.byref(p), None if mask is None else mask.ctypes.data))
+
+    def assimilate(self, observations, *, loc=(0.0, 0.0), rect=None, members=None, wrap_x=False, gain_base=(0, 0, 0, 1), gain_water=0.0,
+                   lo_base=None, hi_base=None, lo_water=None, hi_water=None) -> list:
+        """wx_ensemble_assimilate: the selected members (at least two) pulled towards point observations -- ``(field, x, y, channel,
+        value, error_var)`` tuples, taken in order -- by a serial ensemble square-root filter, on the device, in three launches at most.
+        ``loc`` = (half-width in x, in y) of the Gaspari-Cohn localization in cells (0: none along that axis), ``rect`` = (x, y, w, h) the
+        cells that may change (None: the whole grid), ``gain_base`` / ``gain_water``: one value or one per channel of the two state
+        fields (0: untouched, 1: the full update; default: temperature only), ``lo_*`` / ``hi_*``: clamps (None: none). Returns one dict
+        per observation (applied, prior_mean, prior_var, innovation, alpha). Blocks like ``perturb``."""
+        rect = (0, 0, self.X, self.Y) if rect is None else rect
+        a = _assim_struct(rect, loc, wrap_x, gain_base, gain_water, lo_base, hi_base, lo_water, hi_water)
+        obs, res = _obs_array(observations), (WxEnsObsResult * max(len(observations), 1))()
+        mask = _member_mask(self.n, members)
+        self._chk(lib().wx_ensemble_assimilate(self._e, C.byref(a), len(observations), obs, res, None if mask is None else mask.ctypes.data))
+        return _obs_results(res, len(observations))
 
     def close(self):
         if getattr(self, "_e", None):

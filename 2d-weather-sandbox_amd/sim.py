@@ -336,6 +336,15 @@ class WeatherEnsemble:
         members, lo, hi)."""
         self._e.perturb(field, amplitude, **kw)
 
+    def assimilate(self, observations, *, loc=(0.0, 0.0), rect=None, members=None, wrap_x=None, **kw) -> list:
+        """``engine.Ensemble.assimilate``: the selected members pulled towards point observations -- ``(field, x, y, channel, value,
+        error_var)`` tuples, e.g. a nature run's values at its weather stations -- by a serial ensemble square-root filter on the
+        device (loc, rect, members, gain_base, gain_water, lo_* / hi_*). ``wrap_x`` defaults to the members' ``wrapHorizontally``.
+        Returns one dict per observation (applied, prior_mean, prior_var, innovation, alpha)."""
+        if wrap_x is None:
+            wrap_x = bool(self.members[0].gui.get("wrapHorizontally", True))
+        return self._e.assimilate(observations, loc=loc, rect=rect, members=members, wrap_x=wrap_x, **kw)
+
     def __len__(self):
         return len(self.members)
 

@@ -811,6 +811,76 @@ int wx_ens_quant_cells(int n_members, size_t n_cells, const float *const *field,
                        const uint8_t *member_mask, wx_ens_quant *out);
 int wx_ens_quant_staged_members(void);  /* largest number of selected members the LDS path takes */
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_ASSIMILATE) Point observations assimilated into the members on the device: the ensemble Kalman analysis
+ * that closes the loop perturb -> step -> statistics / quantiles. A host that holds observations (stations on a nature run, a sounding)
+ * pulls the selected members towards them without one host array and without wx_upload, which would reset light, curl, the feedback
+ * textures and the lightning state. A serial ensemble square-root filter (EnSRF, Whitaker and Hamill 2002) with separable Gaspari-Cohn
+ * localization in x and in height, defined bit for bit, in three launches at most whatever the number of observations.
+ *
+ * THE DEFINITION (the kernels, wx_ens_assim_cells and the tests all evaluate it). All arithmetic is double, every operation rounded
+ * separately (no fused multiply-add: contraction is off inside every function that rounds, and every product that feeds a sum or a
+ * difference is a value of its own in every build, so libwxsim.so, libwxsim_fast.so, the device and the host give the same bits). "In
+ * member order": the n selected members k = 0 .. n-1 by ascending member index.
+ *   Order. Observations are taken in order, j = 0 first; observation j sees the members' values as observations 0 .. j-1 left them.
+ *   Prior of observation j. t_k = channel `channel` of cell (x, y) of `field` in member k. The observation is SKIPPED (applied = 0, its
+ *   result doubles NaN, nothing changes) unless in every selected member that cell is an air cell (channel 1 of its WX_FIELD_WALL_CUR
+ *   texel != 0: wx_diag's test) and t_k is finite. Otherwise S = sum (double)t_k in member order, hm = S / n, e_k = (double)t_k - hm,
+ *   Q = sum e_k*e_k in member order, V = Q / (n - 1), D = V + (double)R, innovation = (double)value - hm,
+ *   alpha = 1 / (1 + sqrt((double)R / D)) with the correctly rounded double square root.
+ *   Localization weight of cell (x, y). dx = |x - ox|, with wrap_x dx = min(dx, X - dx); dy = |y - oy|. Per axis the factor is 1 if that
+ *   axis's loc is 0, else G((double)d / (double)loc), G by Horner with the double constants 5.0/3.0, 1.0/12.0, 2.0/3.0 as those C
+ *   expressions:   0 <= z <= 1: p = -0.25*z + 0.5; p = p*z + 0.625; p = p*z - 5.0/3.0; p = p*z; p = p*z + 1.0
+ *                  1 < z < 2:   p = (1.0/12.0)*z - 0.5; p = p*z + 0.625; p = p*z + 5.0/3.0; p = p*z - 5.0; p = p*z + 4.0; p = p - (2.0/3.0)/z
+ *                  z >= 2: 0.   A negative p is 0.     rho = Gx * Gy, one rounded product. (Separable and anisotropic on purpose: the
+ *   grid is a vertical slice, horizontal and vertical length scales differ, and no cell needs a square root.)
+ *   Per cell of the rectangle, state field F in {BASE_CUR, WATER_CUR} (not necessarily the observed one) and channel c with
+ *   g = gain_F[c] != 0: if rho == 0 the channel is untouched. It is updated only if in every selected member the cell is an air cell and
+ *   the value x_k is finite, else untouched in all members. Sx = sum (double)x_k in member order, xm = Sx / n, d_k = (double)x_k - xm,
+ *   Cq = sum d_k*e_k in member order, C = Cq / (n - 1), w = (double)g * rho, K = (w * C) / D. If K == 0 or K is not finite the channel is
+ *   untouched (so a -0.0 never becomes +0.0 by a zero increment). Otherwise a = K * innovation, b = alpha * K and for every member
+ *   o_k = (float)((double)x_k + (a - b*e_k)), then wx_ens_perturb's clamp (lo first, then hi, NaN = none); if o_k is not finite that
+ *   member's channel keeps its bits.
+ * Cells never interact within one observation, and an observation may lie outside the rectangle: its prior is read, its cell is never
+ * changed. A cell's result depends on the rectangle only through the priors: two rectangles that hold the same observed cells give
+ * their common cells the same bits.
+ *
+ * wx_ensemble_assimilate. Answered before the device is touched -- WX_E_INVALID: e, a or obs NULL; n_obs outside 1 .. WX_ENS_OBS_MAX; an
+ * observation's field other than WX_FIELD_BASE_CUR / WX_FIELD_WATER_CUR or channel outside 0 .. 3; a value, error_var, loc or gain that
+ * is not finite; error_var <= 0; loc < 0; fewer than two selected members. WX_E_RANGE: the rectangle or an observation outside the grid.
+ * WX_E_STATE: a selected member was never uploaded (the message names it). Ordering, blocking, error reports and bookkeeping as for
+ * wx_ensemble_perturb, for every selected member and every state field with a non-zero gain: a lazy WX_FIELD_BASE_DISP is assembled
+ * whole first, a pending WX_FIELD_WATER_0 is made first, velocities written are looked at by the next |vx| scan, an updated water field
+ * is no longer known to be water-free. With all gains 0 the call is legal: it fills `result` and changes nothing. `result` (n_obs entries
+ * or NULL) is computed on the device and copied back once. Launches: "ensemble_assimilate_obs" once -- the chain of priors in observation
+ * space, on working copies of the observed channels --, then "ensemble_assimilate" once per state field with a non-zero gain (wx_profile
+ * on member 0 times both); DESIGN.md section 4.
+ * wx_ens_assim_cells (host only, pure): the serial definition, literally, over WHOLE X x Y grids the caller holds (an observation may lie
+ * outside the rectangle) -- member i's cells at base[i] / water[i] (4 floats per cell, rows bottom-up, changed in place) and wall[i]
+ * (4 bytes per cell). WX_E_INVALID / WX_E_RANGE as above, and for n_members < 1, a NULL table, a NULL entry of a selected member. */
+#define WX_HAVE_ENSEMBLE_ASSIMILATE 1
+#define WX_ENS_OBS_MAX 256
+typedef struct wx_ens_obs {        /* one scalar observation of one channel of one cell */
+  int32_t field;                   /* WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR */
+  int32_t x, y, channel;           /* inside the grid (WX_E_RANGE), channel 0..3 */
+  float   value;                   /* finite */
+  float   error_var;               /* R: finite, > 0 */
+} wx_ens_obs;
+typedef struct wx_ens_obs_result { /* one per observation, filled by the call (computed on the device by wx_ensemble_assimilate) */
+  int32_t applied, pad;            /* 1: used; 0: skipped (see above), the doubles are then NaN */
+  double  prior_mean, prior_var, innovation, alpha;
+} wx_ens_obs_result;
+typedef struct wx_ens_assim {
+  int32_t x, y, w, h;              /* the cells that may be changed; no wrap (WX_E_RANGE) */
+  int32_t wrap_x;                  /* distances in x are taken around the grid's width */
+  float   loc_x, loc_y;            /* localization half-widths in cells, finite, >= 0; 0: no localization along that axis */
+  float   gain_base[4], gain_water[4];  /* per channel of the two state fields; 0: the channel's bits are not touched; 1: the full update */
+  float   lo_base[4], hi_base[4], lo_water[4], hi_water[4];  /* clamp of the result, NaN: none (as wx_ens_perturb) */
+} wx_ens_assim;
+int wx_ensemble_assimilate(wx_ensemble *e, const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs,
+                           wx_ens_obs_result *result /* n_obs entries or NULL */, const uint8_t *member_mask);
+int wx_ens_assim_cells(const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs, wx_ens_obs_result *result, int X, int Y, int n_members,
+                       float *const *base, float *const *water, const int8_t *const *wall, const uint8_t *member_mask);
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

@@ -32,6 +32,13 @@ on the temperature of the air cells, timed). Route B does NOT make the same ense
 feedback textures, lightning state and `even`, so its members are not the stepped simulation (the record says so: "route_b_carries_the_
 state": false). The shape's "spawn" key also holds the perturbation kernel's own time (wx_profile on member 0) against its 36 B per
 member-cell at --peak-gbs.
+--assimilate FIELD (BASE_CUR: temperature observations; WATER_CUR: channel 0; --mode ensemble): what ONE wx_ensemble_assimilate call
+with --observations N point observations over the whole grid costs (localization half-widths 20 x 10 cells, all four channels of FIELD
+updated; host to host: the call blocks), against N calls of one observation each, and against the only host route that exists -- B
+read_rect triples (base, water, wall), wx_ens_assim_cells on the host, B wx_upload calls. THE UPLOADS LOSE THE STEPPED STATE (light, curl,
+the feedback textures, the lightning state): the record says so. The shape's "assimilate" key also holds the two kernels' own times
+(wx_profile on member 0) next to the bytes the update kernel moves at most: 3 x 20 B read + 16 B written per member-cell and observation
+whose weight there is not 0.
 --share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
 import argparse
 import json
@@ -55,12 +62,14 @@ def parse():
     ap.add_argument("--droplets", type=int, default=0, help="droplets per member (0: none, precipitation off)")
     ap.add_argument("--statistics", default="", metavar="FIELD", help="time one statistics call over the whole grid against B read_rect calls + numpy (BASE_CUR or WATER_CUR)")
     ap.add_argument("--quantiles", default="", metavar="FIELD", help="time one quantile call over the whole grid against B read_rect calls + np.sort (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--assimilate", default="", metavar="FIELD", help="time one assimilation call of --observations point observations against N calls of one and against read_rect + host function + uploads (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--observations", type=int, default=40, help="observations per call with --assimilate (1 .. 256)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x64,2500x300x8,16000x500x2"
+        a.shapes = "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
     return a
 
 
@@ -320,8 +329,90 @@ def time_spawn(a, pkg, ens, X, Y, B):
             "kernel_gb_per_s": round(gbs, 1) if gbs else None, "kernel_fraction_of_peak": round(gbs / a.peak_gbs, 4) if gbs else None}
 
 
+def time_assimilate(a, pkg, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    E = pkg.engine
+    field, c = a.assimilate, 3 if a.assimilate == "BASE_CUR" else 0
+    ens.step(a.frame)
+    ens.sync()
+    loc = (20.0, 10.0)
+    gains = dict(gain_base=1.0 if field == "BASE_CUR" else 0.0, gain_water=1.0 if field == "WATER_CUR" else 0.0, lo_water=0.0)
+
+    def read_all():
+        return ([h.read_rect("BASE_CUR") for h in ens.members], [h.read_rect("WATER_CUR") for h in ens.members], [h.read_rect("WALL_CUR") for h in ens.members])
+
+    bases, waters, walls = read_all()
+    air = np.all([w[..., 1] != 0 for w in walls], axis=0)
+    ys, xs = np.nonzero(air)
+    rng = np.random.default_rng(1)
+
+    def observations():
+        vals = np.stack([(bases if field == "BASE_CUR" else waters)[i][..., c].astype(np.float64) for i in range(B)])
+        out = []
+        for k in rng.integers(0, len(xs), a.observations):
+            v = vals[:, ys[k], xs[k]]
+            sd = max(float(v.std()), 1e-3 * abs(float(v.mean())), 1e-6)
+            out.append((field, int(xs[k]), int(ys[k]), c, float(v.mean()) + sd * float(rng.normal()), 0.5 * sd * sd))
+        return out
+
+    obs = observations()
+    # member-cells x observations the update kernel may touch: weight != 0 where dx < 2 loc_x and dy < 2 loc_y (the members wrap in x)
+    yy, xx = np.mgrid[0:Y, 0:X]
+    touched = 0
+    for o in obs:
+        dx = np.abs(xx - o[1])
+        touched += int(((np.minimum(dx, X - dx) < 2 * loc[0]) & (np.abs(yy - o[2]) < 2 * loc[1])).sum())
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        ens.assimilate(obs, loc=loc, wrap_x=True, **gains)
+    ens[0].profile(True)
+    t_one, t_n, t_host, t_read, applied = [], [], [], [], 0
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        res = ens.assimilate(obs, loc=loc, wrap_x=True, **gains)
+        t_one.append(time.perf_counter() - t0)
+        applied = sum(r["applied"] for r in res)
+    prof = ens[0].profile_read()
+    ens[0].profile(False)
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        for o in obs:
+            ens.assimilate([o], loc=loc, wrap_x=True, **gains)
+        t_n.append(time.perf_counter() - t0)
+    drops = [h.read_particles() for h in ens.members] if a.droplets else [None] * B
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        bases, waters, walls = read_all()
+        t1 = time.perf_counter()
+        nb, nw, _ = E.ens_assim_cells(bases, waters, walls, X, Y, obs, loc=loc, wrap_x=True, **gains)
+        for i, h in enumerate(ens.members):
+            h.upload(nb[i], nw[i], walls[i], drops[i])
+        ens.sync()
+        t_read.append(t1 - t0)
+        t_host.append(time.perf_counter() - t0)
+    obs_ms, obs_n = prof.get("ensemble_assimilate_obs", (0.0, 0))
+    upd_ms, upd_n = prof.get("ensemble_assimilate", (0.0, 0))
+    obs_us, upd_us = 1e3 * obs_ms / max(obs_n, 1), 1e3 * upd_ms / max(upd_n, 1)
+    bytes_most = 76 * touched * B
+    ms = lambda t: round(1e3 * t, 3)
+    return {"field": field, "members": B, "observations": a.observations, "applied": applied, "loc": list(loc), "calls": a.repeats,
+            "one_call_ms": {"slowest": ms(max(t_one)), "median": ms(statistics.median(t_one))},
+            "n_calls_of_one_ms": {"slowest": ms(max(t_n)), "median": ms(statistics.median(t_n))},
+            "read_host_upload_route_ms": {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))},
+            "speedup_slowest_over_host_route": round(max(t_host) / max(t_one), 2), "speedup_slowest_over_n_calls": round(max(t_n) / max(t_one), 2),
+            "host_route_carries_the_state": False,
+            "host_route_loses": "wx_upload resets light, curl, the feedback textures and the lightning state: its members are fresh uploads, not the stepped simulation",
+            "obs_kernel_us": round(obs_us, 2), "obs_kernel_launches_timed": obs_n, "update_kernel_us": round(upd_us, 2), "update_kernel_launches_timed": upd_n,
+            "update_member_cell_observations": touched * B, "update_kernel_bytes_at_most": bytes_most,
+            "update_kernel_gb_per_s_at_most": round(bytes_most / (upd_us * 1e-6) / 1e9, 1) if upd_us > 0 else None,
+            "update_kernel_fraction_of_peak_at_most": round(bytes_most / (upd_us * 1e-6) / 1e9 / a.peak_gbs, 4) if upd_us > 0 else None}
+
+
 def main():
     a = parse()
+    if a.assimilate and (a.mode != "ensemble" or a.assimilate not in ("BASE_CUR", "WATER_CUR") or not 1 <= a.observations <= 256):
+        sys.exit("--assimilate BASE_CUR | WATER_CUR needs --mode ensemble and --observations 1 .. 256")
     if a.spawn and a.mode != "ensemble":
         sys.exit("--spawn needs --mode ensemble")
     if a.statistics and (a.mode != "ensemble" or a.statistics not in ("BASE_CUR", "WATER_CUR")):
@@ -373,6 +464,10 @@ def main():
             continue
         if a.quantiles:
             out["shapes"][spec] = {"members": B, "quantiles": time_quantiles(a, pkg, ens, X, Y, B)}
+            close()
+            continue
+        if a.assimilate:
+            out["shapes"][spec] = {"members": B, "assimilate": time_assimilate(a, pkg, ens, X, Y, B)}
             close()
             continue
 
