@@ -17,10 +17,16 @@
 // Extremes: per lane the best order-preserving key and its global index per channel (a lane meets its cells in rising global index, so
 // "strictly better" keeps the first occurrence), combined at the end as 64-bit keys (float order above the inverted index) with max.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <cmath>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define WXD_HD __host__ __device__
+#else // a host compiler takes the binning function and the 320-bit finish without the HIP headers (wx_ens_score_cell.h)
+#define WXD_HD
+#endif
 #include "../../include/wxsim.h"
 
 namespace wxd {
@@ -37,10 +43,10 @@ struct Term {
   long long addend; // 0: nothing to add (a zero, a non-finite value, a value outside the quantity's set of cells)
 };
 
-__host__ __device__ inline uint32_t f32_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+WXD_HD inline uint32_t f32_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
 
 // THE binning function: the kernel, wx_diag_accumulate and wx_diag_accumulate_cells all go through it
-__host__ __device__ inline Term term_of(float v, bool take)
+WXD_HD inline Term term_of(float v, bool take)
 {
   const uint32_t b = f32_bits(v), e = (b >> 23) & 255u, frac = b & 0x7FFFFFu;
   const uint32_t m = e ? (frac | 0x800000u) : frac, e1 = e ? e : 1u;
@@ -49,10 +55,10 @@ __host__ __device__ inline Term term_of(float v, bool take)
   if (e == 255u || !take) a = 0;
   return Term{(int)(e1 >> 4), a};
 }
-__host__ __device__ inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
-__host__ __device__ inline bool f32_nan(float v) { return (f32_bits(v) & 0x7FFFFFFFu) > 0x7F800000u; }
+WXD_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
+WXD_HD inline bool f32_nan(float v) { return (f32_bits(v) & 0x7FFFFFFFu) > 0x7F800000u; }
 // order-preserving key of a non-NaN float: a < b <=> ord(a) < ord(b); -0.0 and 0.0 share a key; never 0 and never 0xFFFFFFFF
-__host__ __device__ inline uint32_t ord_of(float v)
+WXD_HD inline uint32_t ord_of(float v)
 {
   uint32_t b = f32_bits(v);
   if (b == 0x80000000u) b = 0;
@@ -70,7 +76,7 @@ struct CellOut {
   uint32_t kmax[8], kmin[8]; // 0: no candidate
   int cnt[7];                // C_AIR .. C_VEG
 };
-__host__ __device__ inline void classify(const float v[8], int wall_dist, int wall_veg, bool in, CellOut &o)
+WXD_HD inline void classify(const float v[8], int wall_dist, int wall_veg, bool in, CellOut &o)
 {
   const bool wall = in && wall_dist == 0, air = in && wall_dist != 0;
   bool nfb = false, nfw = false;

@@ -73,25 +73,17 @@ __device__ __forceinline__ float ld_chan(wxe::CTab m, size_t off, unsigned c) { 
 __device__ __forceinline__ float ld_chan(wxe::CTab m, size_t off, unsigned c) { return ((const float *)m->field)[4 * off + c]; }
 #endif
 
-// P: the selection padded to a power of two, a template parameter so that a column's keys live in registers with constant indices
+// What k_ens_quant_staged<P> and k_ens_score<P> (wx_ens_score.h) share: the staging of one chunk's keys into the LDS image and the
+// register sort of a thread's column. P: the selection padded to a power of two, a template parameter so that a column's keys live in
+// registers with constant indices.
 template <int P>
-__global__ __launch_bounds__(WG) void k_ens_quant_staged(const Args a)
-{
-  constexpr int UN = P >= 32 ? 8 : (P >= 4 ? P / 4 : 1); // members a wave has in flight: all of its P / 4, at most 8 (32 per workgroup)
-  constexpr unsigned ROWS = P > RESULT_ROWS ? P : RESULT_ROWS;
-  extern __shared__ unsigned wxq_lds[]; // [row][channel][lane], ROWS rows
-  const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
-  const wxe::CTab tab = wxe::const_table(a.tab);
-  const unsigned n_sel = (unsigned)a.n_sel;
-  unsigned *const col = wxq_lds + wv * 64u + lane; // this thread's column: row i at col[i * 256]
-  static_assert(ROWS * 1024u <= 65536u && (P & (P - 1)) == 0, "the LDS image");
-  for (unsigned ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (workgroup-uniform trip count: every barrier below is reached by all)
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    const bool valid = x < (unsigned)a.w;
-    const size_t off = valid ? (size_t)(a.y0 + (int)y) * (size_t)a.X + (size_t)(a.x0 + (int)x) : 0, o = valid ? (size_t)y * (size_t)a.w + x : 0;
-    // 1. staging: wave wv takes members wv, wv + 4, ..., UN of them per batch. A member index past the selection is clamped for the
-    // load (the last member again, from the cache) and its keys are KEY_PAD: the batch stays one block of loads without a branch each
+struct Staged {
+  static constexpr int UN = P >= 32 ? 8 : (P >= 4 ? P / 4 : 1); // members a wave has in flight: all of its P / 4, at most 8 (32 per workgroup)
+  static_assert((P & (P - 1)) == 0 && P <= STAGED_MEMBERS, "the LDS image");
+  // 1. staging: wave wv takes members wv, wv + 4, ..., UN of them per batch. A member index past the selection is clamped for the
+  // load (the last member again, from the cache) and its keys are KEY_PAD: the batch stays one block of loads without a branch each
+  static __device__ __forceinline__ void stage(unsigned *lds, wxe::CTab tab, unsigned n_sel, size_t off, bool valid, unsigned lane, unsigned wv)
+  {
     for (unsigned k = wv; k < (unsigned)P; k += 4u * UN) {
       unsigned key[UN][4];
 #pragma unroll
@@ -112,14 +104,12 @@ __global__ __launch_bounds__(WG) void k_ens_quant_staged(const Args a)
 #pragma unroll
       for (int j = 0; j < UN; j++)
 #pragma unroll
-        for (int c = 0; c < 4; c++) wxq_lds[((k + 4u * j) * 4u + c) * 64u + lane] = key[j][c];
+        for (int c = 0; c < 4; c++) lds[((k + 4u * j) * 4u + c) * 64u + lane] = key[j][c];
     }
-    // the rank member's value of this thread's channel (in flight across the barrier)
-    unsigned t_key = KEY_PAD;
-    if (a.has_rank && valid) t_key = rank_key(cell_key(ld_chan(tab + n_sel, off, wv), wxe::ld_wall_dist(tab + n_sel, off)));
-    __syncthreads();
-    // 2. wave wv takes channel wv: its column into registers, a bitonic network over the member index (every index a constant)
-    unsigned key[P];
+  }
+  // 2. the thread's column (row i at col[i * 256]) into registers, a bitonic network over the member index (every index a constant)
+  static __device__ __forceinline__ void sorted_column(unsigned (&key)[P], const unsigned *col)
+  {
 #pragma unroll
     for (int i = 0; i < P; i++) key[i] = col[i * 256];
 #pragma unroll
@@ -132,6 +122,32 @@ __global__ __launch_bounds__(WG) void k_ens_quant_staged(const Args a)
             const unsigned lo = key[i] < key[i ^ j] ? key[i] : key[i ^ j], hi = key[i] < key[i ^ j] ? key[i ^ j] : key[i];
             key[i] = (i & kk) == 0 ? lo : hi, key[i ^ j] = (i & kk) == 0 ? hi : lo;
           }
+  }
+};
+
+template <int P>
+__global__ __launch_bounds__(WG) void k_ens_quant_staged(const Args a)
+{
+  constexpr unsigned ROWS = P > RESULT_ROWS ? P : RESULT_ROWS;
+  extern __shared__ unsigned wxq_lds[]; // [row][channel][lane], ROWS rows
+  const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
+  const wxe::CTab tab = wxe::const_table(a.tab);
+  const unsigned n_sel = (unsigned)a.n_sel;
+  unsigned *const col = wxq_lds + wv * 64u + lane; // this thread's column: row i at col[i * 256]
+  static_assert(ROWS * 1024u <= 65536u && (P & (P - 1)) == 0, "the LDS image");
+  for (unsigned ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (workgroup-uniform trip count: every barrier below is reached by all)
+    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
+    const bool valid = x < (unsigned)a.w;
+    const size_t off = valid ? (size_t)(a.y0 + (int)y) * (size_t)a.X + (size_t)(a.x0 + (int)x) : 0, o = valid ? (size_t)y * (size_t)a.w + x : 0;
+    Staged<P>::stage(wxq_lds, tab, n_sel, off, valid, lane, wv); // 1.
+    // the rank member's value of this thread's channel (in flight across the barrier)
+    unsigned t_key = KEY_PAD;
+    if (a.has_rank && valid) t_key = rank_key(cell_key(ld_chan(tab + n_sel, off, wv), wxe::ld_wall_dist(tab + n_sel, off)));
+    __syncthreads();
+    // 2. wave wv takes channel wv: its column into registers, a bitonic network over the member index (every index a constant)
+    unsigned key[P];
+    Staged<P>::sorted_column(key, col);
     // 3. the counts, then -- the ascending column back in LDS -- v(k), v(k1) by per-lane index
     Tally tl{0, 0, 0, 0};
 #pragma unroll

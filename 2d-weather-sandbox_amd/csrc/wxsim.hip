@@ -57,6 +57,7 @@ enum KernelId {
   K_ENS_STAT,   // per-cell statistics over the members of an ensemble (wx_ens_stat.h)
   K_ENS_PERTURB, // smooth noise added to / multiplied into the members of an ensemble (wx_ens_perturb.h)
   K_ENS_QUANT,  // per-cell quantiles and ranks over the members of an ensemble (wx_ens_quant.h)
+  K_ENS_SCORE,  // the members scored against a truth handle: exact domain sums, rank histograms (wx_ens_score.h)
   K_ENS_ASSIM_OBS, // point observations assimilated into the members: the observation-space pre-pass (wx_ens_assim.h)
   K_ENS_ASSIM,  // the state update of one field (wx_ens_assim.h)
   K_COUNT
@@ -64,7 +65,7 @@ enum KernelId {
 const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "boundary", "advection", "pressure", "lighting",
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
                                            "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb",
-                                           "ensemble_quantiles", "ensemble_assimilate_obs", "ensemble_assimilate"};
+                                           "ensemble_quantiles", "ensemble_scores", "ensemble_assimilate_obs", "ensemble_assimilate"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -2948,4 +2949,5 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 #include "wx_ens_stat.h" // (likewise)
 #include "wx_ens_perturb.h" // (likewise)
 #include "wx_ens_quant.h" // (likewise)
+#include "wx_ens_score.h" // (likewise)
 #include "wx_ens_assim.h" // (likewise)

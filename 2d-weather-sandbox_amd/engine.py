@@ -46,6 +46,7 @@ EXPORTS = [
     "wx_ensemble_statistics", "wx_ens_stat_cells",
     "wx_copy_state", "wx_ensemble_broadcast", "wx_ensemble_perturb", "wx_ens_perturb_cells",
     "wx_ensemble_quantiles", "wx_ens_quant_cells", "wx_ens_quant_staged_members",
+    "wx_ensemble_scores", "wx_ens_score_cells", "wx_ens_score_max_members",
     "wx_ensemble_assimilate", "wx_ens_assim_cells",
 ]
 
@@ -421,6 +422,64 @@ def ens_quant_cells(fields, walls, p, *, members=None, interp="linear", rank_of=
     return planes
 
 
+ENS_SCORE_BINS = 65
+ENS_SCORE_COUNTS = ("n_scored", "n_truth_excluded", "n_empty", "n_overflow", "sum_count")
+ENS_SCORE_SUMS = ("sum_error", "sum_abs_error", "sum_sq_error", "sum_variance", "sum_crps")
+ENS_SCORE_MAPS = ("error", "variance", "crps")
+
+
+class WxEnsScore(C.Structure):
+    """``wx_ens_score`` of include/wxsim.h, member for member: the scalars the call fills and the caller-owned maps (NULL = not wanted)."""
+    _fields_ = ([(k, C.c_int64 * 4) for k in ENS_SCORE_COUNTS] + [(k, C.c_double * 4) for k in ENS_SCORE_SUMS]
+                + [("rank_low", (C.c_int64 * ENS_SCORE_BINS) * 4), ("rank_high", (C.c_int64 * ENS_SCORE_BINS) * 4)] + [(k, C.c_void_p) for k in ENS_SCORE_MAPS])
+
+
+def _ens_score_struct(shape, want):
+    """A wx_ens_score whose maps named in ``want`` are fresh float32 arrays of ``shape`` + (4,), and those arrays by name."""
+    unknown = set(want) - set(ENS_SCORE_MAPS)
+    if unknown:
+        raise KeyError(f"no such map of wx_ens_score: {sorted(unknown)} (there are {ENS_SCORE_MAPS})")
+    st, maps = WxEnsScore(), {}
+    for name in ENS_SCORE_MAPS:
+        if name in want:
+            maps[name] = np.zeros(tuple(shape) + (4,), np.float32)
+            setattr(st, name, maps[name].ctypes.data)
+    return st, maps
+
+
+def _ens_score_dict(st: WxEnsScore, maps: dict) -> dict:
+    out = {k: np.array(getattr(st, k), np.int64) for k in ENS_SCORE_COUNTS}
+    out.update({k: np.array(getattr(st, k), np.float64) for k in ENS_SCORE_SUMS})
+    out["rank_low"] = np.array([list(r) for r in st.rank_low], np.int64)
+    out["rank_high"] = np.array([list(r) for r in st.rank_high], np.int64)
+    out.update(maps)
+    return out
+
+
+def ens_score_cells(fields, walls, truth_field, truth_wall, *, members=None, want=ENS_SCORE_MAPS) -> dict:
+    """wx_ens_score_cells: the score kernel's per-cell function and exact domain sums on the CPU. ``fields[i]`` / ``walls[i]``: member
+    i's cells, float32 (..., 4) and int8 (..., 4) of one common shape (an unselected member's entries may be None); ``truth_field`` /
+    ``truth_wall``: the truth's cells in that shape. Returns the entries of wx_ens_score: per channel n_scored, n_truth_excluded,
+    n_empty, n_overflow, sum_count (int64), sum_error, sum_abs_error, sum_sq_error, sum_variance, sum_crps (float64), rank_low /
+    rank_high (4, 65), and the maps named in ``want`` (error, variance, crps: (..., 4) float32, NaN where not scored)."""
+    f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in fields]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    tf, tw = np.ascontiguousarray(truth_field, np.float32), np.ascontiguousarray(truth_wall, np.int8)
+    n = len(f)
+    have = [a for a in f + wl if a is not None] + [tf, tw]
+    if n < 1 or len(wl) != n or any(a.shape != tf.shape or a.shape[-1:] != (4,) for a in have):
+        raise ValueError("one (..., 4) field and one (..., 4) wall array per member and for the truth, all of one shape")
+    shape = tf.shape[:-1]
+    st, maps = _ens_score_struct(shape, want)
+    fp = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in f])
+    wp = (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in wl])
+    mask = _member_mask(n, members)
+    rc = lib().wx_ens_score_cells(n, int(np.prod(shape, dtype=np.int64)), fp, wp, tf.ctypes.data, tw.ctypes.data, None if mask is None else mask.ctypes.data, C.byref(st))
+    if rc != 0:
+        raise WxError(rc, f"wx_ens_score_cells: no member or more than {Ensemble.SCORE_MAX_MEMBERS} selected, or a selected member absent")
+    return _ens_score_dict(st, maps)
+
+
 def build(force: bool = False, fast: bool = False) -> str:
     """Compile libwxsim.so (``fast``: the tolerance build libwxsim_fast.so) for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -575,6 +634,10 @@ def lib() -> C.CDLL:
     L.wx_ens_quant_cells.argtypes = [i32, C.c_size_t, vp, vp, vp, C.POINTER(WxEnsQuant)]
     L.wx_ens_quant_staged_members.argtypes = []
     L.wx_ens_quant_staged_members.restype = i32
+    L.wx_ensemble_scores.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, C.POINTER(WxEnsScore)]
+    L.wx_ens_score_cells.argtypes = [i32, C.c_size_t, vp, vp, vp, vp, vp, C.POINTER(WxEnsScore)]
+    L.wx_ens_score_max_members.argtypes = []
+    L.wx_ens_score_max_members.restype = i32
     L.wx_ensemble_assimilate.argtypes = [vp, C.POINTER(WxEnsAssim), i32, vp, vp, vp]
     L.wx_ens_assim_cells.argtypes = [C.POINTER(WxEnsAssim), i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     _lib = L
@@ -1179,6 +1242,27 @@ class Ensemble:
         mask = _quant_mask(self.n, members, rank_of)
         self._chk(lib().wx_ensemble_quantiles(self._e, FIELD_IDS[field], int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data, C.byref(st)))
         return planes
+
+    SCORE_MAX_MEMBERS = 64  # wx_ens_score_max_members(): the largest selection ``scores`` takes
+
+    def scores(self, field: str, truth: "Handle", x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, *, members=None,
+               want=()) -> dict:
+        """wx_ensemble_scores: the selected members (None: all but ``truth`` if it is a member of this ensemble) scored against the
+        ``truth`` handle -- a lone ``Handle``, an unselected member, a member of another ensemble -- over the rectangle of ``field``
+        (BASE_CUR or WATER_CUR). Returns the entries of wx_ens_score (``ens_score_cells``): exact domain sums of error, absolute
+        error, squared error, variance and CRPS per channel, the counts, the rank histograms, and the maps named in ``want`` (error,
+        variance, crps: (h, w, 4)). One launch on the device, a few hundred bytes back; blocks like ``sync``."""
+        w = self.X - x if w is None else w
+        h = self.Y - y if h is None else h
+        st, maps = _ens_score_struct((max(h, 0), max(w, 0)), want)
+        mask = _member_mask(self.n, members)
+        if members is None:
+            inside = [i for i, m in enumerate(self.members) if m is truth or (m._h.value == truth._h.value)]
+            if inside:
+                mask = np.ones(self.n, np.uint8)
+                mask[inside] = 0
+        self._chk(lib().wx_ensemble_scores(self._e, truth._h, FIELD_IDS[field], int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data, C.byref(st)))
+        return _ens_score_dict(st, maps)
 
     def broadcast(self, src: int, members=None):
         """wx_ensemble_broadcast: every selected member (None: all others) becomes a device-side clone of member ``src``

@@ -394,6 +394,26 @@ class WeatherEnsemble:
         """The per-cell median over the members, (h, w, 4): ``quantiles(field, (0.5,))["q"][0]``."""
         return self.quantiles(field, (0.5,), x, y, w, h, **kw)["q"][0]
 
+    def scores(self, field: str, truth, x: int = 0, y: int = 0, w: Optional[int] = None, h: Optional[int] = None, **kw) -> dict:
+        """``engine.Ensemble.scores``: the members scored against ``truth`` -- a ``WeatherSim`` (a nature run, a member of this or
+        another ensemble) or an ``engine.Handle`` -- on the device (members, want). On top of the exact sums, counts and rank histograms
+        the derived numbers per channel in plain float64, NaN where nothing was scored: ``bias`` = sum_error / n_scored, ``mae``,
+        ``rmse`` = sqrt(sum_sq_error / n_scored), ``spread`` = sqrt(sum_variance / n_scored), ``crps``, and ``rank_histogram`` =
+        (rank_low + rank_high) / 2 -- tied cells split evenly between the two ends of their tie. The maps asked for with ``want``
+        (error, variance, crps) come back under ``maps``."""
+        from .engine import ENS_SCORE_MAPS
+        out = self._e.scores(field, getattr(truth, "handle", truth), x, y, w, h, **kw)
+        out["maps"] = {k: out.pop(k) for k in ENS_SCORE_MAPS if k in out}
+        n = out["n_scored"].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["bias"] = out["sum_error"] / n
+            out["mae"] = out["sum_abs_error"] / n
+            out["rmse"] = np.sqrt(out["sum_sq_error"] / n)
+            out["spread"] = np.sqrt(out["sum_variance"] / n)
+            out["crps"] = out["sum_crps"] / n
+        out["rank_histogram"] = (out["rank_low"] + out["rank_high"]).astype(np.float64) / 2.0
+        return out
+
     @property
     def engine(self):
         return self._e

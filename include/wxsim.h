@@ -881,6 +881,68 @@ int wx_ensemble_assimilate(wx_ensemble *e, const wx_ens_assim *a, int n_obs, con
 int wx_ens_assim_cells(const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs, wx_ens_obs_result *result, int X, int Y, int n_members,
                        float *const *base, float *const *water, const int8_t *const *wall, const uint8_t *member_mask);
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_SCORES) The members scored against a truth run on the device: what an observing-system experiment
+ * asks after every cycle -- did the ensemble get closer to the nature run, and is its spread honest? One call reads the selected
+ * members and the truth once and returns, per channel, the exact domain sums of error, absolute error, squared error, ensemble
+ * variance and CRPS, two rank histograms and the counts that go with them: a few hundred bytes instead of a dozen planes. The result
+ * does not depend on the order of the members, the launch shape or the build.
+ *
+ * THE PER-CELL FUNCTION (the kernel, wx_ens_score_cells and the tests all evaluate this definition). For cell (x, y) and channel c:
+ *   Which values enter. Exactly as in wx_ensemble_quantiles, with the same keys: a selected member in which the cell is a wall cell
+ *   contributes nothing, of the remaining values the FINITE ones enter, an entered -0.0 is taken as +0.0. n counts them and
+ *   v(0) <= v(1) <= ... <= v(n-1) are the entered values in ascending order.
+ *   Truth. t = channel c of the same cell of `truth`'s `field`, -0.0 taken as +0.0.
+ *   When a cell-channel is scored. All three must hold, otherwise it is counted in exactly ONE of the reason counters, tested in this
+ *   order: (1) the cell is an air cell in `truth` (channel 1 of its WX_FIELD_WALL_CUR texel != 0) and t is finite -- else
+ *   n_truth_excluded; (2) n >= 1 -- else n_empty; (3) all five per-cell floats below are finite -- else n_overflow.
+ *   Per-cell arithmetic. All arithmetic is double, every operation rounded separately (no fused multiply-add: contraction is off inside
+ *   every function that rounds and every product that feeds a sum is a value of its own in every build, so libwxsim.so,
+ *   libwxsim_fast.so, the device and the host give the same bits). All sums start at +0.0 and run in ASCENDING order of the values,
+ *   i = 0 first -- not in member order.
+ *     u_i = (double)v(i) - (double)t
+ *     S = sum (double)v(i);  m = S / n;  err = m - (double)t
+ *     Q = sum d_i*d_i with d_i = (double)v(i) - m;  var = Q / n -- the POPULATION variance. Its bits differ from the variance plane of
+ *       wx_ensemble_statistics, which sums in member order.
+ *     A = sum |u_i|;  G = sum (double)(2*i - n + 1) * u_i;  crps = A / n - G / ((double)n * (double)n) -- the standard ensemble CRPS,
+ *       mean |x - t| - 1/(2 n^2) sum sum |x_i - x_j|, the double sum taken over the sorted values. No clamp at 0. With identical members
+ *       equal to t, G is exactly 0 and crps is +0.0.
+ *     The five floats: e = (float)err, ae = (float)fabs(err), se = (float)(err*err), vr = (float)var, cr = (float)crps.
+ *   Rank. n_below = the number of entered values with v < t, n_equal = the number with v == t (the quantile call's float compare:
+ *   -0.0 == 0.0). Each scored cell-channel adds 1 to rank_low[c][n_below] and 1 to rank_high[c][n_below + n_equal]: an untied cell lands
+ *   in the same bin of both. How ties are split between the two is the host's business: integers are exact.
+ *   Domain sums. Per channel, over the scored cell-channels: sum_error, sum_abs_error, sum_sq_error, sum_variance and sum_crps are the
+ *   EXACT sums of the floats e, ae, se, vr, cr, rounded to double once -- the correctly rounded double of the exact sum, what Python's
+ *   math.fsum returns -- taken with wx_diag's integer bins and its 320-bit finish. n_scored[c] counts the scored cell-channels,
+ *   sum_count[c] is the sum of their n.
+ *   The optional maps error, variance, crps (w*h*4 each) hold e, vr, cr, NaN where the cell-channel is not scored.
+ *
+ * wx_ensemble_scores. Answered before the device is touched -- WX_E_INVALID: e, truth or out NULL; a field other than WX_FIELD_BASE_CUR /
+ * WX_FIELD_WATER_CUR; nobody selected; more than wx_ens_score_max_members() selected (the message says so: a streaming path can follow);
+ * `truth` is a selected member of e; `truth` is a slab handle, a handle of another X or Y, or a handle on another device. WX_E_RANGE: the
+ * rectangle does not lie inside the grid (no wrap). WX_E_STATE: a selected member, or `truth`, was never uploaded (the message names it).
+ * `truth` is any whole-domain handle: a lone one, an unselected member of e, a member of another ensemble. The work is ordered behind
+ * everything pending on the ensemble's stream AND on truth's stream, as wx_copy_state orders two handles: truth's pending report is
+ * consumed and returned first ("truth: ..."), and then nothing is launched. Everything else as for wx_ensemble_quantiles: member_mask has
+ * one byte per member (NULL = all), the members' pointers are taken at the time of the call, the call BLOCKS like wx_ensemble_sync and
+ * consumes and returns a member's pending report ("member i: ..."), it changes nothing, its device buffers belong to the ensemble and go
+ * with wx_ensemble_destroy, and wx_profile on member 0 times the launch (kernel name "ensemble_scores").
+ * wx_ens_score_cells (host only, pure): the same function over n_cells cells the caller holds, member i's cells at field[i] (4 floats
+ * per cell) / wall[i] (4 bytes per cell), the truth's at truth_field / truth_wall; maps as above with w*h = n_cells. WX_E_INVALID as
+ * above, and for n_members < 1, a NULL table, truth array or output struct, a NULL entry of a selected member. */
+#define WX_HAVE_ENSEMBLE_SCORES 1
+#define WX_ENS_SCORE_BINS 65       /* n_below and n_below + n_equal lie in 0 .. wx_ens_score_max_members() */
+typedef struct wx_ens_score {
+  int64_t n_scored[4], n_truth_excluded[4], n_empty[4], n_overflow[4], sum_count[4];
+  double  sum_error[4], sum_abs_error[4], sum_sq_error[4], sum_variance[4], sum_crps[4];
+  int64_t rank_low[4][WX_ENS_SCORE_BINS], rank_high[4][WX_ENS_SCORE_BINS];
+  float  *error, *variance, *crps; /* optional w*h*4 maps, NaN where the cell-channel is not scored; NULL: not wanted */
+} wx_ens_score;
+int wx_ensemble_scores(wx_ensemble *e, wx_sim *truth, int field, int x, int y, int w, int h,
+                       const uint8_t *member_mask /* n_members bytes, NULL = all */, wx_ens_score *out);
+int wx_ens_score_cells(int n_members, size_t n_cells, const float *const *field, const int8_t *const *wall,
+                       const float *truth_field, const int8_t *truth_wall, const uint8_t *member_mask, wx_ens_score *out);
+int wx_ens_score_max_members(void);  /* == wx_ens_quant_staged_members() */
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

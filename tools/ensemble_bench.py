@@ -25,6 +25,12 @@ and the definition's arithmetic in numpy -- after --frame iterations, --repeats 
 the kernel's own time (wx_profile on member 0) and, from the same run, the time of the ensemble_statistics kernel with the variance
 wanted (two passes over the members). Without --shapes: the two shapes the statistics were measured at and one on the streaming path
 (more members than wx_ens_quant_staged_members()): 100x100x64, 2500x300x8, 100x100x96.
+--scores FIELD (BASE_CUR or WATER_CUR; --mode ensemble): what ONE wx_ensemble_scores call over the whole grid costs (B members scored
+against a truth that is member B of an ensemble of B + 1; no maps: a few hundred bytes come back; host to host) against the route it
+replaces -- wx_ensemble_statistics for mean and variance, wx_ensemble_quantiles with rank_of for n_below / n_equal, read_rect of the
+truth, and for the CRPS, which no existing call gives, B read_rect calls, np.sort along the member axis and the weighted sums in numpy
+-- after --frame iterations, --repeats calls of each; under the shape's "scores" key with the kernel's own time (wx_profile on member 0)
+and, from the same run, the quantile kernel's. Without --shapes: 100x100x64 and 2500x300x8.
 --spawn (--mode ensemble): B members made from ONE stepped state (a lone handle after --frame x 5 iterations), timed two ways, host to
 host, --repeats times each: route A = wx_copy_state into member 0 + wx_ensemble_broadcast + ONE wx_ensemble_perturb (temperature, lattice
 pitch 8); route B = what a host did before -- B wx_upload calls of host arrays (the state read back once, untimed; per member numpy noise
@@ -62,6 +68,7 @@ def parse():
     ap.add_argument("--droplets", type=int, default=0, help="droplets per member (0: none, precipitation off)")
     ap.add_argument("--statistics", default="", metavar="FIELD", help="time one statistics call over the whole grid against B read_rect calls + numpy (BASE_CUR or WATER_CUR)")
     ap.add_argument("--quantiles", default="", metavar="FIELD", help="time one quantile call over the whole grid against B read_rect calls + np.sort (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--scores", default="", metavar="FIELD", help="time one score call (B members against member B of B + 1) against statistics + quantiles + read_rect + numpy (BASE_CUR or WATER_CUR)")
     ap.add_argument("--assimilate", default="", metavar="FIELD", help="time one assimilation call of --observations point observations against N calls of one and against read_rect + host function + uploads (BASE_CUR or WATER_CUR)")
     ap.add_argument("--observations", type=int, default=40, help="observations per call with --assimilate (1 .. 256)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
@@ -69,7 +76,7 @@ def parse():
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
+        a.shapes = "100x100x64,2500x300x8" if a.scores else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
     return a
 
 
@@ -272,6 +279,87 @@ def time_quantiles(a, pkg, ens, X, Y, B):
             "quantiles_kernel_over_statistics_kernel": round(kernel_us / stat_us, 3) if stat_us > 0 else None}
 
 
+def numpy_scores(stat, rank, truth, truth_wall, fields, walls):
+    """What a host reduces the planes to today: the domain sums in plain float64 (np.sum, not exact), the two histograms, and the CRPS
+    from the members' sorted values."""
+    import numpy as np
+    n = stat["count"]
+    with np.errstate(all="ignore"):
+        ok = (truth_wall[..., 1] != 0)[..., None] & np.isfinite(truth) & (n > 0)
+        err = stat["mean"].astype(np.float64) - truth
+        v = np.stack(fields)
+        take = ~np.stack([wl[..., 1] == 0 for wl in walls])[..., None] & np.isfinite(v)
+        s = np.sort(np.where(take, v, np.float32(np.inf)), axis=0).astype(np.float64)
+        i = np.arange(len(fields)).reshape(-1, 1, 1, 1)
+        inside = i < n
+        u = s - truth.astype(np.float64)
+        A = np.where(inside, np.abs(u), 0.0).sum(0)
+        G = np.where(inside, (2 * i - n + 1) * u, 0.0).sum(0)
+        crps = A / n - G / (n.astype(np.float64) ** 2)
+    out = {"n_scored": ok.sum((0, 1))}
+    for name, x in (("sum_error", err), ("sum_abs_error", np.abs(err)), ("sum_sq_error", err * err), ("sum_variance", stat["variance"].astype(np.float64)), ("sum_crps", crps)):
+        out[name] = np.where(ok, x, 0.0).sum((0, 1))
+    out["rank_low"] = np.stack([np.bincount(rank["n_below"][..., c][ok[..., c]], minlength=65) for c in range(4)])
+    out["rank_high"] = np.stack([np.bincount((rank["n_below"] + rank["n_equal"])[..., c][ok[..., c]], minlength=65) for c in range(4)])
+    return out
+
+
+def time_scores(a, pkg, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    field = a.scores
+    sel = list(range(B))
+
+    def device():
+        return ens.scores(field, ens[B], members=sel)
+
+    def host():
+        t0 = time.perf_counter()
+        stat = ens.statistics(field, members=sel, want=("mean", "variance", "count"))
+        rank = ens.quantiles(field, (), rank_of=B, want=("n_below", "n_equal"))
+        truth, truth_wall = ens[B].read_rect(field), ens[B].read_rect("WALL_CUR")
+        fields, walls = [ens[i].read_rect(field) for i in sel], [ens[i].read_rect("WALL_CUR") for i in sel]
+        t1 = time.perf_counter()
+        return numpy_scores(stat, rank, truth, truth_wall, fields, walls), t1 - t0
+
+    ens.step(a.frame)
+    ens.sync()
+    got, (want, _) = device(), host()
+    scale = 1e-7 * X * Y * max(1.0, float(np.nanmax(np.abs(ens[B].read_rect(field)))))
+    for k, v in want.items():  # two routes that disagree are not two timings of one thing (the host's means are float32 and its sums cancel: loose)
+        if not (np.array_equal(got[k], v) if v.dtype.kind == "i" else np.allclose(got[k], v, rtol=1e-4, atol=scale)):
+            sys.exit("--scores %s %dx%dx%d: wx_ensemble_scores and the host route disagree in %s: %r / %r" % (field, X, Y, B, k, got[k], v))
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        device()
+    ens[0].profile(True)
+    t_dev, t_host, t_calls = [], [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        device()
+        t_dev.append(time.perf_counter() - t0)
+    kernel_ms, launches = ens[0].profile_read().get("ensemble_scores", (0.0, 0))
+    for _ in range(a.repeats):  # the comparison: the quantile kernel reads the same bytes and sorts the same keys
+        ens.quantiles(field, (0.1, 0.5, 0.9), members=sel)
+    quant_ms, quant_launches = ens[0].profile_read().get("ensemble_quantiles", (0.0, 0))
+    ens[0].profile(False)
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        _, calls = host()
+        t_calls.append(calls)
+        t_host.append(time.perf_counter() - t0)
+    kernel_us, quant_us = 1e3 * kernel_ms / max(launches, 1), 1e3 * quant_ms / max(quant_launches, 1)
+    ms = lambda t: round(1e3 * t, 3)
+    return {"field": field, "members": B, "calls": a.repeats, "same_numbers": True, "n_scored": [int(v) for v in got["n_scored"]],
+            "scores_call_ms": {"slowest": ms(max(t_dev)), "median": ms(statistics.median(t_dev))},
+            "host_route_ms": {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_calls_and_read_rect_median": ms(statistics.median(t_calls))},
+            "speedup_slowest": round(max(t_host) / max(t_dev), 2),
+            "kernel_us": round(kernel_us, 2), "kernel_launches_timed": launches,
+            "kernel_gb_read_per_s": round(20 * X * Y * (B + 1) / (kernel_us * 1e-6) / 1e9, 1) if kernel_us > 0 else None,
+            "quantiles_kernel_us": round(quant_us, 2), "quantiles_kernel_launches_timed": quant_launches,
+            "scores_kernel_over_quantiles_kernel": round(kernel_us / quant_us, 3) if quant_us > 0 else None}
+
+
 def time_spawn(a, pkg, ens, X, Y, B):
     import statistics
     import numpy as np
@@ -419,6 +507,8 @@ def main():
         sys.exit("--statistics BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.quantiles and (a.mode != "ensemble" or a.quantiles not in ("BASE_CUR", "WATER_CUR")):
         sys.exit("--quantiles BASE_CUR | WATER_CUR needs --mode ensemble")
+    if a.scores and (a.mode != "ensemble" or a.scores not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--scores BASE_CUR | WATER_CUR needs --mode ensemble")
     sys.path.insert(0, a.root)
     if a.share > 0:
         if "debug" not in os.environ.get("WXSIM_LIB", ""):
@@ -437,6 +527,12 @@ def main():
         if a.spawn:
             ens = E.Ensemble(B, X, Y, a.droplets)
             out["shapes"][spec] = {"members": B, "spawn": time_spawn(a, pkg, ens, X, Y, B)}
+            ens.close()
+            continue
+        if a.scores:  # B members and the truth behind them
+            ens = E.Ensemble(B + 1, X, Y)
+            make_members(pkg, X, Y, B + 1, lambda i: ens[i], a.flow, 0)
+            out["shapes"][spec] = {"members": B, "scores": time_scores(a, pkg, ens, X, Y, B)}
             ens.close()
             continue
         if a.mode == "ensemble":
