@@ -4,6 +4,7 @@ host entry point -- the serial definition built from the kernels' own functions 
 `reference` below restates in plain Python: Python floats are doubles, ONE Python operation per rounded operation, math.sqrt, and
 numpy only for the double -> float32 conversion. Every comparison of states is `==` on bits, NaNs compared as positions."""
 import ctypes as C
+import functools
 import math
 import os
 import re
@@ -282,54 +283,69 @@ def planted(B=5, X=17, Y=7):
     return bases, waters, wl, X, Y
 
 
-def test_planted_wall_and_nonfinite_observations_are_skipped(pkg):
-    bases, waters, wl, X, Y = planted()
+# THE PLANTED CASES. Each is a function of `run` -- run(bases, waters, walls, X, Y, observations, where, **keywords) -> (bases, waters,
+# results) after the call -- that builds its arrays, hands them to `run` and applies the value-level assertions to what comes back.
+# Here `run` is `check` (the host function, held to `reference`); tests/test_ensemble_assimilate_gpu.py hands in the device call on
+# the same arrays. B = 5 members walk the kernels' remainder loop alone, B = 9 a load group of 8 and one member behind it.
+def planted_skipped(run, B=5):
+    bases, waters, wl, X, Y = planted(B)
     wl[2][3, 4, 1] = 0  # the observed cell is a wall in one member
     bases[1][2, 9, 3] = NAN
-    bases[4][4, 12, 3] = -INF
+    bases[B - 1][4, 12, 3] = -INF
     obs = [(B_, 4, 3, 3, 301.0, 0.1), (B_, 9, 2, 3, 301.0, 0.1), (B_, 12, 4, 3, 301.0, 0.1)]
-    gb, gw, res = check(pkg, bases, waters, wl, X, Y, obs, "skipped", gain_base=1.0, gain_water=1.0, loc=(4.0, 3.0))
+    gb, gw, res = run(bases, waters, wl, X, Y, obs, "skipped", gain_base=1.0, gain_water=1.0, loc=(4.0, 3.0))
     assert [r["applied"] for r in res] == [False] * 3 and all(r[k] != r[k] for r in res for k in ("prior_mean", "prior_var", "innovation", "alpha"))
     assert all(same_bits(a, b) for a, b in zip(gb + gw, bases + waters))
 
 
-def test_planted_nan_in_a_state_cell_leaves_that_channel_in_all_members(pkg):
-    bases, waters, wl, X, Y = planted()
-    bases[3][3, 6, 0] = NAN
+def planted_state_nan(run, B=5, member=3):
+    bases, waters, wl, X, Y = planted(B)
+    bases[member][3, 6, 0] = NAN
     obs = [(B_, 5, 3, 3, 301.5, 0.1)]
-    gb, _, res = check(pkg, bases, waters, wl, X, Y, obs, "state nan", gain_base=1.0, loc=(4.0, 3.0))
+    gb, _, res = run(bases, waters, wl, X, Y, obs, "state nan", gain_base=1.0, loc=(4.0, 3.0))
     assert res[0]["applied"]
     ch = np.stack([changed(a, b) for a, b in zip(gb, bases)])  # (member, y, x, c)
     assert not ch[:, 3, 6, 0].any() and ch[:, 3, 6, 1:].all()
 
 
-def test_planted_equal_members_change_nothing_and_keep_the_sign_of_zero(pkg):
-    bases, waters, wl, X, Y = planted()
+def planted_state_wall(run, B=5, member=3):
+    """A state cell that is a wall in ONE member is left alone in all of them, in every channel (the entry test of the member walk)."""
+    bases, waters, wl, X, Y = planted(B)
+    wl[member][3, 6, 1] = 0
+    obs = [(B_, 5, 3, 3, 301.5, 0.1)]
+    gb, gw, res = run(bases, waters, wl, X, Y, obs, "state wall", gain_base=1.0, gain_water=1.0, loc=(4.0, 3.0))
+    assert res[0]["applied"]
+    ch = np.stack([changed(a, b) for a, b in zip(gb + gw, bases + waters)])
+    assert not ch[:, 3, 6].any() and ch[:, 3, 7, 3].all() and not ch[:, 0].any()  # (row 0 is the floor: a wall in every member)
+
+
+def planted_equal_members(run, B=5):
+    bases, waters, wl, X, Y = planted(B)
     for b in bases:
         b[...] = bases[0]
         b[2, 3:9, 0] = -0.0
     obs = [(B_, 5, 3, 3, 305.0, 0.1)]
-    gb, _, res = check(pkg, bases, waters, wl, X, Y, obs, "V = 0", gain_base=1.0)
+    gb, _, res = run(bases, waters, wl, X, Y, obs, "V = 0", gain_base=1.0)
     assert res[0]["applied"] and res[0]["prior_var"] == 0.0 and res[0]["alpha"] == 0.5
     assert all(same_bits(a, b) for a, b in zip(gb, bases))
     # members that differ in temperature only: C = 0 for vx, whose -0.0 keep their sign bit, while the temperature moves
     for i, b in enumerate(bases):
         b[..., 3] += np.float32(0.25 * i)
-    gb, _, _ = check(pkg, bases, waters, wl, X, Y, obs, "C = 0", gain_base=1.0)
+    gb, _, _ = run(bases, waters, wl, X, Y, obs, "C = 0", gain_base=1.0)
     assert all(same_bits(a[..., :3], b[..., :3]) for a, b in zip(gb, bases)) and all(np.signbit(a[2, 3:9, 0]).all() for a in gb)
     assert all(changed(a, b)[..., 3].any() for a, b in zip(gb, bases))
 
 
-def test_planted_gain_zero_clamp_and_overflow(pkg):
-    bases, waters, wl, X, Y = planted()
+def planted_gain_zero_clamp_and_overflow(run, B=5):
+    bases, waters, wl, X, Y = planted(B)
     obs = [(B_, 5, 3, 3, 303.0, 0.01)]
-    gb, gw, _ = check(pkg, bases, waters, wl, X, Y, obs, "gain 0", gain_base=(1, 0, 1, 1), gain_water=(0, 1, 0, 1))
+    gb, gw, _ = run(bases, waters, wl, X, Y, obs, "gain 0", gain_base=(1, 0, 1, 1), gain_water=(0, 1, 0, 1))
     for a, b in zip(gb, bases):
         assert not changed(a, b)[..., 1].any() and changed(a, b)[..., 3].any()
     for a, b in zip(gw, waters):
         assert not changed(a, b)[..., 0].any() and not changed(a, b)[..., 2].any() and changed(a, b)[..., 3].any()
-    free, _, _ = check(pkg, bases, waters, wl, X, Y, obs, "no clamp", gain_base=1.0)
-    gb, _, _ = check(pkg, bases, waters, wl, X, Y, obs, "clamp", gain_base=1.0, hi_base=(NAN, NAN, NAN, 300.75), lo_base=(0.05, NAN, NAN, NAN))
+    free, _, _ = run(bases, waters, wl, X, Y, obs, "no clamp", gain_base=1.0)
+    gb, _, _ = run(bases, waters, wl, X, Y, obs, "clamp", gain_base=1.0, hi_base=(NAN, NAN, NAN, 300.75), lo_base=(0.05, NAN, NAN, NAN))
     # the clamp bites: where the unclamped update leaves the interval, the clamped one sits on its edge (untouched cells -- the floor --
     # are not clamped)
     hit_hi = hit_lo = 0
@@ -341,25 +357,25 @@ def test_planted_gain_zero_clamp_and_overflow(pkg):
         hit_hi, hit_lo = hit_hi + int(over.sum()), hit_lo + int(under.sum())
     assert hit_hi > 0 and hit_lo > 0
     # a result that overflows float: the increment at the observed cell would carry member 0 beyond FLT_MAX, so it keeps its bits
-    for i, b in enumerate(bases):
-        b[3, 5, 3] = FLT_MAX * np.float32(0.5 + 0.1 * i)
+    for i, b in enumerate(bases):  # (i % 5: members 5 .. repeat the factors of 0 .., so that every one stays a float)
+        b[3, 5, 3] = FLT_MAX * np.float32(0.5 + 0.1 * (i % 5))
     obs = [(B_, 5, 3, 3, -float(FLT_MAX), 1e30)]
-    gb, _, res = check(pkg, bases, waters, wl, X, Y, obs, "overflow", gain_base=(0, 0, 0, 1), gain_water=0.0, loc=(1.0, 1.0))
+    gb, _, res = run(bases, waters, wl, X, Y, obs, "overflow", gain_base=(0, 0, 0, 1), gain_water=0.0, loc=(1.0, 1.0))
     assert res[0]["applied"]
     big = [(B_, 5, 3, 3, float(FLT_MAX), 1e-30)]
     for i, b in enumerate(bases):
-        b[3, 5, 3] = -FLT_MAX * np.float32(0.5 + 0.1 * i)
-        b[3, 6, 3] = FLT_MAX * np.float32(0.99 - 0.2 * i)  # correlated negatively and large: K * innovation leaves the float range
-    gb, _, res = check(pkg, bases, waters, wl, X, Y, big, "overflow 2", gain_base=(0, 0, 0, 8), gain_water=0.0, loc=(1.5, 1.0))
+        b[3, 5, 3] = -FLT_MAX * np.float32(0.5 + 0.1 * (i % 5))
+        b[3, 6, 3] = FLT_MAX * np.float32(0.99 - 0.2 * (i % 5))  # correlated negatively and large: K * innovation leaves the float range
+    gb, _, res = run(bases, waters, wl, X, Y, big, "overflow 2", gain_base=(0, 0, 0, 8), gain_water=0.0, loc=(1.5, 1.0))
     kept = [not changed(a, b)[3, 6, 3] for a, b in zip(gb, bases)]
     assert res[0]["applied"] and any(kept), kept
 
 
-def test_planted_localization_edges_and_wrap(pkg):
-    bases, waters, wl, X, Y = planted()
+def planted_localization_edges_and_wrap(run, B=5):
+    bases, waters, wl, X, Y = planted(B)
     obs = [(B_, 8, 3, 3, 302.0, 0.05)]
     for loc in ((0.0, 0.0), (3.0, 0.0), (0.0, 1.0), (3.0, 1.0)):
-        gb, _, _ = check(pkg, bases, waters, wl, X, Y, obs, ("loc", loc), gain_base=1.0, loc=loc)
+        gb, _, _ = run(bases, waters, wl, X, Y, obs, ("loc", loc), gain_base=1.0, loc=loc)
         ch = np.stack([changed(a, b)[..., 3] for a, b in zip(gb, bases)]).any(axis=0)
         ys, xs = np.nonzero(ch)
         # dx == loc is inside (G(1) = 5/24 > 0), dx == 2 loc is the first cell outside (G(2) = 0); row 0 is the floor
@@ -373,19 +389,19 @@ def test_planted_localization_edges_and_wrap(pkg):
     # an observation at x = 0 reaches x = X - 1 with wrap_x, and not without
     obs = [(B_, 0, 3, 3, 302.0, 0.05)]
     for wrap in (True, False):
-        gb, _, _ = check(pkg, bases, waters, wl, X, Y, obs, ("wrap", wrap), gain_base=1.0, loc=(2.0, 1.0), wrap_x=wrap)
+        gb, _, _ = run(bases, waters, wl, X, Y, obs, ("wrap", wrap), gain_base=1.0, loc=(2.0, 1.0), wrap_x=wrap)
         ch = np.stack([changed(a, b)[..., 3] for a, b in zip(gb, bases)]).any(axis=0)
         assert ch[3, 0] and ch[3, 3] and not ch[3, 4]
         assert ch[3, X - 1] == wrap and ch[3, X - 3] == wrap and not ch[3, X - 4]
 
 
-def test_planted_observation_outside_the_rectangle_duplicates_and_overlap(pkg):
-    bases, waters, wl, X, Y = planted()
+def planted_observation_outside_the_rectangle_duplicates_and_overlap(run, B=5):
+    bases, waters, wl, X, Y = planted(B)
     rect = (6, 1, 8, 5)
     obs = [(B_, 3, 3, 3, 302.0, 0.05),   # outside the rectangle, its footprint reaches in
            (B_, 8, 3, 3, 301.0, 0.05), (B_, 8, 3, 3, 300.0, 0.05),  # twice the same cell and channel
            (W_, 10, 4, 0, 0.011, 1e-7), (B_, 11, 3, 3, 299.5, 0.1)]  # overlapping footprints, two fields
-    gb, gw, res = check(pkg, bases, waters, wl, X, Y, obs, "outside, duplicates, overlap", gain_base=1.0, gain_water=1.0, loc=(4.0, 2.0), rect=rect)
+    gb, gw, res = run(bases, waters, wl, X, Y, obs, "outside, duplicates, overlap", gain_base=1.0, gain_water=1.0, loc=(4.0, 2.0), rect=rect)
     assert all(r["applied"] for r in res)
     inside = np.zeros((Y, X), bool)
     inside[1:6, 6:14] = True
@@ -393,6 +409,46 @@ def test_planted_observation_outside_the_rectangle_duplicates_and_overlap(pkg):
         assert not changed(a, b)[~inside].any() and changed(a, b)[inside].any()
     assert res[2]["prior_var"] < res[1]["prior_var"]  # the second of the pair sees what the first left
     assert res[2]["prior_mean"] != res[1]["prior_mean"]
+
+
+# (case, the keywords that place the planted NaN / wall: inside the load group of 8 and in the remainder member behind it)
+PLANTED = [(planted_skipped, [{}]), (planted_state_nan, [dict(member=3), dict(member=-1)]), (planted_state_wall, [dict(member=3), dict(member=-1)]),
+           (planted_equal_members, [{}]), (planted_gain_zero_clamp_and_overflow, [{}]), (planted_localization_edges_and_wrap, [{}]),
+           (planted_observation_outside_the_rectangle_duplicates_and_overlap, [{}])]
+PLANTED_IDS = [f.__name__[len("planted_"):] for f, _ in PLANTED]
+
+
+def test_planted_wall_and_nonfinite_observations_are_skipped(pkg):
+    planted_skipped(functools.partial(check, pkg))
+
+
+def test_planted_nan_in_a_state_cell_leaves_that_channel_in_all_members(pkg):
+    planted_state_nan(functools.partial(check, pkg))
+
+
+def test_planted_equal_members_change_nothing_and_keep_the_sign_of_zero(pkg):
+    planted_equal_members(functools.partial(check, pkg))
+
+
+def test_planted_gain_zero_clamp_and_overflow(pkg):
+    planted_gain_zero_clamp_and_overflow(functools.partial(check, pkg))
+
+
+def test_planted_localization_edges_and_wrap(pkg):
+    planted_localization_edges_and_wrap(functools.partial(check, pkg))
+
+
+def test_planted_observation_outside_the_rectangle_duplicates_and_overlap(pkg):
+    planted_observation_outside_the_rectangle_duplicates_and_overlap(functools.partial(check, pkg))
+
+
+@pytest.mark.parametrize("case,placements", PLANTED, ids=PLANTED_IDS)
+def test_planted_cases_with_a_load_group_of_8_and_a_member_behind_it(pkg, case, placements):
+    """Every planted case on B = 9 members (the cases above are B = 5), and a wall in one member's state cell on both."""
+    for kw in placements:
+        case(functools.partial(check, pkg), B=9, **kw)
+    if case is planted_state_wall:
+        case(functools.partial(check, pkg), B=5)
 
 
 # tools/find_assimilate_separators.py: (product, the three members' float32 values, observed value, error variance, member 0 after:

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import impulse_scenes as I
-from test_ensemble_assimilate_cpu import SEPARATOR_KW, SEPARATORS, plant_separators, separator_cell
+from test_ensemble_assimilate_cpu import PLANTED, PLANTED_IDS, SEPARATOR_KW, SEPARATORS, plant_separators, separator_cell
 from test_ensemble_gpu import same_bits
 from test_ensemble_perturb_gpu import pre_values
 from test_ensemble_statistics_gpu import make_ensemble, member_specs
@@ -233,6 +233,45 @@ def test_planted_separators_on_the_device(pkg):
         check_separators(pkg, specs, obs, ens[0].read_rect(B_), res)
     finally:
         ens.close()
+
+
+def device_run(pkg):
+    """`run` of the planted cases of tests/test_ensemble_assimilate_cpu.py on the device: the arrays are uploaded as they are (nothing
+    is stepped), the call is made, what the members hold then and the results equal the host function's bit for bit, and the device's
+    arrays go back to the case's value-level assertions."""
+    E, P = pkg.engine, pkg.params
+
+    def run(bases, waters, walls, Xp, Yp, obs, where, **kw):
+        u = P.uniforms_from_gui(P.merge_settings(None), Yp)
+        ens = E.Ensemble(len(bases), Xp, Yp, 0)
+        try:
+            for m, b, w, wl in zip(ens.members, bases, waters, walls):
+                m.upload(b, w, wl)
+                m.set_params(P.fill_struct(P.WxParams(), u), u["initial_T"])
+                assert b.view(np.uint32).tobytes() == m.read_rect(B_).view(np.uint32).tobytes(), where  # the planted bits are on the device
+            res = ens.assimilate(obs, **kw)
+            want_b, want_w, want_res = E.ens_assim_cells(bases, waters, walls, Xp, Yp, obs, **kw)
+            assert same_results(res, want_res), (where, res, want_res)
+            got_b, got_w = [m.read_rect(B_) for m in ens.members], [m.read_rect(W_) for m in ens.members]
+            for i in range(len(bases)):
+                for f, got, want in ((B_, got_b[i], want_b[i]), (W_, got_w[i], want_w[i])):
+                    assert same_bits(got, want), (where, f, "member", i, np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:4].tolist())
+            return got_b, got_w, res
+        finally:
+            ens.close()
+
+    return run
+
+
+@pytest.mark.parametrize("B", [5, 9])
+@pytest.mark.parametrize("case,placements", PLANTED, ids=PLANTED_IDS)
+def test_planted_cases_through_the_entry_test_and_the_member_walks_of_the_kernels(pkg, case, placements, B):
+    """The planted cases of the CPU test through k_ens_assim_obs and k_ens_assim on 17 x 7: non-finite and wall observations skipped,
+    a NaN and a wall in one member's state cell (the entry test ok[c] of the member walk -- with B = 9 once inside the load group of 8,
+    once in the remainder member behind it; B = 5 walks the remainder loop alone), V = 0 and the sign of zero, gain 0, the clamp edges,
+    the result beyond FLT_MAX that keeps its bits, localization at exactly dx == loc and dx == 2 loc, the wrap, duplicates."""
+    for kw in placements if B == 9 else placements[:1]:
+        case(device_run(pkg), B=B, **kw)
 
 
 _FAST_LEG = r"""

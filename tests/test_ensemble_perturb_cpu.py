@@ -226,8 +226,15 @@ def test_host_function_equals_the_definition(pkg, field, X, Y, B, kw):
     got = pkg.engine.ens_perturb_cells(fin, win, X, Y, field, AMP, mode=("add", "mul")[mode], rect=rect, lo=lo, hi=hi, **kw)
     want = reference(fin, win, X, Y, amplitude=AMP, mode=mode, rect=rect, lo=lo, hi=hi, **kw)
     check(got, want, (field, kw))
+    assert_what_a_perturbation_leaves_alone(got, fin, win, kw.get("members"), lo, hi)
+
+
+def assert_what_a_perturbation_leaves_alone(got, fin, win, members, lo, hi):
+    """The value-level assertions on `hand_built` members perturbed with AMP (tests/test_ensemble_perturb_gpu.py applies them to what
+    the device holds): ``got`` after, ``fin`` / ``win`` the fields and walls before, over the same cells."""
+    B = len(fin)
     for i in range(B):
-        sel = kw.get("members") is None or i in kw["members"]
+        sel = members is None or i in members
         changed = got[i].view(np.uint32) != fin[i].view(np.uint32)
         assert changed.any() == sel, i
         # never a wall cell, never channel 1 (amplitude 0), never a non-finite value; and what was finite stays finite
@@ -236,6 +243,54 @@ def test_host_function_equals_the_definition(pkg, field, X, Y, B, kw):
     if not np.isnan(lo[0]):
         ch = got[0][..., 0][(got[0].view(np.uint32) != fin[0].view(np.uint32))[..., 0]]
         assert ch.min() >= np.float32(lo[0]) and ch.max() <= np.float32(hi[0]) and (ch == np.float32(lo[0])).any() and (ch == np.float32(hi[0])).any()
+
+
+PX, PY = 57, 9
+# (field, keywords) of the planted runs: both modes, a lattice of 1 / 3 / 8 cells, wrap_x, both clamps, a rectangle, a sparse mask
+PLANTED_RUNS = [("BASE_CUR", dict(mode=0, scale=1)), ("WATER_CUR", dict(mode=1, scale=3, seed=2024)), ("BASE_CUR", dict(mode=0, scale=8, seed=5, wrap_x=True)),
+                ("WATER_CUR", dict(mode=0, scale=3, seed=3, lo=(-0.01, NAN, NAN, 279.0), hi=(0.02, NAN, 0.0, NAN))),
+                ("BASE_CUR", dict(mode=1, scale=2, seed=1, rect=(5, 2, 30, 7))), ("WATER_CUR", dict(mode=0, scale=4, seed=77, members=[0, 2]))]
+
+
+def planted_run(pkg, B, field, kw, perturb):
+    """One planted run: `hand_built` members (NaN, +-Inf, -0.0, subnormals, +-FLT_MAX -- whose product with 1 + a r overflows and is
+    refused -- sprinkled over ordinary values, walls that differ per member), ``perturb(fields, walls, field, keywords) -> fields
+    after``, the host function's bits, and the CPU test's value-level assertions on the result."""
+    f, w = hand_built(B, PX, PY)
+    kw = dict(kw)
+    rect, mode = kw.pop("rect", None), ("add", "mul")[kw.pop("mode")]
+    lo, hi = kw.pop("lo", (NAN,) * 4), kw.pop("hi", (NAN,) * 4)
+    if B == 17 and "members" in kw:
+        kw["members"] = [0, 3, 16]
+    cut = (lambda arrs: arrs) if rect is None else (lambda arrs: [np.ascontiguousarray(a[rect[1]:rect[1] + rect[3], rect[0]:rect[0] + rect[2]]) for a in arrs])
+    call = dict(mode=mode, rect=rect, lo=lo, hi=hi, **kw)
+    got = cut(perturb(f, w, field, call))
+    want = pkg.engine.ens_perturb_cells(cut(f), cut(w), PX, PY, field, AMP, **call)
+    for i in range(B):
+        assert same_bits(got[i], want[i]), (field, call, "member", i, np.argwhere(got[i].view(np.uint32) != want[i].view(np.uint32))[:4].tolist())
+    assert_what_a_perturbation_leaves_alone(got, cut(f), cut(w), kw.get("members"), lo, hi)
+    specials = [np.isin(a.view(np.uint32), SPECIALS.view(np.uint32)) for a in cut(f)]
+    assert all(s.any() for s in specials) and any((g.view(np.uint32) != a.view(np.uint32))[s].any() for g, a, s in zip(got, cut(f), specials))  # the finite ones move
+
+
+@pytest.mark.parametrize("B", [3, 17])
+def test_planted_special_values_through_the_host_function(pkg, B):
+    """(tests/test_ensemble_perturb_gpu.py runs the same through the kernel.)"""
+    for field, kw in PLANTED_RUNS:
+        planted_run(pkg, B, field, kw, lambda f, w, field, call: _pasted(pkg, f, w, field, call))
+
+
+def _pasted(pkg, f, w, field, call):
+    """The host function on the rectangle's cells, pasted back into whole grids."""
+    rect = call["rect"]
+    if rect is None:
+        return pkg.engine.ens_perturb_cells(f, w, PX, PY, field, AMP, **call)
+    x, y, rw, rh = rect
+    new = pkg.engine.ens_perturb_cells(cut(f, rect), cut(w, rect), PX, PY, field, AMP, **call)
+    out = [a.copy() for a in f]
+    for o, n in zip(out, new):
+        o[y:y + rh, x:x + rw] = n
+    return out
 
 
 def test_an_overflowing_result_is_refused_not_stored(pkg):

@@ -11,6 +11,8 @@ import pytest
 
 import impulse_scenes as I
 from test_ensemble_gpu import FIELDS, same_bits
+from test_ensemble_perturb_cpu import AMP as PLANTED_AMP
+from test_ensemble_perturb_cpu import PLANTED_RUNS, PX, PY, planted_run
 from test_ensemble_statistics_gpu import make_ensemble, member_specs
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +82,32 @@ def test_device_equals_host_function(pkg, B):
             assert same_bits(m.read_rect("WALL_CUR"), pre[i]["WALL_CUR"])
         ens.step(1)  # ... and the ensemble steps on
         ens.sync()
+    finally:
+        ens.close()
+
+
+@pytest.mark.parametrize("B", [3, 17])
+def test_planted_special_values_through_the_kernel(pkg, B):
+    """The hand-built members of the CPU test through k_ens_perturb (nothing is stepped; every run starts from a fresh upload, whose
+    bits the members show before the call): the device holds the host function's bits and what must be left alone is left alone --
+    wall cells, the channel of amplitude 0, non-finite values, unselected members, the FLT_MAX whose result would overflow."""
+    E, P = pkg.engine, pkg.params
+    u = P.uniforms_from_gui(P.merge_settings(None), PY)
+    ens = E.Ensemble(B, PX, PY, 0)
+
+    def on_the_device(f, w, field, call):
+        for m, a, wl in zip(ens.members, f, w):
+            m.upload(a, a, wl)
+            m.set_params(P.fill_struct(P.WxParams(), u), u["initial_T"])
+            assert m.read_rect(field).view(np.uint32).tobytes() == a.view(np.uint32).tobytes()
+        ens.perturb(field, PLANTED_AMP, **call)
+        other = "WATER_CUR" if field == "BASE_CUR" else "BASE_CUR"
+        assert all(m.read_rect(other).view(np.uint32).tobytes() == a.view(np.uint32).tobytes() for m, a in zip(ens.members, f))
+        return [m.read_rect(field) for m in ens.members]
+
+    try:
+        for field, kw in PLANTED_RUNS:
+            planted_run(pkg, B, field, kw, on_the_device)
     finally:
         ens.close()
 
