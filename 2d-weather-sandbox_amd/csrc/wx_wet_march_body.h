@@ -456,7 +456,11 @@
   }
   {
     const __attribute__((address_space(4))) VxTrack &vc = *(const __attribute__((address_space(4))) VxTrack *)(ka_c + offsetof(KArgs, vx));
-    vx_track_commit(VxTrack{vc.max_bits, vc.violation, vc.limit, vc.zone_l, vc.zone_r, vc.limit_in}, vx_seen, lane, strip);
+    // (lanes 2 .. 60 only, the ones whose post-boundary velocity feeds an advection that is used: the vorticity stage reads the curl of
+    // both neighbours, so lanes 61 and 62 hold values built from lane 63's missing right neighbour -- a lone cell of 1.12 cells / iteration in
+    // the second column of a strip was reported as 1.68 by the wave to its left, tests/test_vx_watch_gpu.py. Every column is an
+    // output lane, 4 .. 59, of the wave that owns it; masked here, behind the row loop, which keeps its one v_max per row step)
+    vx_track_commit(VxTrack{vc.max_bits, vc.violation, vc.limit, vc.zone_l, vc.zone_r, vc.limit_in}, lane >= 2 && lane <= 60 ? vx_seen : 0.0f, lane, strip);
   }
 #ifdef WX_WET_TIMING
   if (lane == 0) {

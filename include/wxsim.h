@@ -142,8 +142,13 @@ int wx_create_slab(int X_global, int Y, int x0, int X_owned, int halo, int n_dro
  * A |vx| that reaches the bound inside a period is REPORTED by the next blocking call (WX_E_STATE), never silent; so is a velocity of
  * 2 * halo - 8 cells / iteration and more anywhere in the slab (beyond that even the strips three halo widths from the edges read ghost columns). wx_slab_step /
  * wx_group_step do all of this themselves without a host round trip inside a period: the maxima travel with the exchange (one word per
- * slab, all-gathered) and size the period after the next; slab.py's host-driven exchange all-reduces them. Hosts that drive
- * wx_step_overlap / wx_halo_* themselves call the three functions once per period. */
+ * slab, all-gathered) and size the period after the next; slab.py's host-driven exchange all-reduces them. Which measurement sizes
+ * which period: the first period after an upload, and the one that starts at the first exchange, are sized by the maximum of the
+ * uploaded state (every slab scans its own, once); the period that starts at exchange e > 1 is sized by the larger of the two latest
+ * COMPLETED measurements -- the maxima rolled at exchanges e - 1 and e - 2 (at e = 2: e - 1 alone), each the largest |vx| of 0.5 and more
+ * any slab recorded between the exchange before it and itself, else 0. The measurement taken AT exchange e is still on its way to the
+ * hosts then and is used from e + 1 on; the older of the two keeps a flow that slowed down for one period its margin for one more.
+ * Hosts that drive wx_step_overlap / wx_halo_* themselves call the three functions once per period. */
 int wx_slab_vx_take(wx_sim *s, float *vmax);
 int wx_slab_set_vx_bound(wx_sim *s, float v_measured);
 int wx_slab_cone(const wx_sim *s);
