@@ -15,6 +15,7 @@
 // to the same buffer again (ENS_BUFS chunks later).
 
 struct EnsStatState; // wx_ens_stat.h
+struct EnsPriorState; // wx_ens_inflate.h
 
 struct wx_ensemble {
   std::vector<wx_sim *> member;
@@ -31,11 +32,13 @@ struct wx_ensemble {
   int64_t iters_batched = 0, iters_solo = 0, march_launches = 0; // wx_ensemble_stats
   int64_t iters_particles = 0, particle_launches = 0;            // wx_ensemble_particle_stats
   EnsStatState *stat = nullptr; // wx_ensemble_statistics: its device table, output planes and pinned copies (made by the first call)
+  EnsPriorState *prior = nullptr; // wx_ensemble_prior_save: one device-side snapshot per field (made by the first call)
   bool broken = false; // a step failed half-way: members' host state ran ahead of what was launched (wx_ensemble_step refuses from then on)
   std::string err;
 };
 
 static void ens_stat_release(wx_ensemble *e); // wx_ens_stat.h
+static void ens_prior_release(wx_ensemble *e); // wx_ens_inflate.h
 
 static int efail(wx_ensemble *e, int code, const char *fmt, ...)
 {
@@ -80,6 +83,7 @@ void wx_ensemble_destroy(wx_ensemble *e)
     hipFree(e->dev[b]);
   }
   ens_stat_release(e);
+  ens_prior_release(e);
   if (e->stream) hipStreamDestroy(e->stream);
   (void)hipSetDevice(prev);
   delete e;

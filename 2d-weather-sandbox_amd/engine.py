@@ -48,6 +48,7 @@ EXPORTS = [
     "wx_ensemble_quantiles", "wx_ens_quant_cells", "wx_ens_quant_staged_members",
     "wx_ensemble_scores", "wx_ens_score_cells", "wx_ens_score_max_members",
     "wx_ensemble_assimilate", "wx_ens_assim_cells",
+    "wx_ensemble_prior_save", "wx_ensemble_prior_drop", "wx_ensemble_inflate", "wx_ens_inflate_cells",
 ]
 
 
@@ -352,6 +353,57 @@ def ens_assim_cells(bases, waters, walls, X: int, Y: int, observations, *, loc=(
     return nb, nw, _obs_results(res, len(observations))
 
 
+INFLATE_MODES = {"const": 0, "rtps": 1, "rtpp": 2}
+
+
+class WxEnsInflate(C.Structure):
+    """``wx_ens_inflate`` of include/wxsim.h, member for member."""
+    _fields_ = [
+        ("field", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("mode", C.c_int32),
+        ("coef", C.c_float * 4), ("lambda_lo", C.c_float), ("lambda_hi", C.c_float), ("lo", C.c_float * 4), ("hi", C.c_float * 4),
+        ("lambda_out", C.c_void_p),
+    ]
+
+
+def _inflate_struct(field, coef, mode, rect, lambda_bounds, lo, hi, lambda_out=None) -> WxEnsInflate:
+    p = WxEnsInflate()
+    p.field = int(FIELD_IDS.get(field, field))
+    p.x, p.y, p.w, p.h = [int(v) for v in rect]
+    p.mode = int(INFLATE_MODES.get(mode, mode))
+    p.coef[:] = _four(coef, 1.0 if p.mode == 0 else 0.0)
+    nan = float("nan")
+    lb = (None, None) if lambda_bounds is None else lambda_bounds
+    p.lambda_lo, p.lambda_hi = [nan if v is None else float(v) for v in lb]
+    p.lo[:], p.hi[:] = _four(lo, nan), _four(hi, nan)
+    p.lambda_out = None if lambda_out is None else lambda_out.ctypes.data
+    return p
+
+
+def ens_inflate_cells(fields, walls, field, coef, *, mode="const", priors=None, members=None, lambda_bounds=None, lo=None, hi=None, want_lambda=False):
+    """wx_ens_inflate_cells: covariance inflation (``mode`` "const": ``coef`` = lambda per channel, 1 = untouched) or relaxation to the
+    prior ("rtps", "rtpp": ``coef`` = alpha, 0 = untouched) over the members, on the CPU, literally as include/wxsim.h defines it.
+    ``fields[i]`` / ``walls[i]`` / ``priors[i]``: member i's cells, float32 (..., 4), int8 (..., 4) and float32 (..., 4) of one common
+    shape; an unselected member's entries may be None, and so may ``priors`` in mode "const". Returns new arrays (the arguments are not
+    changed), or with ``want_lambda`` (new arrays, the map of the lambda applied: NaN where a channel was left alone)."""
+    n = len(fields)
+    mask = _member_mask(n, members)
+    out = [None if a is None else np.array(a, np.float32, order="C") for a in fields]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    pr = [None] * n if priors is None else [None if a is None else np.ascontiguousarray(a, np.float32) for a in priors]
+    have = [a for a in out if a is not None]
+    if n < 1 or len(wl) != n or len(pr) != n or not have or any(a is not None and (a.shape != have[0].shape or a.shape[-1:] != (4,)) for a in out + wl + pr):
+        raise ValueError("one (..., 4) field, wall and (in the relaxation modes) prior array per member, all of one shape")
+    shape = have[0].shape[:-1]
+    lam = np.zeros(tuple(shape) + (4,), np.float32) if want_lambda else None
+    ptrs = lambda arrs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
+    p = _inflate_struct(field, coef, mode, (0, 0, 1, 1), lambda_bounds, lo, hi, lam)
+    rc = lib().wx_ens_inflate_cells(C.byref(p), n, int(np.prod(shape, dtype=np.int64)), ptrs(out), ptrs(wl), None if priors is None else ptrs(pr),
+                                    None if mask is None else mask.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_ens_inflate_cells: bad descriptor, a missing array of a selected member, or fewer than two members selected")
+    return (out, lam) if want_lambda else out
+
+
 ENS_QUANT_MAX = 8
 QUANT_INTERP = {"linear": 0, "lower": 1, "higher": 2}
 
@@ -640,6 +692,10 @@ def lib() -> C.CDLL:
     L.wx_ens_score_max_members.restype = i32
     L.wx_ensemble_assimilate.argtypes = [vp, C.POINTER(WxEnsAssim), i32, vp, vp, vp]
     L.wx_ens_assim_cells.argtypes = [C.POINTER(WxEnsAssim), i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.wx_ensemble_prior_save.argtypes = [vp, i32, i32, i32, i32, i32, vp]
+    L.wx_ensemble_prior_drop.argtypes = [vp, i32]
+    L.wx_ensemble_inflate.argtypes = [vp, C.POINTER(WxEnsInflate), vp]
+    L.wx_ens_inflate_cells.argtypes = [C.POINTER(WxEnsInflate), i32, C.c_size_t, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1298,6 +1354,34 @@ class Ensemble:
         mask = _member_mask(self.n, members)
         self._chk(lib().wx_ensemble_assimilate(self._e, C.byref(a), len(observations), obs, res, None if mask is None else mask.ctypes.data))
         return _obs_results(res, len(observations))
+
+    def save_prior(self, field: str, rect=None, members=None):
+        """wx_ensemble_prior_save: a device-side snapshot of ``rect`` = (x, y, w, h) (None: the whole grid) of ``field`` (BASE_CUR or
+        WATER_CUR) of the selected members -- what ``inflate`` in the modes "rtps" and "rtpp" relaxes to. One slot per field: the next
+        save replaces it, ``drop_prior`` frees it (n x w x h x 16 bytes of device memory). One launch; blocks like ``statistics``."""
+        x, y, w, h = (0, 0, self.X, self.Y) if rect is None else rect
+        mask = _member_mask(self.n, members)
+        self._chk(lib().wx_ensemble_prior_save(self._e, int(FIELD_IDS.get(field, field)), int(x), int(y), int(w), int(h), None if mask is None else mask.ctypes.data))
+
+    def drop_prior(self, field: str):
+        """wx_ensemble_prior_drop: frees the snapshot of ``field`` (nothing happens if there is none)."""
+        self._chk(lib().wx_ensemble_prior_drop(self._e, int(FIELD_IDS.get(field, field))))
+
+    def inflate(self, field: str, coef, *, mode="const", rect=None, members=None, lambda_bounds=None, lo=None, hi=None, want_lambda=False):
+        """wx_ensemble_inflate: the spread of the selected members (at least two) of ``field`` (BASE_CUR or WATER_CUR) inside ``rect`` =
+        (x, y, w, h) (None: the whole grid) put back, in one launch. ``mode`` "const": the deviations from the ensemble mean times
+        ``coef`` (lambda, one value or one per channel; 1: channel untouched). "rtps": relaxation to prior spread, lambda = 1 + alpha
+        (sb - sa) / sa per cell with ``coef`` = alpha (0: untouched) and ``lambda_bounds`` = (lowest, highest) lambda (None: none).
+        "rtpp": relaxation to prior perturbations, (1 - alpha) x' + alpha xb'. The two relaxation modes read the snapshot that
+        ``save_prior`` took of the same field and members. ``lo`` / ``hi``: clamps (None: none). Cells that are a wall or hold a
+        non-finite value in any selected member are left alone. With ``want_lambda`` ("const", "rtps") the (h, w, 4) map of the lambda
+        applied comes back, NaN where a channel was left alone. Blocks like ``perturb``."""
+        rect = (0, 0, self.X, self.Y) if rect is None else rect
+        lam = np.zeros((max(int(rect[3]), 0), max(int(rect[2]), 0), 4), np.float32) if want_lambda else None
+        p = _inflate_struct(field, coef, mode, rect, lambda_bounds, lo, hi, lam)
+        mask = _member_mask(self.n, members)
+        self._chk(lib().wx_ensemble_inflate(self._e, C.byref(p), None if mask is None else mask.ctypes.data))
+        return lam
 
     def close(self):
         if getattr(self, "_e", None):

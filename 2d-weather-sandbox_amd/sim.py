@@ -345,6 +345,46 @@ class WeatherEnsemble:
             wrap_x = bool(self.members[0].gui.get("wrapHorizontally", True))
         return self._e.assimilate(observations, loc=loc, rect=rect, members=members, wrap_x=wrap_x, **kw)
 
+    def save_prior(self, field: str, rect=None, members=None):
+        """``engine.Ensemble.save_prior``: the device-side snapshot of one field that ``inflate`` relaxes to in the modes "rtps" / "rtpp"."""
+        self._e.save_prior(field, rect, members)
+
+    def drop_prior(self, field: str):
+        """``engine.Ensemble.drop_prior``: frees that field's snapshot."""
+        self._e.drop_prior(field)
+
+    def inflate(self, field: str, coef, **kw):
+        """``engine.Ensemble.inflate``: covariance inflation about the ensemble mean (mode "const") or relaxation to the saved prior
+        ("rtps", "rtpp") of one field of the selected members (mode, rect, members, lambda_bounds, lo, hi, want_lambda)."""
+        return self._e.inflate(field, coef, **kw)
+
+    def analysis(self, observations, *, relax=None, inflate=None, **assimilate_kw) -> list:
+        """One analysis step of a cycling filter: ``save_prior`` of the state fields with a non-zero gain (only with ``relax``), then
+        ``assimilate(observations, **assimilate_kw)``, then the inflation -- ``relax`` = ("rtps", alpha) or ("rtpp", alpha): relaxation
+        to the prior just saved; ``inflate`` = lambda: constant inflation about the analysis mean (after the relaxation if both are
+        given). alpha / lambda: one value or one per channel; they act on the channels the analysis updates (gain != 0), inside its
+        ``rect`` and on its ``members``. The clamps of the analysis (lo_* / hi_*) hold for the inflation too. Returns the
+        per-observation results of ``assimilate``."""
+        from .engine import _four
+        gains = {"BASE_CUR": _four(assimilate_kw.get("gain_base", (0, 0, 0, 1)), 0.0), "WATER_CUR": _four(assimilate_kw.get("gain_water", 0.0), 0.0)}
+        fields = [f for f, g in gains.items() if any(v != 0.0 for v in g)]
+        rect, members = assimilate_kw.get("rect"), assimilate_kw.get("members")
+        if relax is not None:
+            mode, alpha = relax
+            if mode not in ("rtps", "rtpp"):
+                raise ValueError('relax: ("rtps", alpha) or ("rtpp", alpha)')
+            for f in fields:
+                self.save_prior(f, rect, members)
+        res = self.assimilate(observations, **assimilate_kw)
+        for f in fields:
+            suffix = "base" if f == "BASE_CUR" else "water"
+            clamp = dict(lo=assimilate_kw.get("lo_" + suffix), hi=assimilate_kw.get("hi_" + suffix))
+            if relax is not None:
+                self.inflate(f, [a if g != 0.0 else 0.0 for a, g in zip(_four(alpha, 0.0), gains[f])], mode=mode, rect=rect, members=members, **clamp)
+            if inflate is not None:
+                self.inflate(f, [l if g != 0.0 else 1.0 for l, g in zip(_four(inflate, 1.0), gains[f])], mode="const", rect=rect, members=members, **clamp)
+        return res
+
     def __len__(self):
         return len(self.members)
 

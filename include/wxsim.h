@@ -948,6 +948,80 @@ int wx_ens_score_cells(int n_members, size_t n_cells, const float *const *field,
                        const float *truth_field, const int8_t *truth_wall, const uint8_t *member_mask, wx_ens_score *out);
 int wx_ens_score_max_members(void);  /* == wx_ens_quant_staged_members() */
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_INFLATE) Covariance inflation and relaxation to the prior, on the device: the step of a cycling filter
+ * that puts back the spread wx_ensemble_assimilate removes. A square-root filter with localization under-estimates its analysis
+ * variance; without inflation the spread collapses, the members stop listening to observations and the rank histograms of
+ * wx_ensemble_scores go U-shaped. (wx_ensemble_perturb in mode 1 is NOT inflation: v * (1 + a r) scales the whole value by a noise
+ * field, moves the mean and knows nothing of the spread the analysis took away.) Three schemes, one launch, no host array and no
+ * wx_upload: WX_INFLATE_CONST, multiplicative inflation about the ensemble mean; WX_INFLATE_RTPS, relaxation to prior spread (Whitaker
+ * and Hamill 2012); WX_INFLATE_RTPP, relaxation to prior perturbations (Zhang et al. 2004). The two relaxation schemes read the prior
+ * from a device-side snapshot that the host takes with wx_ensemble_prior_save before the analysis.
+ *
+ * THE SNAPSHOT. wx_ensemble_prior_save copies the rectangle of `field` of every selected member into a buffer the ensemble owns, laid
+ * out [k][h][w] texels of 4 floats (k: position among the selected members, ascending member index): n * w * h * 16 bytes -- 10 MB for
+ * 64 members of 100 x 100, 96 MB for 8 of 2500 x 300. One slot per field: the next save of that field replaces it, wx_ensemble_prior_drop
+ * or wx_ensemble_destroy frees it. The snapshot remembers its field, rectangle and selection. A later wx_ensemble_step does not
+ * invalidate it: the prior is whatever the host saved. One launch (kernel name "ensemble_prior_save", one lane per member-cell: 16 B
+ * read, 16 B written). Refusals, ordering, blocking and report consumption as for wx_ensemble_statistics (WX_E_INVALID: e NULL, a field
+ * other than WX_FIELD_BASE_CUR / WX_FIELD_WATER_CUR, nobody selected; WX_E_RANGE: the rectangle; WX_E_STATE: a selected member never
+ * uploaded; WX_E_NOMEM: the buffer -- the old snapshot of that field is gone then); it changes nothing a host can observe.
+ *
+ * THE PER-CELL FUNCTION (the kernel, wx_ens_inflate_cells and the tests all evaluate this definition). All arithmetic is double, every
+ * operation rounded separately (no fused multiply-add: contraction is off inside every function that rounds, and every product that
+ * feeds a sum is a value of its own in every build, so libwxsim.so, libwxsim_fast.so, the device and the host give the same bits);
+ * sqrt is the correctly rounded double square root. "In member order": the n selected members k = 0 .. n-1 by ascending member index.
+ * x_k is member k's value of channel c of the cell, p_k its snapshot value.
+ *   Neutral. A channel whose coef[c] is neutral -- CONST: 1, RTPS / RTPP: 0 -- is untouched.
+ *   Eligibility. Otherwise the channel is updated only if in every selected member the cell is an air cell (channel 1 of its
+ *   WX_FIELD_WALL_CUR texel != 0: wx_diag's test) and x_k is finite, and in RTPS / RTPP every p_k is finite too; else it is untouched in
+ *   all members.
+ *   Mean. S = sum (double)x_k in member order, m = S / n, d_k = (double)x_k - m.
+ *   CONST. lambda = (double)coef[c].
+ *   RTPS. Qa = sum d_k*d_k in member order; Sb = sum (double)p_k, mb = Sb / n, b_k = (double)p_k - mb, Qb = sum b_k*b_k, both in member
+ *   order; sa = sqrt(Qa / (n - 1)), sb = sqrt(Qb / (n - 1)). If sa == 0 the channel is untouched. Otherwise
+ *   lambda = 1 + (double)coef[c] * ((sb - sa) / sa) -- a difference, a quotient, a rounded product, a sum --, then the bounds: if
+ *   lambda_lo is not NaN and lambda < lambda_lo, lambda = lambda_lo; then if lambda_hi is not NaN and lambda > lambda_hi, lambda = lambda_hi.
+ *   CONST and RTPS, common tail. If lambda is not finite or lambda == 1 the channel is untouched (so a -0.0 never becomes +0.0 by a
+ *   factor of one). Otherwise for every member o_k = (float)(m + lambda*d_k).
+ *   RTPP. a = (double)coef[c], g = 1 - a, and for every member o_k = (float)(m + (g*d_k + a*b_k)) with b_k as above: two rounded
+ *   products and two rounded sums. (a == 1: o_k - m is b_k, the prior's perturbation about the analysis mean.)
+ *   Clamp. Then wx_ens_perturb's clamp (lo first, then hi, NaN = none). If o_k is not finite that member's channel keeps its bits.
+ *   lambda_out (CONST and RTPS) holds (float)lambda where the channel was updated -- where the common tail was reached and passed --
+ *   and NaN elsewhere.
+ * Cells never interact, and neither do channels: any split of a rectangle gives the same bits.
+ *
+ * wx_ensemble_inflate. Answered before the device is touched -- WX_E_INVALID: e or p NULL; a field other than WX_FIELD_BASE_CUR /
+ * WX_FIELD_WATER_CUR; an unknown mode; a coef that is not finite or is negative; an RTPP coef > 1; lambda_out given with RTPP; fewer than
+ * two selected members. WX_E_RANGE: the rectangle does not lie inside the grid (no wrap). WX_E_STATE: a selected member was never
+ * uploaded; in RTPS / RTPP, no snapshot of that field, a selection that differs from the snapshot's, a rectangle not inside the
+ * snapshot's (the message says which). CONST never looks at a snapshot. Bookkeeping, ordering, blocking and report consumption exactly
+ * as for wx_ensemble_perturb: a lazy WX_FIELD_BASE_DISP is assembled whole first, a pending WX_FIELD_WATER_0 is made first, velocities
+ * written are looked at by the next |vx| scan, written water ends the water-free state. The snapshot is read, never written.
+ * wx_profile on member 0 times the launch (kernel name "ensemble_inflate"); traffic per member-cell: DESIGN.md section 4.
+ * wx_ens_inflate_cells (host only, pure): the same function over n_cells cells the caller holds -- member i's cells at field[i]
+ * (4 floats per cell, changed in place), wall[i] (4 bytes per cell) and prior[i] (4 floats per cell; the table or its entries may be
+ * NULL in CONST). The rectangle of the descriptor is not looked at; lambda_out, if given, holds n_cells * 4 floats. WX_E_INVALID as
+ * above, and for n_members < 1, a NULL table, a NULL entry of a selected member. */
+#define WX_HAVE_ENSEMBLE_INFLATE 1
+#define WX_INFLATE_CONST 0
+#define WX_INFLATE_RTPS  1
+#define WX_INFLATE_RTPP  2
+typedef struct wx_ens_inflate {
+  int32_t field;            /* WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR */
+  int32_t x, y, w, h;       /* cells that may change; no wrap (WX_E_RANGE) */
+  int32_t mode;             /* WX_INFLATE_* */
+  float   coef[4];          /* per channel. CONST: lambda (neutral 1). RTPS / RTPP: alpha (neutral 0). Neutral: bits untouched */
+  float   lambda_lo, lambda_hi; /* RTPS only: bounds of the derived lambda, NaN: none */
+  float   lo[4], hi[4];     /* clamp of the result as wx_ens_perturb, NaN: none */
+  float  *lambda_out;       /* optional w*h*4 map (CONST, RTPS): the lambda applied, NaN where the channel was left alone */
+} wx_ens_inflate;
+int wx_ensemble_prior_save(wx_ensemble *e, int field, int x, int y, int w, int h, const uint8_t *member_mask);
+int wx_ensemble_prior_drop(wx_ensemble *e, int field);   /* frees that field's snapshot; WX_OK if there is none */
+int wx_ensemble_inflate(wx_ensemble *e, const wx_ens_inflate *p, const uint8_t *member_mask);
+int wx_ens_inflate_cells(const wx_ens_inflate *p, int n_members, size_t n_cells, float *const *field,
+                         const int8_t *const *wall, const float *const *prior /* NULL entries allowed in CONST */,
+                         const uint8_t *member_mask);   /* host only, pure; lambda_out over n_cells */
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

@@ -45,6 +45,14 @@ read_rect triples (base, water, wall), wx_ens_assim_cells on the host, B wx_uplo
 the feedback textures, the lightning state): the record says so. The shape's "assimilate" key also holds the two kernels' own times
 (wx_profile on member 0) next to the bytes the update kernel moves at most: 3 x 20 B read + 16 B written per member-cell and observation
 whose weight there is not 0.
+--inflate FIELD (BASE_CUR or WATER_CUR; --mode ensemble): what ONE wx_ensemble_inflate call over the whole grid costs per mode (CONST
+lambda 1.1; RTPS alpha 0.5; RTPP alpha 0.5; all four channels; host to host: the call blocks), and one wx_ensemble_prior_save, against
+the only host route that exists -- B read_rect pairs (field, wall) and wx_ens_inflate_cells on the host; THE WAY BACK WOULD BE B
+wx_upload CALLS, which lose the stepped state (light, curl, the feedback textures, the lightning state) and are not timed: the record
+says so. The shape's "inflate" key also holds the kernels' own times (wx_profile on member 0) against the bytes per member-cell the
+walks request when every cell is updated -- CONST 52, RTPS 100, RTPP 84, the snapshot 32 -- and against what crosses the memory interface
+if every re-read of a walk is served on the chip -- 36, 52, 52 --, both at --peak-gbs. Without
+--shapes: 100x100x64 and 2500x300x8.
 --share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
 import argparse
 import json
@@ -70,13 +78,14 @@ def parse():
     ap.add_argument("--quantiles", default="", metavar="FIELD", help="time one quantile call over the whole grid against B read_rect calls + np.sort (BASE_CUR or WATER_CUR)")
     ap.add_argument("--scores", default="", metavar="FIELD", help="time one score call (B members against member B of B + 1) against statistics + quantiles + read_rect + numpy (BASE_CUR or WATER_CUR)")
     ap.add_argument("--assimilate", default="", metavar="FIELD", help="time one assimilation call of --observations point observations against N calls of one and against read_rect + host function + uploads (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--inflate", default="", metavar="FIELD", help="time one inflation call per mode over the whole grid against read_rect + the host function (BASE_CUR or WATER_CUR)")
     ap.add_argument("--observations", type=int, default=40, help="observations per call with --assimilate (1 .. 256)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = "100x100x64,2500x300x8" if a.scores else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
+        a.shapes = "100x100x64,2500x300x8" if a.scores or a.inflate else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
     return a
 
 
@@ -497,8 +506,80 @@ def time_assimilate(a, pkg, ens, X, Y, B):
             "update_kernel_fraction_of_peak_at_most": round(bytes_most / (upd_us * 1e-6) / 1e9 / a.peak_gbs, 4) if upd_us > 0 else None}
 
 
+INFLATE_BYTES = {"const": 52, "rtps": 100, "rtpp": 84}  # per member-cell, every cell updated: what the walks of csrc/wx_ens_inflate.h request
+INFLATE_BYTES_ONCE = {"const": 36, "rtps": 52, "rtpp": 52}  # ... and what crosses the memory interface if every re-read is served on the chip
+PRIOR_SAVE_BYTES = 32
+
+
+def time_inflate(a, pkg, ens, X, Y, B):
+    import statistics
+    E = pkg.engine
+    field = a.inflate
+    ens.step(a.frame)
+    ens.sync()
+    ens.save_prior(field)
+    ens.step(a.frame)
+    ens.sync()
+    calls = {"const": dict(coef=1.1), "rtps": dict(coef=0.5), "rtpp": dict(coef=0.5)}
+    clamp = dict(lo=0.0) if field == "WATER_CUR" else {}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        ens.inflate(field, 1.0 + 1e-6, mode="const", **clamp)
+    ms = lambda t: round(1e3 * t, 3)  # noqa: E731
+    rec = {"field": field, "members": B, "calls": a.repeats, "modes": {}}
+    for mode, kw in calls.items():
+        ens[0].profile(True)
+        t_call = []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            ens.inflate(field, kw["coef"], mode=mode, **clamp)
+            t_call.append(time.perf_counter() - t0)
+        prof = ens[0].profile_read()
+        ens[0].profile(False)
+        k_ms, k_n = prof.get("ensemble_inflate", (0.0, 0))
+        k_us = 1e3 * k_ms / max(k_n, 1)
+        nbytes = INFLATE_BYTES[mode] * X * Y * B
+        gbs = nbytes / (k_us * 1e-6) / 1e9 if k_us > 0 else None
+        once = INFLATE_BYTES_ONCE[mode] * X * Y * B / (k_us * 1e-6) / 1e9 if k_us > 0 else None
+        rec["modes"][mode] = {"coef": kw["coef"], "one_call_ms": {"slowest": ms(max(t_call)), "median": ms(statistics.median(t_call))},
+                              "kernel_us": round(k_us, 2), "kernel_launches_timed": k_n, "bytes_per_member_cell_at_most": INFLATE_BYTES[mode],
+                              "kernel_gb_per_s_at_most": round(gbs, 1) if gbs else None, "kernel_fraction_of_peak_at_most": round(gbs / a.peak_gbs, 4) if gbs else None,
+                              "bytes_per_member_cell_read_once": INFLATE_BYTES_ONCE[mode], "kernel_gb_per_s_read_once": round(once, 1) if once else None,
+                              "kernel_fraction_of_peak_read_once": round(once / a.peak_gbs, 4) if once else None}
+    ens[0].profile(True)
+    t_save = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        ens.save_prior(field)
+        t_save.append(time.perf_counter() - t0)
+    prof = ens[0].profile_read()
+    ens[0].profile(False)
+    s_ms, s_n = prof.get("ensemble_prior_save", (0.0, 0))
+    s_us = 1e3 * s_ms / max(s_n, 1)
+    gbs = PRIOR_SAVE_BYTES * X * Y * B / (s_us * 1e-6) / 1e9 if s_us > 0 else None
+    rec["prior_save"] = {"one_call_ms": {"slowest": ms(max(t_save)), "median": ms(statistics.median(t_save))}, "kernel_us": round(s_us, 2), "kernel_launches_timed": s_n,
+                         "snapshot_bytes": 16 * X * Y * B, "kernel_gb_per_s": round(gbs, 1) if gbs else None,
+                         "kernel_fraction_of_peak": round(gbs / a.peak_gbs, 4) if gbs else None}
+    # the host route: B read_rect pairs + the host function (RTPS; the prior read once more, as a host would have kept it); no way back is timed
+    prior = [h.read_rect(field) for h in ens.members]
+    t_host, t_read = [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        fields, walls = [h.read_rect(field) for h in ens.members], [h.read_rect("WALL_CUR") for h in ens.members]
+        t1 = time.perf_counter()
+        E.ens_inflate_cells(fields, walls, field, 0.5, mode="rtps", priors=prior, **clamp)
+        t_read.append(t1 - t0)
+        t_host.append(time.perf_counter() - t0)
+    rec["read_host_route_rtps_ms"] = {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))}
+    rec["speedup_slowest_over_host_route_rtps"] = round(max(t_host) / float(rec["modes"]["rtps"]["one_call_ms"]["slowest"]) * 1e3, 2)
+    rec["host_route_way_back"] = "not timed: B wx_upload calls, which reset light, curl, the feedback textures and the lightning state"
+    return rec
+
+
 def main():
     a = parse()
+    if a.inflate and (a.mode != "ensemble" or a.inflate not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--inflate BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.assimilate and (a.mode != "ensemble" or a.assimilate not in ("BASE_CUR", "WATER_CUR") or not 1 <= a.observations <= 256):
         sys.exit("--assimilate BASE_CUR | WATER_CUR needs --mode ensemble and --observations 1 .. 256")
     if a.spawn and a.mode != "ensemble":
@@ -560,6 +641,10 @@ def main():
             continue
         if a.quantiles:
             out["shapes"][spec] = {"members": B, "quantiles": time_quantiles(a, pkg, ens, X, Y, B)}
+            close()
+            continue
+        if a.inflate:
+            out["shapes"][spec] = {"members": B, "inflate": time_inflate(a, pkg, ens, X, Y, B)}
             close()
             continue
         if a.assimilate:
