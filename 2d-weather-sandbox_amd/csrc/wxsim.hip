@@ -60,6 +60,8 @@ enum KernelId {
   K_ENS_SCORE,  // the members scored against a truth handle: exact domain sums, rank histograms (wx_ens_score.h)
   K_ENS_PRIOR_SAVE, // the snapshot of the members that the relaxation modes of wx_ensemble_inflate read (wx_ens_inflate.h)
   K_ENS_INFLATE, // covariance inflation / relaxation to the prior over the members of an ensemble (wx_ens_inflate.h)
+  K_ENS_COV_PRED, // covariance maps: the predictors' chains, the pre-pass (wx_ens_cov.h)
+  K_ENS_COV,    // covariance, correlation and sensitivity maps over the members of an ensemble (wx_ens_cov.h)
   K_ENS_ASSIM_OBS, // point observations assimilated into the members: the observation-space pre-pass (wx_ens_assim.h)
   K_ENS_ASSIM,  // the state update of one field (wx_ens_assim.h)
   K_COUNT
@@ -67,7 +69,8 @@ enum KernelId {
 const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "boundary", "advection", "pressure", "lighting",
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
                                            "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb",
-                                           "ensemble_quantiles", "ensemble_scores", "ensemble_prior_save", "ensemble_inflate", "ensemble_assimilate_obs", "ensemble_assimilate"};
+                                           "ensemble_quantiles", "ensemble_scores", "ensemble_prior_save", "ensemble_inflate", "ensemble_covariance_pred", "ensemble_covariance",
+                                           "ensemble_assimilate_obs", "ensemble_assimilate"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -2954,3 +2957,4 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 #include "wx_ens_score.h" // (likewise)
 #include "wx_ens_assim.h" // (likewise)
 #include "wx_ens_inflate.h" // (likewise)
+#include "wx_ens_cov.h" // (likewise)

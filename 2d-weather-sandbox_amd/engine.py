@@ -49,6 +49,7 @@ EXPORTS = [
     "wx_ensemble_scores", "wx_ens_score_cells", "wx_ens_score_max_members",
     "wx_ensemble_assimilate", "wx_ens_assim_cells",
     "wx_ensemble_prior_save", "wx_ensemble_prior_drop", "wx_ensemble_inflate", "wx_ens_inflate_cells",
+    "wx_ensemble_covariance", "wx_ens_cov_cells",
 ]
 
 
@@ -404,6 +405,98 @@ def ens_inflate_cells(fields, walls, field, coef, *, mode="const", priors=None, 
     return (out, lam) if want_lambda else out
 
 
+ENS_COV_MAX = 8
+COV_SOURCES = {"current": 0, "prior": 1}
+COV_PLANES = ("cov", "corr", "slope", "variance")
+
+
+class WxEnsCovPred(C.Structure):
+    """``wx_ens_cov_pred`` of include/wxsim.h, member for member: one scalar predictor."""
+    _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("channel", C.c_int32), ("pad", C.c_int32),
+                ("values", C.c_void_p)]
+
+
+class WxEnsCovResult(C.Structure):
+    """``wx_ens_cov_result`` of include/wxsim.h: what the call says about one predictor."""
+    _fields_ = [("valid", C.c_int32), ("pad", C.c_int32), ("mean", C.c_double), ("variance", C.c_double)]
+
+
+class WxEnsCov(C.Structure):
+    """``wx_ens_cov`` of include/wxsim.h, member for member: what is asked for and the caller-owned output planes (NULL = not wanted)."""
+    _fields_ = [
+        ("field", C.c_int32), ("source", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("n_pred", C.c_int32), ("pad", C.c_int32),
+        ("cov", C.c_void_p), ("corr", C.c_void_p), ("slope", C.c_void_p), ("variance", C.c_void_p),
+    ]
+
+
+def _cov_predictors(predictors, n_members: int):
+    """``(field, x, y, channel)`` tuples (a point of the members' current state; field: a name) or sequences / arrays of one number per
+    member, as an array of wx_ens_cov_pred. Returns (the array, the float64 arrays it points into)."""
+    preds = (WxEnsCovPred * max(len(predictors), 1))()
+    keep = []
+    for j, p in enumerate(predictors):
+        if isinstance(p, (tuple, list)) and len(p) == 4 and isinstance(p[0], str):
+            preds[j].kind = 0
+            preds[j].field, preds[j].x, preds[j].y, preds[j].channel = int(FIELD_IDS.get(p[0], -1)), int(p[1]), int(p[2]), int(p[3])
+        else:
+            v = np.ascontiguousarray(p, np.float64).reshape(-1)
+            if v.size != n_members:
+                raise ValueError(f"predictor {j}: {v.size} numbers for {n_members} members (one per member, by member index)")
+            keep.append(v)
+            preds[j].kind, preds[j].values = 1, v.ctypes.data
+    return preds, keep
+
+
+def _cov_struct(field, source, rect, n_pred: int, want):
+    for name in want:
+        if name not in COV_PLANES:
+            raise ValueError(f"want: {name!r} is none of {COV_PLANES}")
+    c = WxEnsCov()
+    c.field, c.source = int(FIELD_IDS.get(field, field)), int(COV_SOURCES.get(source, source))
+    c.x, c.y, c.w, c.h = [int(v) for v in rect]
+    c.n_pred = int(n_pred)
+    h, w, k = max(c.h, 0), max(c.w, 0), max(min(c.n_pred, ENS_COV_MAX), 0)
+    planes = {name: np.zeros(((h, w, 4) if name == "variance" else (k, h, w, 4)), np.float32) for name in COV_PLANES if name in want}
+    for name, a in planes.items():
+        setattr(c, name, a.ctypes.data)
+    return c, planes
+
+
+def _cov_results(res, n: int) -> list:
+    return [{"valid": bool(r.valid), "mean": r.mean, "variance": r.variance} for r in res[:n]]
+
+
+def ens_cov_cells(bases, waters, walls, X: int, Y: int, field, predictors, *, source="current", rect=None, members=None, priors=None,
+                  want=COV_PLANES) -> dict:
+    """wx_ens_cov_cells: the covariance, correlation and sensitivity maps of include/wxsim.h on the CPU, literally as defined.
+    ``bases[i]`` / ``waters[i]`` / ``walls[i]``: member i's WHOLE grid, float32 (Y, X, 4) and int8 (Y, X, 4); an unselected member's
+    entries may be None, and so may a whole list that neither the state nor a point predictor needs. ``priors[i]``: the (h, w, 4) cells
+    of ``rect`` of member i's snapshot (``source`` "prior" only). ``predictors``: ``(field name, x, y, channel)`` tuples or one number
+    per member. Returns the planes named in ``want`` -- cov, corr, slope: (n_pred, h, w, 4); variance: (h, w, 4) -- and ``results``."""
+    rect = (0, 0, int(X), int(Y)) if rect is None else tuple(int(v) for v in rect)
+    n = len(walls)
+    mask = _member_mask(n, members)
+    shape, pshape = (int(Y), int(X), 4), (max(rect[3], 0), max(rect[2], 0), 4)
+    conv = lambda arrs, t: None if arrs is None else [None if a is None else np.ascontiguousarray(a, t) for a in arrs]  # noqa: E731
+    nb, nw, wl, pr = conv(bases, np.float32), conv(waters, np.float32), conv(walls, np.int8), conv(priors, np.float32)
+    for arrs, shp in ((nb, shape), (nw, shape), (wl, shape), (pr, pshape)):
+        if arrs is not None and (len(arrs) != n or any(a is not None and a.shape != shp for a in arrs)):
+            raise ValueError(f"one {shape} base, water and wall array and (source prior) one {pshape} prior array per member")
+    if n < 1:
+        raise ValueError("no members")
+    ptrs = lambda arrs: None if arrs is None else (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
+    preds, keep = _cov_predictors(predictors, n)
+    c, planes = _cov_struct(field, source, rect, len(predictors), want)
+    res = (WxEnsCovResult * max(len(predictors), 1))()
+    rc = lib().wx_ens_cov_cells(C.byref(c), preds, res, int(X), int(Y), n, ptrs(nb), ptrs(nw), ptrs(wl), ptrs(pr), None if mask is None else mask.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_ens_cov_cells: bad descriptor or predictor, rectangle or point outside the grid, a missing array, or fewer than two members selected")
+    planes["results"] = _cov_results(res, len(predictors))
+    del keep
+    return planes
+
+
 ENS_QUANT_MAX = 8
 QUANT_INTERP = {"linear": 0, "lower": 1, "higher": 2}
 
@@ -696,6 +789,8 @@ def lib() -> C.CDLL:
     L.wx_ensemble_prior_drop.argtypes = [vp, i32]
     L.wx_ensemble_inflate.argtypes = [vp, C.POINTER(WxEnsInflate), vp]
     L.wx_ens_inflate_cells.argtypes = [C.POINTER(WxEnsInflate), i32, C.c_size_t, vp, vp, vp, vp]
+    L.wx_ensemble_covariance.argtypes = [vp, C.POINTER(WxEnsCov), vp, vp, vp]
+    L.wx_ens_cov_cells.argtypes = [C.POINTER(WxEnsCov), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -1382,6 +1477,25 @@ class Ensemble:
         mask = _member_mask(self.n, members)
         self._chk(lib().wx_ensemble_inflate(self._e, C.byref(p), None if mask is None else mask.ctypes.data))
         return lam
+
+    def covariance(self, field: str, predictors, *, source="current", rect=None, members=None, want=COV_PLANES) -> dict:
+        """wx_ensemble_covariance: for every cell and channel of ``rect`` = (x, y, w, h) (None: the whole grid) of ``field`` (BASE_CUR
+        or WATER_CUR) the sample covariance, over the selected members (at least two), between the members' values and up to 8 scalar
+        ``predictors`` -- ``(field name, x, y, channel)``: the members' own current value at a point; or one number per member (by
+        member index): a forecast metric --, all in one pass over the members. ``source`` "current": the field as it is now; "prior": the
+        snapshot ``save_prior`` took of it. Returns the planes named in ``want`` -- ``cov``, ``corr`` (clamped to [-1, 1]), ``slope``
+        (cov / var of the cell: the ensemble sensitivity dJ/dx): (n_pred, h, w, 4) float32; ``variance``: (h, w, 4) -- NaN where a cell
+        is a wall or holds a non-finite value in any selected member, and ``results``: one dict per predictor (valid, mean, variance).
+        Changes nothing; two launches; blocks like ``statistics``."""
+        rect = (0, 0, self.X, self.Y) if rect is None else rect
+        preds, keep = _cov_predictors(predictors, self.n)
+        c, planes = _cov_struct(field, source, rect, len(predictors), want)
+        res = (WxEnsCovResult * max(len(predictors), 1))()
+        mask = _member_mask(self.n, members)
+        self._chk(lib().wx_ensemble_covariance(self._e, C.byref(c), preds, res, None if mask is None else mask.ctypes.data))
+        planes["results"] = _cov_results(res, len(predictors))
+        del keep
+        return planes
 
     def close(self):
         if getattr(self, "_e", None):

@@ -358,6 +358,25 @@ class WeatherEnsemble:
         ("rtps", "rtpp") of one field of the selected members (mode, rect, members, lambda_bounds, lo, hi, want_lambda)."""
         return self._e.inflate(field, coef, **kw)
 
+    def covariance(self, field: str, predictors, **kw) -> dict:
+        """``engine.Ensemble.covariance``: the sample covariance, correlation and regression slope, over the selected members, between
+        every cell-channel of one field and up to 8 scalar predictors, in one pass on the device (source, rect, members, want)."""
+        return self._e.covariance(field, predictors, **kw)
+
+    def correlation(self, field: str, point, *, source="current", rect=None, members=None) -> np.ndarray:
+        """The ensemble correlation of ``field`` with the members' current value at ``point`` = (field name, x, y, channel), as one
+        (h, w, 4) plane: where it sinks into the sampling noise of about 1 / sqrt(n - 1) is where a localization half-width belongs."""
+        return self._e.covariance(field, [tuple(point)], source=source, rect=rect, members=members, want=("corr",))["corr"][0]
+
+    def sensitivity(self, metric, field: str, *, rect=None, members=None) -> dict:
+        """Ensemble sensitivity analysis (Torn and Hakim 2008): the regression of a per-member forecast metric J_k onto the prior that
+        ``save_prior`` took of ``field``. ``metric``: one number per member, or a callable that is given the list of the members'
+        ``diagnostics`` entries and returns them. Returns ``slope`` = dJ/dx and ``corr``, (h, w, 4) each, and ``result`` (the metric's
+        mean and variance over the members). Without a saved prior the library's WX_E_STATE message comes through."""
+        values = metric(self.diagnostics()) if callable(metric) else metric
+        out = self._e.covariance(field, [np.asarray(values, np.float64)], source="prior", rect=rect, members=members, want=("slope", "corr"))
+        return {"slope": out["slope"][0], "corr": out["corr"][0], "result": out["results"][0]}
+
     def analysis(self, observations, *, relax=None, inflate=None, **assimilate_kw) -> list:
         """One analysis step of a cycling filter: ``save_prior`` of the state fields with a non-zero gain (only with ``relax``), then
         ``assimilate(observations, **assimilate_kw)``, then the inflation -- ``relax`` = ("rtps", alpha) or ("rtpp", alpha): relaxation

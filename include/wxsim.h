@@ -1022,6 +1022,88 @@ int wx_ens_inflate_cells(const wx_ens_inflate *p, int n_members, size_t n_cells,
                          const int8_t *const *wall, const float *const *prior /* NULL entries allowed in CONST */,
                          const uint8_t *member_mask);   /* host only, pure; lambda_out over n_cells */
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_COVARIANCE) Covariance, correlation and sensitivity maps on the device: the quantity the filter runs
+ * on, made visible. wx_ensemble_assimilate forms the sample covariance, over the members, between a state cell and a scalar, weights
+ * it and throws it away. This call returns it, for every cell and channel of a rectangle, against up to WX_ENS_COV_MAX scalar
+ * PREDICTORS at once -- the members are read once for all of them --, together with the correlation (where does it sink into the
+ * sampling noise of about 1/sqrt(n-1)? that is how loc_x / loc_y are chosen) and the regression slope dJ/dx = cov(J, x) / var(x), the
+ * ensemble sensitivity of Torn and Hakim (2008). The state x is the members' field as it is now (WX_COV_SOURCE_CURRENT) or the snapshot
+ * wx_ensemble_prior_save took of it (WX_COV_SOURCE_PRIOR): "which part of the analysis decides the rain 500 iterations later" regresses
+ * a forecast metric J_k (e.g. from wx_ensemble_diagnostics) onto the saved prior, which lives only on the device.
+ *
+ * THE DEFINITION (the kernels, wx_ens_cov_cells and the tests all evaluate it). All arithmetic is double, every operation rounded
+ * separately (no fused multiply-add: contraction is off inside every function that rounds, and every product that feeds a sum is a
+ * value of its own in every build, so libwxsim.so, libwxsim_fast.so, the device and the host give the same bits); sqrt is the correctly
+ * rounded double square root. "In member order": the n selected members k = 0 .. n-1 by ascending member index. All sums start at +0.0.
+ *   Predictor j. WX_COV_PRED_POINT: t_k = (double) of channel `channel` of cell (x, y) of member k's CURRENT `field` (whatever the
+ *   source of the state); valid only if in every selected member that cell is an air cell (channel 1 of its WX_FIELD_WALL_CUR texel
+ *   != 0) and the value is finite. WX_COV_PRED_VALUES: t_k = values[member index] (n_members entries, by member index; the entries of
+ *   unselected members are not looked at); always valid, because entries that are not finite or exceed the float range are refused.
+ *   Valid: Sj = sum t_k in member order, jm = Sj / n, e_k = t_k - jm, Qj = sum e_k*e_k in member order; result[j] = {1, jm, Qj / (n-1)}.
+ *   For a point these are the bits wx_ens_obs_result.prior_mean / prior_var have for the same cell and channel. Invalid:
+ *   result[j] = {0, NaN, NaN} and every plane of that predictor is NaN everywhere.
+ *   Cell-channel. x_k is member k's value of channel c of the cell: of `field` (CURRENT) or of its snapshot (PRIOR). It is ELIGIBLE iff
+ *   in every selected member the cell is an air cell -- by the CURRENT wall texture in both sources: the snapshot holds no walls -- and
+ *   x_k is finite. Eligible: Sx = sum (double)x_k, xm = Sx / n, d_k = (double)x_k - xm, Qx = sum d_k*d_k, and for every valid predictor
+ *   Cq_j = sum d_k*e_jk, all in member order. Then
+ *     variance = (float)(Qx / (n-1))                the members' own sample variance
+ *     cov_j    = (float)(Cq_j / (n-1))
+ *     slope_j  = Qx == 0 ? NaN : (float)(Cq_j / Qx)    dJ/dx, the sensitivity
+ *     corr_j   = den == 0 ? NaN : (float)clamp(Cq_j / den, -1, 1)  with den = sqrt(Qx * Qj) (a rounded product, then the root)
+ *   Not eligible: NaN in all four. A double beyond the float range converts to +-Inf, as the C conversion does.
+ *   No product or sum here can overflow a double: |x_k|, |t_k| <= FLT_MAX (that is why VALUES are held to the float range), so
+ *   |d*e| <= 4 FLT_MAX^2, a Q or Cq is at most 65535 times that, and Qx * Qj < 1e166.
+ * Consequences. A point predictor's own cell-channel (same field, CURRENT) has Cq == Qx == Qj bit for bit: corr and slope are exactly
+ * 1.0f and cov has the bits of variance (unless Q is 0: NaN, NaN, 0). Cells never interact, and neither do channels: any split of the
+ * rectangle gives the same bits. Plane j depends on no other predictor.
+ *
+ * wx_ensemble_covariance. Answered before the device is touched -- WX_E_INVALID: e, c or pred NULL; a field other than
+ * WX_FIELD_BASE_CUR / WX_FIELD_WATER_CUR, for the state or for a point; an unknown kind or source; n_pred outside 1 .. WX_ENS_COV_MAX; a
+ * point channel outside 0 .. 3; VALUES with a NULL pointer, or with a selected member's entry that is not finite or has |v| > FLT_MAX;
+ * fewer than two selected members. WX_E_RANGE: the rectangle or a point lies outside the grid (no wrap). WX_E_STATE: a selected member
+ * was never uploaded (the message names it); with WX_COV_SOURCE_PRIOR, no snapshot of that field, a selection that differs from the
+ * snapshot's, a rectangle not inside the snapshot's (wx_ensemble_inflate's three checks; the message says which). `result` holds n_pred
+ * entries or is NULL. Everything else as for wx_ensemble_statistics: member_mask has one byte per member (NULL = all), the members'
+ * pointers are taken at the time of the call, the work is ordered behind everything pending on the ensemble's stream, the call BLOCKS
+ * like wx_ensemble_sync and consumes and returns a member's pending report ("member i: ..."), its device buffers belong to the ensemble
+ * and go with wx_ensemble_destroy. It CHANGES NOTHING a host can observe: no member is written, no lazy field is assembled, the
+ * snapshot is read only. Two launches: the predictors' chains (kernel name "ensemble_covariance_pred", one workgroup), then the maps
+ * (kernel name "ensemble_covariance"); wx_profile on member 0 times them; traffic per member-cell: DESIGN.md section 4.
+ * wx_ens_cov_cells (host only, pure): the same definition over whole X x Y grids the caller holds -- member i's at base[i] / water[i]
+ * (4 floats per cell) and wall[i] (4 bytes per cell); a table no predictor and no CURRENT state needs may be NULL -- and, with
+ * WX_COV_SOURCE_PRIOR, prior[i]: the w*h cells of the rectangle (4 floats per cell). Planes as above. WX_E_INVALID / WX_E_RANGE as above,
+ * and WX_E_INVALID for n_members < 1, a NULL table that is needed, a NULL entry of a selected member. */
+#define WX_HAVE_ENSEMBLE_COVARIANCE 1
+#define WX_ENS_COV_MAX 8
+#define WX_COV_PRED_POINT  0   /* the members' own value of one channel of one cell of their CURRENT state */
+#define WX_COV_PRED_VALUES 1   /* one double per member from the host: a forecast metric */
+#define WX_COV_SOURCE_CURRENT 0  /* x_k: the members' field as it is now */
+#define WX_COV_SOURCE_PRIOR   1  /* x_k: the snapshot wx_ensemble_prior_save took of that field */
+typedef struct wx_ens_cov_pred {
+  int32_t kind;             /* WX_COV_PRED_* */
+  int32_t field, x, y, channel;  /* POINT: WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR, the cell, 0 .. 3; VALUES: not looked at */
+  int32_t pad;
+  const double *values;     /* VALUES: n_members entries, by member index; POINT: not looked at */
+} wx_ens_cov_pred;
+typedef struct wx_ens_cov_result {
+  int32_t valid, pad;
+  double  mean, variance;   /* jm and Qj / (n-1); NaN if not valid */
+} wx_ens_cov_result;
+typedef struct wx_ens_cov {
+  int32_t field;            /* WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR */
+  int32_t source;           /* WX_COV_SOURCE_* */
+  int32_t x, y, w, h;       /* the rectangle; no wrap (WX_E_RANGE) */
+  int32_t n_pred, pad;      /* 1 .. WX_ENS_COV_MAX */
+  float  *cov, *corr, *slope;  /* n_pred planes of w*h*4 each, plane j = predictor j; NULL: not wanted */
+  float  *variance;         /* w*h*4: the members' own sample variance; NULL: not wanted */
+} wx_ens_cov;
+int wx_ensemble_covariance(wx_ensemble *e, const wx_ens_cov *c, const wx_ens_cov_pred *pred,
+                           wx_ens_cov_result *result /* n_pred entries or NULL */, const uint8_t *member_mask);
+int wx_ens_cov_cells(const wx_ens_cov *c, const wx_ens_cov_pred *pred, wx_ens_cov_result *result, int X, int Y, int n_members,
+                     const float *const *base, const float *const *water, const int8_t *const *wall,
+                     const float *const *prior /* w*h cells of the rectangle per member; WX_COV_SOURCE_PRIOR only */,
+                     const uint8_t *member_mask);   /* host only, pure */
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

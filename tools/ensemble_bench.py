@@ -53,6 +53,12 @@ says so. The shape's "inflate" key also holds the kernels' own times (wx_profile
 walks request when every cell is updated -- CONST 52, RTPS 100, RTPP 84, the snapshot 32 -- and against what crosses the memory interface
 if every re-read of a walk is served on the chip -- 36, 52, 52 --, both at --peak-gbs. Without
 --shapes: 100x100x64 and 2500x300x8.
+--covariance FIELD (BASE_CUR or WATER_CUR; --mode ensemble): what ONE wx_ensemble_covariance call over the whole grid costs with 1 and
+with 8 point predictors (all four planes wanted; host to host: the call blocks), 8 calls of one predictor next to the one call of 8,
+against B read_rect pairs (field, wall) plus the same arithmetic in numpy (float64, vectorised over the cells), and against the
+statistics kernel (mean and variance wanted) of the same run, which reads the same member bytes. The shape's "covariance" key holds
+the kernels' own times (wx_profile on member 0) and the fraction of --peak-gbs against 20 B + 16 B per member-cell plus the planes
+written. Without --shapes: 100x100x64 and 2500x300x8.
 --share K (debug build of the library only): the segment-height sweep -- every member's launch shape as for an ensemble of K members."""
 import argparse
 import json
@@ -79,13 +85,14 @@ def parse():
     ap.add_argument("--scores", default="", metavar="FIELD", help="time one score call (B members against member B of B + 1) against statistics + quantiles + read_rect + numpy (BASE_CUR or WATER_CUR)")
     ap.add_argument("--assimilate", default="", metavar="FIELD", help="time one assimilation call of --observations point observations against N calls of one and against read_rect + host function + uploads (BASE_CUR or WATER_CUR)")
     ap.add_argument("--inflate", default="", metavar="FIELD", help="time one inflation call per mode over the whole grid against read_rect + the host function (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--covariance", default="", metavar="FIELD", help="time one covariance call with 1 and with 8 point predictors over the whole grid against read_rect + numpy and the statistics kernel (BASE_CUR or WATER_CUR)")
     ap.add_argument("--observations", type=int, default=40, help="observations per call with --assimilate (1 .. 256)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = "100x100x64,2500x300x8" if a.scores or a.inflate else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
+        a.shapes = "100x100x64,2500x300x8" if a.scores or a.inflate or a.covariance else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
     return a
 
 
@@ -576,8 +583,107 @@ def time_inflate(a, pkg, ens, X, Y, B):
     return rec
 
 
+def numpy_covariance(fields, walls, points):
+    """The arithmetic of wx_ensemble_covariance in numpy, float64, vectorised over the cells (not bit-exact: numpy's sums are pairwise):
+    what a host does with B read_rect results."""
+    import numpy as np
+    f = np.stack([np.float64(a) for a in fields])
+    air = np.all(np.stack([w[..., 1] != 0 for w in walls]), axis=0)
+    ok = air[..., None] & np.isfinite(f).all(axis=0)
+    n = f.shape[0]
+    d = f - f.mean(axis=0)
+    qx = (d * d).sum(axis=0)
+    out = {"variance": np.where(ok, qx / (n - 1), np.nan).astype(np.float32), "cov": [], "corr": [], "slope": []}
+    for x, y, c in points:
+        t = f[:, y, x, c]
+        e = t - t.mean()
+        qj = float((e * e).sum())
+        cq = np.tensordot(e, d, axes=(0, 0))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["cov"].append(np.where(ok, cq / (n - 1), np.nan).astype(np.float32))
+            out["slope"].append(np.where(ok, cq / qx, np.nan).astype(np.float32))
+            out["corr"].append(np.where(ok, np.clip(cq / np.sqrt(qx * qj), -1, 1), np.nan).astype(np.float32))
+    return out
+
+
+COV_READ_BYTES = 36  # per member-cell: walk 1's 16 B + 4 B, walk 2's 16 B (csrc/wx_ens_cov.h)
+
+
+def time_covariance(a, pkg, ens, X, Y, B):
+    import statistics
+    field = a.covariance
+    ens.step(a.frame)
+    ens.sync()
+    air = None
+    for h in ens.members:
+        w = h.read_rect("WALL_CUR")[..., 1] != 0
+        air = w if air is None else air & w
+    import numpy as np
+    ys, xs = np.nonzero(air)
+    pick = np.linspace(0, len(xs) - 1, 8).astype(int)
+    points = [(field, int(xs[i]), int(ys[i]), 3 if field == "BASE_CUR" else 0) for i in pick]
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        ens.covariance(field, points[:1], want=("corr",))
+    ms = lambda t: round(1e3 * t, 3)  # noqa: E731
+    rec = {"field": field, "members": B, "calls": a.repeats, "predictors": {}}
+    for n_pred in (1, 8):
+        ens[0].profile(True)
+        t_call = []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            ens.covariance(field, points[:n_pred])
+            t_call.append(time.perf_counter() - t0)
+        prof = ens[0].profile_read()
+        ens[0].profile(False)
+        k_ms, k_n = prof.get("ensemble_covariance", (0.0, 0))
+        p_ms, p_n = prof.get("ensemble_covariance_pred", (0.0, 0))
+        k_us = 1e3 * k_ms / max(k_n, 1)
+        nbytes = COV_READ_BYTES * X * Y * B + (3 * n_pred + 1) * 16 * X * Y
+        once = (COV_READ_BYTES - 16) * X * Y * B + (3 * n_pred + 1) * 16 * X * Y
+        gbs = nbytes / (k_us * 1e-6) / 1e9 if k_us > 0 else None
+        gbs_once = once / (k_us * 1e-6) / 1e9 if k_us > 0 else None
+        rec["predictors"][str(n_pred)] = {"one_call_ms": {"slowest": ms(max(t_call)), "median": ms(statistics.median(t_call))},
+                                          "kernel_us": round(k_us, 2), "prepass_kernel_us": round(1e3 * p_ms / max(p_n, 1), 2), "kernel_launches_timed": k_n,
+                                          "bytes_requested": nbytes, "kernel_gb_per_s_requested": round(gbs, 1) if gbs else None,
+                                          "kernel_fraction_of_peak_requested": round(gbs / a.peak_gbs, 4) if gbs else None,
+                                          "kernel_gb_per_s_second_walk_on_chip": round(gbs_once, 1) if gbs_once else None,
+                                          "kernel_fraction_of_peak_second_walk_on_chip": round(gbs_once / a.peak_gbs, 4) if gbs_once else None}
+    t_eight = []
+    for _ in range(a.repeats):  # 8 calls of one predictor: what taking several predictors at once saves
+        t0 = time.perf_counter()
+        for p in points:
+            ens.covariance(field, [p])
+        t_eight.append(time.perf_counter() - t0)
+    rec["eight_calls_of_one_ms"] = {"slowest": ms(max(t_eight)), "median": ms(statistics.median(t_eight))}
+    rec["eight_calls_over_one_call_of_eight_median"] = round(statistics.median(t_eight) * 1e3 / float(rec["predictors"]["8"]["one_call_ms"]["median"]), 2)
+    # the statistics kernel of the same run: the same member bytes, two planes written
+    ens[0].profile(True)
+    for _ in range(a.repeats):
+        ens.statistics(field, want=("mean", "variance"))
+    prof = ens[0].profile_read()
+    ens[0].profile(False)
+    s_ms, s_n = prof.get("ensemble_statistics", (0.0, 0))
+    rec["statistics_kernel_us_mean_variance"] = round(1e3 * s_ms / max(s_n, 1), 2)
+    # the host route: B read_rect pairs + numpy
+    for n_pred in (1, 8):
+        t_host, t_read = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            fields, walls = [h.read_rect(field) for h in ens.members], [h.read_rect("WALL_CUR") for h in ens.members]
+            t1 = time.perf_counter()
+            numpy_covariance(fields, walls, [p[1:] for p in points[:n_pred]])
+            t_read.append(t1 - t0)
+            t_host.append(time.perf_counter() - t0)
+        rec["read_numpy_route_%d_ms" % n_pred] = {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))}
+        rec["speedup_median_over_read_numpy_route_%d" % n_pred] = round(statistics.median(t_host) * 1e3 / float(rec["predictors"][str(n_pred)]["one_call_ms"]["median"]), 2)
+    return rec
+
+
 def main():
     a = parse()
+    if a.covariance and (a.mode != "ensemble" or a.covariance not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--covariance BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.inflate and (a.mode != "ensemble" or a.inflate not in ("BASE_CUR", "WATER_CUR")):
         sys.exit("--inflate BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.assimilate and (a.mode != "ensemble" or a.assimilate not in ("BASE_CUR", "WATER_CUR") or not 1 <= a.observations <= 256):
@@ -645,6 +751,10 @@ def main():
             continue
         if a.inflate:
             out["shapes"][spec] = {"members": B, "inflate": time_inflate(a, pkg, ens, X, Y, B)}
+            close()
+            continue
+        if a.covariance:
+            out["shapes"][spec] = {"members": B, "covariance": time_covariance(a, pkg, ens, X, Y, B)}
             close()
             continue
         if a.assimilate:
