@@ -2825,7 +2825,7 @@ static int pool_events_apply_mode(wx_sim *s, const void *dev_bufs, int n_ranks, 
   if (int rc = pool_fence(s, st)) return rc;
   const char *b = (const char *)dev_bufs;
   const int cap = (int)((stride - POOL_HDR) / sizeof(PoolEvent)); // entries a rank's (possibly truncated) buffer holds
-  hipLaunchKernelGGL(k_pool_check, dim3(1), dim3(64), 0, st, n_ranks, stride, cap, b, s->state, 1);
+  hipLaunchKernelGGL(k_pool_check, dim3((n_ranks + 63) / 64), dim3(64), 0, st, n_ranks, stride, cap, b, s->state, 1); // (one thread per rank: the key holds 1024)
   if (s->pool.ev_seen_host) { // the library's transport sizes the coming all-gathers by what this one carried (wx_comm.h: pool_stride_update)
     HIPCHK(s, hipMemcpyAsync(s->pool.ev_seen_host, &s->state->pool_seen_max, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(s, hipEventRecord(s->pool.ev_counted, st));

@@ -408,6 +408,7 @@ int wx_step_overlap(wx_sim *s, int n_iter, unsigned flags);
  *       `inactiveDroplets` uniform (app.js:5957-5966) from the inactive records -- every rank holds all of them: no collective;
  *   lightning state: wx_lightning_get -> pick the latest strike -> wx_lightning_set;  then wx_slab_period_begin.
  * Buffer overflows (more status flips / edge droplets than the fixed capacities) are reported by the next blocking call (WX_E_STATE).
+ * wx_pool_events_apply checks the header of every one of its n_ranks buffers against the stride's capacity, whatever n_ranks is.
  * wx_read_particles returns the LOCAL view of the pool; wx_pool_flags says per droplet what it is worth: 0 = tracked by another rank
  * (stale here), 1 = inactive (the same record on every rank), 2 = active inside this rank's owned columns (THE record), 3 = ghost copy. */
 int wx_slab_set_rank(wx_sim *s, int rank);

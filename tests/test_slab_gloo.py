@@ -14,6 +14,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from pool_model import ModelPoolEngine  # the numpy model of the pool kernels, shared with tests/test_pool_exchange_*.py
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HALO_FIELDS = ("BASE_CUR", "WATER_CUR", "LIGHT_0", "LIGHT_1", "WALL_CUR")
@@ -135,122 +137,6 @@ def test_slab_geometry(pkg):
         slab.slab_columns(100, 0, 3)
     with pytest.raises(ValueError):
         slab.SlabSim(object(), 0, 2, 4)
-
-
-class ModelPoolEngine:
-    """The droplet-pool side of the slab-engine interface as a numpy model of the exchange kernels (csrc/wx_kernels.h: k_pool_events_pack /
-    _best / _apply, k_pool_edges_pack / _apply) on a 1-D domain, with the physics of a period SCRIPTED by the test: checks
-    SlabSim.exchange() -- all-gather of the status-flip events, edge droplets in the batch of send / recv, lightning -- over gloo."""
-    EV = np.dtype([("gid", "<i4"), ("key", "<i4"), ("rec", "<f4", 5), ("pad", "<i4")])
-    ER = np.dtype([("gid", "<i4"), ("rec", "<f4", 5)])
-    CAP = 64
-
-    def __init__(self, rank, world, n, X, halo):
-        self.rank, self.world, self.n_droplets, self.X, self.halo = rank, world, n, X, halo
-        self.xo = X // world
-        self.pool = np.zeros((n, 5), np.float32)
-        self.remote = np.zeros(n, bool)
-        self.flips = np.zeros(n, np.uint16)
-        self.meta = np.zeros(n, np.uint8)  # low 4 bits: last iteration processed (+1); bit 7: processed inside the owned columns
-        self.strike = np.zeros(4, np.float32)
-        self.periods, self.refreshed = 0, []
-
-    def col(self, px):  # global column of a position in [-1, 1)
-        return np.floor((px / 2.0 + 0.5) * self.X).astype(int) % self.X
-
-    def owned(self, px):
-        return (self.col(px) // self.xo) == self.rank
-
-    # grid side: nothing to exchange
-    def new_buffer(self):
-        return torch.zeros(8, dtype=torch.uint8)
-
-    def pack(self, side, buf):
-        pass
-
-    def unpack(self, side, buf):
-        pass
-
-    def step(self, n):
-        pass
-
-    def sync(self):
-        pass
-
-    def new_pool_buffers(self, world):
-        eb, gb = 16 + self.CAP * self.EV.itemsize, 16 + self.CAP * self.ER.itemsize
-        z = lambda k: torch.zeros(k, dtype=torch.uint8)
-        return z(eb), z(eb * world), [z(gb), z(gb)], [z(gb), z(gb)]
-
-    def pool_events_pack(self, buf):
-        sel = np.nonzero((self.flips != 0) & ((self.meta & 0x80) != 0))[0]
-        ev = np.zeros(len(sel), self.EV)
-        for k, i in enumerate(sel):
-            f = int(self.flips[i])
-            first = (f & -f).bit_length() - 1
-            ev[k] = (i, (first << 18) | ((15 - bin(f).count("1")) << 14) | ((15 - int(self.meta[i] & 15)) << 10) | self.rank, self.pool[i], 0)
-        self.flips[:] = 0
-        self.meta[:] = 0
-        raw = np.zeros(len(buf), np.uint8)
-        raw[:4] = np.array([len(sel)], "<i4").view(np.uint8)
-        raw[16:16 + ev.nbytes] = ev.view(np.uint8)
-        buf.copy_(torch.from_numpy(raw))
-
-    def pool_events_apply(self, gathered, world, stride=0):
-        raw = gathered.numpy()
-        stride = stride or len(raw) // world
-        evs = []
-        for r in range(world):
-            cnt = int(raw[r * stride:r * stride + 4].view("<i4")[0])
-            evs.append(raw[r * stride + 16:r * stride + 16 + cnt * self.EV.itemsize].view(self.EV))
-        allev = np.concatenate(evs)
-        best = {}
-        for e in allev:
-            best[int(e["gid"])] = min(best.get(int(e["gid"]), 1 << 30), int(e["key"]))
-        for e in allev:
-            if best[int(e["gid"])] == int(e["key"]) and (int(e["key"]) & 1023) != self.rank:
-                self.pool[e["gid"]] = e["rec"]
-                self.remote[e["gid"]] = False
-
-    def pool_edges_pack(self, left, right, refresh):
-        self.refreshed.append(bool(refresh))
-        out = {0: [], 1: []}
-        for i in range(self.n_droplets):
-            if self.remote[i] or self.pool[i, 2] < 0:
-                continue
-            c = int(self.col(self.pool[i, 0]))
-            if c // self.xo != self.rank:
-                self.remote[i] = True
-                continue
-            lc = c - self.rank * self.xo
-            if lc < self.halo:
-                out[0].append(i)
-            if lc >= self.xo - self.halo:
-                out[1].append(i)
-        for side, buf in ((0, left), (1, right)):
-            rec = np.zeros(len(out[side]), self.ER)
-            for k, i in enumerate(out[side]):
-                rec[k] = (i, self.pool[i])
-            raw = np.zeros(len(buf), np.uint8)
-            raw[:4] = np.array([len(rec)], "<i4").view(np.uint8)
-            raw[16:16 + rec.nbytes] = rec.view(np.uint8)
-            buf.copy_(torch.from_numpy(raw))
-
-    def pool_edges_apply(self, buf):
-        raw = buf.numpy()
-        cnt = int(raw[:4].view("<i4")[0])
-        for e in raw[16:16 + cnt * self.ER.itemsize].view(self.ER):
-            self.pool[e["gid"]] = e["rec"]
-            self.remote[e["gid"]] = False
-
-    def lightning(self):
-        return self.strike
-
-    def set_lightning(self, v):
-        self.strike = np.asarray(v, np.float32).copy()
-
-    def period_begin(self):
-        self.periods += 1
 
 
 def _rec(px, active, tag):
