@@ -30,9 +30,8 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/wxsim.h"
-#include "wx_ens_stat.h"
+#include "wx_ens_frame.h"
 #include "wx_ens_perturb.h"
-#include "wx_ens_quant.h"
 #include "wx_ens_assim_cell.h"
 
 namespace wxa {
@@ -87,13 +86,11 @@ typedef const __attribute__((address_space(4))) ObsHdr *CHdr;
 typedef const __attribute__((address_space(4))) double *CE;
 __device__ __forceinline__ CHdr const_hdr(const ObsHdr *h) { return (CHdr)(unsigned long long)h; }
 __device__ __forceinline__ CE const_e(const double *e) { return (CE)(unsigned long long)e; }
-#define WX_ENS_ASSIM_LOADS_ISSUED() __builtin_amdgcn_sched_barrier(0)
 #else // host pass of the single-source compile: same meaning, never executed
 typedef const ObsHdr *CHdr;
 typedef const double *CE;
 __device__ __forceinline__ CHdr const_hdr(const ObsHdr *h) { return h; }
 __device__ __forceinline__ CE const_e(const double *e) { return e; }
-#define WX_ENS_ASSIM_LOADS_ISSUED() ((void)0)
 #endif
 
 __global__ __launch_bounds__(OBS_WG) void k_ens_assim_obs(const ObsArgs a)
@@ -182,7 +179,7 @@ __global__ __launch_bounds__(WG) void k_ens_assim(const Args a)
         int wd[UNROLL];
 #pragma unroll
         for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
-        WX_ENS_ASSIM_LOADS_ISSUED();
+        WX_ENS_LOADS_ISSUED();
 #pragma unroll
         for (int i = 0; i < UNROLL; i++) {
           const bool air = wd[i] != 0;
@@ -208,7 +205,7 @@ __global__ __launch_bounds__(WG) void k_ens_assim(const Args a)
         wxe::f32x4 v[UNROLL];
 #pragma unroll
         for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off);
-        WX_ENS_ASSIM_LOADS_ISSUED();
+        WX_ENS_LOADS_ISSUED();
 #pragma unroll
         for (int i = 0; i < UNROLL; i++) {
           const double ek = e[k + i];
@@ -243,7 +240,7 @@ __global__ __launch_bounds__(WG) void k_ens_assim(const Args a)
         wxe::f32x4 v[UNROLL];
 #pragma unroll
         for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off);
-        WX_ENS_ASSIM_LOADS_ISSUED();
+        WX_ENS_LOADS_ISSUED();
 #pragma unroll
         for (int i = 0; i < UNROLL; i++) write(k + i, v[i]);
       }
@@ -251,7 +248,6 @@ __global__ __launch_bounds__(WG) void k_ens_assim(const Args a)
     }
   }
 }
-#undef WX_ENS_ASSIM_LOADS_ISSUED
 #endif // __HIPCC__
 
 } // namespace wxa
@@ -264,36 +260,28 @@ int wx_ens_assim_cells(const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs, 
 
 int wx_ensemble_assimilate(wx_ensemble *e, const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs, wx_ens_obs_result *result, const uint8_t *member_mask)
 {
+  static const char *const call = "wx_ensemble_assimilate";
   if (!e || !a || !obs) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
   const char *why;
   if (int rc = wxa::check_desc(a, n_obs, obs, e->X, e->Y, &why)) return efail(e, rc, "wx_ensemble_assimilate: %s", why);
-  const int B = (int)e->member.size();
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  const std::vector<int> sel = ens_select(e, member_mask);
   if (sel.size() < 2) return efail(e, WX_E_INVALID, "wx_ensemble_assimilate: the member mask selects %zu member(s); a sample variance takes two", sel.size());
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_assimilate before wx_upload", i);
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
 
   const int n = (int)sel.size();
   size_t at[5];
   const size_t total = wxa::table_layout(n_obs, n, at);
-  if (int rc = ens_stat_reserve(e, 2 * n, total)) return rc;
-  EnsStatState *st = e->stat;
+  EnsCall c(e, call, K_ENS_ASSIM_OBS);
+  if (int rc = ens_begin(c, 2 * n, total)) return rc;
+  EnsStage *st = c.st;
   bool update[2] = {false, false}; // base, water
-  for (int c = 0; c < 4; c++) update[0] = update[0] || a->gain_base[c] != 0.0f, update[1] = update[1] || a->gain_water[c] != 0.0f;
-  for (int k = 0; k < n; k++) {
-    wx_sim *m = e->member[sel[k]];
+  for (int ch = 0; ch < 4; ch++) update[0] = update[0] || a->gain_base[ch] != 0.0f, update[1] = update[1] || a->gain_water[ch] != 0.0f;
+  for (int i : sel) {
     if (update[0])
-      if (int rc = epass(e, sel[k], ens_perturb_prepare(m, WX_FIELD_BASE_CUR))) return rc;
+      if (int rc = epass(e, i, ens_perturb_prepare(e->member[i], WX_FIELD_BASE_CUR))) return rc;
     if (update[1])
-      if (int rc = epass(e, sel[k], ens_perturb_prepare(m, WX_FIELD_WATER_CUR))) return rc;
-    // the members' pointers as they are NOW (a step rotates the planes)
-    st->tab_host[k] = wxe::Member{m->base[0], m->wall[0], sel[k], 0};
-    st->tab_host[n + k] = wxe::Member{m->water[1], m->wall[0], sel[k], 0};
+      if (int rc = epass(e, i, ens_perturb_prepare(e->member[i], WX_FIELD_WATER_CUR))) return rc;
   }
   memcpy(st->out_host + at[0], obs, sizeof(wx_ens_obs) * (size_t)n_obs);
 
@@ -302,45 +290,29 @@ int wx_ensemble_assimilate(wx_ensemble *e, const wx_ens_assim *a, int n_obs, con
   oa.X = e->X, oa.n_sel = n, oa.n_obs = n_obs, oa.a = *a, oa.tab = st->tab_dev;
   oa.t.obs = (wx_ens_obs *)(st->out_dev + at[0]), oa.t.res = (wx_ens_obs_result *)(st->out_dev + at[1]);
   oa.t.hdr = (wxa::ObsHdr *)(st->out_dev + at[2]), oa.t.e = (double *)(st->out_dev + at[3]), oa.t.W = (float *)(st->out_dev + at[4]);
+  const size_t w_bytes = 4 * (size_t)n_obs * (size_t)n;
+  oa.w_in_lds = w_bytes <= wxa::OBS_LDS_BYTES ? 1 : 0;
 
-  // on the ensemble's stream, behind everything pending: table and observations, the pre-pass, the update launches, the results
-  const char *failed = kKernelNames[K_ENS_ASSIM_OBS];
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, 2 * (size_t)n * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemcpyAsync(oa.t.obs, st->out_host + at[0], sizeof(wx_ens_obs) * (size_t)n_obs, hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    {
-      ProfScope ps(e->member[0], K_ENS_ASSIM_OBS); // (wx_profile on member 0 sees the launches, whoever is selected)
-      const size_t w_bytes = 4 * (size_t)n_obs * (size_t)n;
-      oa.w_in_lds = w_bytes <= wxa::OBS_LDS_BYTES ? 1 : 0;
-      hipLaunchKernelGGL(wxa::k_ens_assim_obs, dim3(1), dim3(wxa::OBS_WG), oa.w_in_lds ? w_bytes : 0, e->stream, oa);
-    }
-    he = hipGetLastError();
-  }
-  for (int f = 0; f < 2 && he == hipSuccess; f++) {
+  // table and observations, the pre-pass, the update launches, the results
+  ens_table_base_water(c, sel);
+  if (c.he == hipSuccess) c.he = hipMemcpyAsync(oa.t.obs, st->out_host + at[0], sizeof(wx_ens_obs) * (size_t)n_obs, hipMemcpyHostToDevice, e->stream);
+  ens_launch(c, K_ENS_ASSIM_OBS, [&] { hipLaunchKernelGGL(wxa::k_ens_assim_obs, dim3(1), dim3(wxa::OBS_WG), oa.w_in_lds ? w_bytes : 0, e->stream, oa); });
+  const unsigned wgs = ens_wgs_wave_per_item(ens_chunks(a->w, a->h), wxa::WAVES, wxa::MAX_WGS);
+  for (int f = 0; f < 2; f++) {
     if (!update[f]) continue;
-    failed = kKernelNames[K_ENS_ASSIM];
     wxa::Args ka;
     memset(&ka, 0, sizeof(ka));
     ka.X = e->X, ka.x0 = a->x, ka.y0 = a->y, ka.w = a->w, ka.h = a->h, ka.n_sel = n, ka.n_obs = n_obs;
     ka.loc = wxa::Loc{e->X, a->wrap_x ? 1 : 0, a->loc_x, a->loc_y};
     memcpy(ka.gain, f ? a->gain_water : a->gain_base, 16), memcpy(ka.lo, f ? a->lo_water : a->lo_base, 16), memcpy(ka.hi, f ? a->hi_water : a->hi_base, 16);
     ka.tab = st->tab_dev + (f ? n : 0), ka.hdr = oa.t.hdr, ka.e = oa.t.e;
-    const unsigned chunks = (unsigned)((a->w + 63) / 64) * (unsigned)a->h;
-    const unsigned wgs = std::min<unsigned>((chunks + wxa::WAVES - 1) / wxa::WAVES, wxa::MAX_WGS);
-    {
-      ProfScope ps(e->member[0], K_ENS_ASSIM);
-      hipLaunchKernelGGL(wxa::k_ens_assim, dim3(wgs), dim3(wxa::WG), 0, e->stream, ka);
-    }
-    he = hipGetLastError();
+    ens_launch(c, K_ENS_ASSIM, [&] { hipLaunchKernelGGL(wxa::k_ens_assim, dim3(wgs), dim3(wxa::WG), 0, e->stream, ka); });
   }
-  if (he == hipSuccess && result)
-    he = hipMemcpyAsync(st->out_host + at[1], oa.t.res, sizeof(wx_ens_obs_result) * (size_t)n_obs, hipMemcpyDeviceToHost, e->stream);
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_assimilate (%s): %s", failed, hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_perturb, and like it a place where every member's pending report is looked at and consumed
-  const int rc = wx_ensemble_sync(e);
-  if (result) memcpy(result, st->out_host + at[1], sizeof(wx_ens_obs_result) * (size_t)n_obs);
+  if (c.he == hipSuccess && result)
+    c.he = hipMemcpyAsync(st->out_host + at[1], oa.t.res, sizeof(wx_ens_obs_result) * (size_t)n_obs, hipMemcpyDeviceToHost, e->stream);
+  const int rc = ens_finish(c);
+  // The members are changed by now, so what the filter did goes back even when the sync hands on a member's pending report (an
+  // overflowed list of an earlier step, say): the report is about that member, not about this call. Not after a failed enqueue.
+  if (c.he == hipSuccess && result) memcpy(result, st->out_host + at[1], sizeof(wx_ens_obs_result) * (size_t)n_obs);
   return rc;
 }

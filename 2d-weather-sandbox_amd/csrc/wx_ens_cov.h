@@ -25,8 +25,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/wxsim.h"
-#include "wx_ens_stat.h"
-#include "wx_ens_quant.h"
+#include "wx_ens_frame.h"
 #include "wx_ens_inflate.h"
 #include "wx_ens_cov_cell.h"
 
@@ -84,13 +83,11 @@ typedef const __attribute__((address_space(4))) PredHdr *CHdr;
 typedef const __attribute__((address_space(4))) double *CE;
 __device__ __forceinline__ CHdr const_hdr(const PredHdr *h) { return (CHdr)(unsigned long long)h; }
 __device__ __forceinline__ CE const_e(const double *e) { return (CE)(unsigned long long)e; }
-#define WX_ENS_COV_LOADS_ISSUED() __builtin_amdgcn_sched_barrier(0)
 #else // host pass of the single-source compile: same meaning, never executed
 typedef const PredHdr *CHdr;
 typedef const double *CE;
 __device__ __forceinline__ CHdr const_hdr(const PredHdr *h) { return h; }
 __device__ __forceinline__ CE const_e(const double *e) { return e; }
-#define WX_ENS_COV_LOADS_ISSUED() ((void)0)
 #endif
 
 __global__ __launch_bounds__(PRED_WG) void k_ens_cov_pred(const PredArgs a)
@@ -153,7 +150,7 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
       int wd[UNROLL];
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) v[i] = ld_x(k + i, off, poff), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
-      WX_ENS_COV_LOADS_ISSUED();
+      WX_ENS_LOADS_ISSUED();
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) {
         const bool air = wd[i] != 0;
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
       wxe::f32x4 v[UNROLL];
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) v[i] = ld_x(k + i, off, poff);
-      WX_ENS_COV_LOADS_ISSUED();
+      WX_ENS_LOADS_ISSUED();
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) take(k + i, v[i]);
     }
@@ -230,7 +227,6 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
     }
   }
 }
-#undef WX_ENS_COV_LOADS_ISSUED
 
 template <int SOURCE>
 static void launch_cov(int np, unsigned wgs, hipStream_t stream, const Args &a)
@@ -252,33 +248,20 @@ int wx_ens_cov_cells(const wx_ens_cov *c, const wx_ens_cov_pred *pred, wx_ens_co
 
 int wx_ensemble_covariance(wx_ensemble *e, const wx_ens_cov *c, const wx_ens_cov_pred *pred, wx_ens_cov_result *result, const uint8_t *member_mask)
 {
+  static const char *const call = "wx_ensemble_covariance";
   if (!e || !c || !pred) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
   const char *why;
   if (int rc = wxc::check_desc(c, pred, &why)) return efail(e, rc, "wx_ensemble_covariance: %s", why);
-  const int B = (int)e->member.size();
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  const std::vector<int> sel = ens_select(e, member_mask);
   if (sel.size() < 2) return efail(e, WX_E_INVALID, "wx_ensemble_covariance: the member mask selects %zu member(s); a sample covariance takes two", sel.size());
   if (int rc = wxc::check_values(c, pred, sel, &why)) return efail(e, rc, "wx_ensemble_covariance: %s", why);
   if (int rc = wxc::check_rect(c, pred, e->X, e->Y, &why)) return efail(e, rc, "wx_ensemble_covariance: %s", why);
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_covariance before wx_upload", i);
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
   const bool from_prior = c->source == WX_COV_SOURCE_PRIOR;
   const EnsPriorSlot *snap = nullptr;
-  if (from_prior) {
-    snap = e->prior ? &e->prior->slot[c->field == WX_FIELD_BASE_CUR ? 0 : 1] : nullptr;
-    if (!snap || !snap->have) return efail(e, WX_E_STATE, "wx_ensemble_covariance: no snapshot of field %d (wx_ensemble_prior_save comes first)", c->field);
-    for (int i = 0; i < B; i++)
-      if ((snap->selected[(size_t)i] != 0) != (!member_mask || member_mask[i]))
-        return efail(e, WX_E_STATE, "wx_ensemble_covariance: the selection differs from the snapshot's (member %d)", i);
-    if (c->x < snap->x || c->y < snap->y || c->x + c->w > snap->x + snap->w || c->y + c->h > snap->y + snap->h)
-      return efail(e, WX_E_STATE, "wx_ensemble_covariance: rect (%d,%d %dx%d) is not inside the snapshot's (%d,%d %dx%d)", c->x, c->y, c->w, c->h, snap->x, snap->y,
-                   snap->w, snap->h);
-  }
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
+  if (from_prior)
+    if (int rc = ens_snapshot_for(e, call, c->field, member_mask, c->x, c->y, c->w, c->h, &snap)) return rc;
 
   const int n = (int)sel.size(), n_pred = c->n_pred, np = wxc::bucket_of(n_pred);
   const size_t plane = (size_t)c->w * (size_t)c->h * sizeof(float4);
@@ -291,14 +274,9 @@ int wx_ensemble_covariance(wx_ensemble *e, const wx_ens_cov *c, const wx_ens_cov
     at[i] = total;
     if (want[i]) total += plane * (size_t)(i < 3 ? n_pred : 1);
   }
-  if (int rc = ens_stat_reserve(e, 2 * n, total)) return rc;
-  EnsStatState *st = e->stat;
-  // the members' pointers as they are NOW (a step rotates the planes): base_0 / water_1 and wall_0, what wx_ensemble_statistics reads
-  for (int k = 0; k < n; k++) {
-    const wx_sim *m = e->member[sel[k]];
-    st->tab_host[k] = wxe::Member{m->base[0], m->wall[0], sel[k], 0};
-    st->tab_host[n + k] = wxe::Member{m->water[1], m->wall[0], sel[k], 0};
-  }
+  EnsCall frame(e, call, K_ENS_COV_PRED);
+  if (int rc = ens_begin(frame, 2 * n, total)) return rc;
+  EnsStage *st = frame.st;
   // the host's numbers, by position among the selected members; the other rows are the pre-pass's
   double *e_host = (double *)(st->out_host + tat[0]);
   memset(e_host, 0, 8 * (size_t)np * (size_t)n);
@@ -321,36 +299,18 @@ int wx_ensemble_covariance(wx_ensemble *e, const wx_ens_cov *c, const wx_ens_cov
   a.cov = want[0] ? (float4 *)(st->out_dev + at[0]) : nullptr, a.corr = want[1] ? (float4 *)(st->out_dev + at[1]) : nullptr;
   a.slope = want[2] ? (float4 *)(st->out_dev + at[2]) : nullptr, a.variance = want[3] ? (float4 *)(st->out_dev + at[3]) : nullptr;
 
-  // on the ensemble's stream, behind everything pending: table and host values, the pre-pass, the maps, results and planes to the pinned copy
-  const char *failed = kKernelNames[K_ENS_COV_PRED];
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, 2 * (size_t)n * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemcpyAsync(pa.t.e, e_host, 8 * (size_t)np * (size_t)n, hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    {
-      ProfScope ps(e->member[0], K_ENS_COV_PRED); // (wx_profile on member 0 sees the launches, whoever is selected)
-      hipLaunchKernelGGL(wxc::k_ens_cov_pred, dim3(1), dim3(wxc::PRED_WG), 0, e->stream, pa);
-    }
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess) {
-    failed = kKernelNames[K_ENS_COV];
-    const unsigned chunks = (unsigned)((c->w + 63) / 64) * (unsigned)c->h;
-    const unsigned wgs = std::min<unsigned>((chunks + wxc::WAVES - 1) / wxc::WAVES, wxc::MAX_WGS);
-    {
-      ProfScope ps(e->member[0], K_ENS_COV);
-      if (from_prior) wxc::launch_cov<WX_COV_SOURCE_PRIOR>(np, wgs, e->stream, a);
-      else wxc::launch_cov<WX_COV_SOURCE_CURRENT>(np, wgs, e->stream, a);
-    }
-    he = hipGetLastError();
-  }
+  // table and host values, the pre-pass, the maps, results and planes to the pinned copy
+  ens_table_base_water(frame, sel);
+  if (frame.he == hipSuccess) frame.he = hipMemcpyAsync(pa.t.e, e_host, 8 * (size_t)np * (size_t)n, hipMemcpyHostToDevice, e->stream);
+  ens_launch(frame, K_ENS_COV_PRED, [&] { hipLaunchKernelGGL(wxc::k_ens_cov_pred, dim3(1), dim3(wxc::PRED_WG), 0, e->stream, pa); });
+  const unsigned wgs = ens_wgs_wave_per_item(ens_chunks(c->w, c->h), wxc::WAVES, wxc::MAX_WGS);
+  ens_launch(frame, K_ENS_COV, [&] {
+    if (from_prior) wxc::launch_cov<WX_COV_SOURCE_PRIOR>(np, wgs, e->stream, a);
+    else wxc::launch_cov<WX_COV_SOURCE_CURRENT>(np, wgs, e->stream, a);
+  });
   // (the e rows are not wanted back: the copy starts at the results)
-  if (he == hipSuccess) he = hipMemcpyAsync(st->out_host + tat[1], st->out_dev + tat[1], total - tat[1], hipMemcpyDeviceToHost, e->stream);
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_covariance (%s): %s", failed, hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_statistics, and like it a place where every member's pending report is looked at and consumed
-  if (int rc = wx_ensemble_sync(e)) return rc;
+  if (frame.he == hipSuccess) frame.he = hipMemcpyAsync(st->out_host + tat[1], st->out_dev + tat[1], total - tat[1], hipMemcpyDeviceToHost, e->stream);
+  if (int rc = ens_finish(frame)) return rc;
   if (result) memcpy(result, st->out_host + tat[1], sizeof(wx_ens_cov_result) * (size_t)n_pred);
   for (int i = 0; i < 4; i++)
     if (want[i]) memcpy(want[i], st->out_host + at[i], plane * (size_t)(i < 3 ? n_pred : 1));

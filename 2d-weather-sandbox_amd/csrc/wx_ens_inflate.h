@@ -23,7 +23,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/wxsim.h"
-#include "wx_ens_stat.h"
+#include "wx_ens_frame.h"
 #include "wx_ens_perturb.h"
 #include "wx_ens_inflate_cell.h"
 
@@ -52,16 +52,6 @@ struct Args {
 enum { WG = 256, WAVES = WG / 64, MAX_WGS = 2048, UNROLL = 8, SAVE_MAX_WGS = 2048 };
 
 #if defined(__HIPCC__)
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ wxe::f32x4 ld_prior(const float4 *p, size_t i) { return ((const __attribute__((address_space(1))) wxe::f32x4 *)(unsigned long long)p)[i]; }
-__device__ __forceinline__ void st_texel(float4 *p, size_t i, wxe::f32x4 v) { ((__attribute__((address_space(1))) wxe::f32x4 *)(unsigned long long)p)[i] = v; }
-#define WX_ENS_INFLATE_LOADS_ISSUED() __builtin_amdgcn_sched_barrier(0)
-#else // host pass of the single-source compile: same meaning, never executed
-__device__ __forceinline__ wxe::f32x4 ld_prior(const float4 *p, size_t i) { return wxe::f32x4{p[i].x, p[i].y, p[i].z, p[i].w}; }
-__device__ __forceinline__ void st_texel(float4 *p, size_t i, wxe::f32x4 v) { p[i] = make_float4(v.x, v.y, v.z, v.w); }
-#define WX_ENS_INFLATE_LOADS_ISSUED() ((void)0)
-#endif
-
 __global__ __launch_bounds__(WG) void k_ens_prior_save(const SaveArgs a)
 {
   const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
@@ -107,7 +97,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
         v[i] = wxe::ld_field(tab + k + i, off), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
         if (RELAX) p[i] = ld_prior(a.prior, (size_t)(k + i) * pstride + poff);
       }
-      WX_ENS_INFLATE_LOADS_ISSUED();
+      WX_ENS_LOADS_ISSUED();
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) {
         const bool air = wd[i] != 0;
@@ -146,7 +136,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
           wxe::f32x4 v[UNROLL], p[UNROLL];
 #pragma unroll
           for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off), p[i] = ld_prior(a.prior, (size_t)(k + i) * pstride + poff);
-          WX_ENS_INFLATE_LOADS_ISSUED();
+          WX_ENS_LOADS_ISSUED();
 #pragma unroll
           for (int i = 0; i < UNROLL; i++) write(k + i, v[i], p[i]);
         }
@@ -162,7 +152,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
             wxe::f32x4 v[UNROLL], p[UNROLL];
 #pragma unroll
             for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off), p[i] = ld_prior(a.prior, (size_t)(k + i) * pstride + poff);
-            WX_ENS_INFLATE_LOADS_ISSUED();
+            WX_ENS_LOADS_ISSUED();
 #pragma unroll
             for (int i = 0; i < UNROLL; i++) {
               q_add(Qa[0], v[i].x, m[0]), q_add(Qa[1], v[i].y, m[1]), q_add(Qa[2], v[i].z, m[2]), q_add(Qa[3], v[i].w, m[3]);
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
             wxe::f32x4 v[UNROLL];
 #pragma unroll
             for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off);
-            WX_ENS_INFLATE_LOADS_ISSUED();
+            WX_ENS_LOADS_ISSUED();
 #pragma unroll
             for (int i = 0; i < UNROLL; i++) write(k + i, v[i]);
           }
@@ -207,7 +197,6 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
     }
   }
 }
-#undef WX_ENS_INFLATE_LOADS_ISSUED
 #endif // __HIPCC__
 
 } // namespace wxi
@@ -255,27 +244,34 @@ int wx_ensemble_prior_drop(wx_ensemble *e, int field)
   return WX_OK;
 }
 
+// The snapshot a call reads (RTPS / RTPP, WX_COV_SOURCE_PRIOR): there is one of this field, it was taken of exactly this selection, and
+// the rectangle lies inside its rectangle.
+static int ens_snapshot_for(wx_ensemble *e, const char *call, int field, const uint8_t *member_mask, int x, int y, int w, int h, const EnsPriorSlot **snap)
+{
+  const EnsPriorSlot *s = e->prior ? &e->prior->slot[field == WX_FIELD_BASE_CUR ? 0 : 1] : nullptr;
+  if (!s || !s->have) return efail(e, WX_E_STATE, "%s: no snapshot of field %d (wx_ensemble_prior_save comes first)", call, field);
+  for (int i = 0; i < (int)e->member.size(); i++)
+    if ((s->selected[(size_t)i] != 0) != (!member_mask || member_mask[i])) return efail(e, WX_E_STATE, "%s: the selection differs from the snapshot's (member %d)", call, i);
+  if (x < s->x || y < s->y || x + w > s->x + s->w || y + h > s->y + s->h)
+    return efail(e, WX_E_STATE, "%s: rect (%d,%d %dx%d) is not inside the snapshot's (%d,%d %dx%d)", call, x, y, w, h, s->x, s->y, s->w, s->h);
+  *snap = s;
+  return WX_OK;
+}
+
 int wx_ensemble_prior_save(wx_ensemble *e, int field, int x, int y, int w, int h, const uint8_t *member_mask)
 {
+  static const char *const call = "wx_ensemble_prior_save";
   if (!e) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
-  if (field != WX_FIELD_BASE_CUR && field != WX_FIELD_WATER_CUR)
-    return efail(e, WX_E_INVALID, "wx_ensemble_prior_save: field %d: WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR (the fields that are stored whole and interleaved)", field);
-  if (w <= 0 || h <= 0 || x < 0 || y < 0 || (long long)x + w > e->X || (long long)y + h > e->Y)
-    return efail(e, WX_E_RANGE, "wx_ensemble_prior_save: rect (%d,%d %dx%d) outside %dx%d (no wrap)", x, y, w, h, e->X, e->Y);
-  const int B = (int)e->member.size();
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  if (int rc = ens_check_state_field(e, call, field)) return rc;
+  if (int rc = ens_check_rect(e, call, x, y, w, h)) return rc;
+  const std::vector<int> sel = ens_select(e, member_mask);
   if (sel.empty()) return efail(e, WX_E_INVALID, "wx_ensemble_prior_save: the member mask selects nobody");
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_prior_save before wx_upload", i);
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
 
   const int n = (int)sel.size();
-  if (int rc = ens_stat_reserve(e, n, 16)) return rc;
-  EnsStatState *st = e->stat;
+  EnsCall c(e, call, K_ENS_PRIOR_SAVE);
+  if (int rc = ens_begin(c, n, 16)) return rc;
   if (!e->prior) e->prior = new EnsPriorState();
   EnsPriorSlot &s = e->prior->slot[field == WX_FIELD_BASE_CUR ? 0 : 1];
   const size_t bytes = (size_t)n * (size_t)w * (size_t)h * sizeof(float4);
@@ -289,102 +285,66 @@ int wx_ensemble_prior_save(wx_ensemble *e, int field, int x, int y, int w, int h
     }
     s.bytes = bytes;
   }
-  // the members' pointers as they are NOW (a step rotates the planes)
-  for (int k = 0; k < n; k++) {
-    const wx_sim *m = e->member[sel[k]];
-    st->tab_host[k] = wxe::Member{field == WX_FIELD_BASE_CUR ? m->base[0] : m->water[1], m->wall[0], sel[k], 0};
-  }
+  ens_table_field(c, sel, field);
+
   wxi::SaveArgs a;
   memset(&a, 0, sizeof(a));
-  a.X = e->X, a.x0 = x, a.y0 = y, a.w = w, a.h = h, a.n_sel = n, a.tab = st->tab_dev, a.out = s.buf;
-  // on the ensemble's stream, behind everything pending: table, kernel
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, (size_t)n * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    const unsigned long long items = (unsigned long long)((w + 63) / 64) * (unsigned)h * (unsigned)n;
-    const unsigned wgs = (unsigned)std::min<unsigned long long>((items + wxi::WAVES - 1) / wxi::WAVES, wxi::SAVE_MAX_WGS);
-    {
-      ProfScope ps(e->member[0], K_ENS_PRIOR_SAVE); // (wx_profile on member 0 sees the launch, whoever is selected)
-      hipLaunchKernelGGL(wxi::k_ens_prior_save, dim3(wgs), dim3(wxi::WG), 0, e->stream, a);
-    }
-    he = hipGetLastError();
+  a.X = e->X, a.x0 = x, a.y0 = y, a.w = w, a.h = h, a.n_sel = n, a.tab = c.st->tab_dev, a.out = s.buf;
+  const unsigned wgs = ens_wgs_wave_per_item((unsigned long long)ens_chunks(w, h) * (unsigned)n, wxi::WAVES, wxi::SAVE_MAX_WGS);
+  ens_launch(c, K_ENS_PRIOR_SAVE, [&] { hipLaunchKernelGGL(wxi::k_ens_prior_save, dim3(wgs), dim3(wxi::WG), 0, e->stream, a); });
+  if (c.he == hipSuccess) { // (the snapshot stands once its kernel is enqueued, whatever the sync hands on about a member)
+    s.have = true, s.x = x, s.y = y, s.w = w, s.h = h;
+    s.selected.assign(e->member.size(), 0);
+    for (int i : sel) s.selected[(size_t)i] = 1;
   }
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_prior_save (%s): %s", kKernelNames[K_ENS_PRIOR_SAVE], hipGetErrorString(he));
-  }
-  s.have = true, s.x = x, s.y = y, s.w = w, s.h = h;
-  s.selected.assign((size_t)B, 0);
-  for (int i : sel) s.selected[(size_t)i] = 1;
-  // blocking like wx_ensemble_statistics, and like it a place where every member's pending report is looked at and consumed
-  return wx_ensemble_sync(e);
+  return ens_finish(c);
 }
 
 int wx_ensemble_inflate(wx_ensemble *e, const wx_ens_inflate *p, const uint8_t *member_mask)
 {
+  static const char *const call = "wx_ensemble_inflate";
   if (!e || !p) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
   const char *why;
   if (int rc = wxi::check_desc(p, &why)) return efail(e, rc, "wx_ensemble_inflate: %s", why);
-  const int B = (int)e->member.size();
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  const std::vector<int> sel = ens_select(e, member_mask);
   if (sel.size() < 2) return efail(e, WX_E_INVALID, "wx_ensemble_inflate: the member mask selects %zu member(s); a spread takes two", sel.size());
   if (int rc = wxi::check_rect(p, e->X, e->Y, &why)) return efail(e, rc, "wx_ensemble_inflate: %s", why);
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_inflate before wx_upload", i);
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
   const bool relax = p->mode != WX_INFLATE_CONST;
   const EnsPriorSlot *snap = nullptr;
-  if (relax) {
-    snap = e->prior ? &e->prior->slot[p->field == WX_FIELD_BASE_CUR ? 0 : 1] : nullptr;
-    if (!snap || !snap->have) return efail(e, WX_E_STATE, "wx_ensemble_inflate: no snapshot of field %d (wx_ensemble_prior_save comes first)", p->field);
-    for (int i = 0; i < B; i++)
-      if ((snap->selected[(size_t)i] != 0) != (!member_mask || member_mask[i]))
-        return efail(e, WX_E_STATE, "wx_ensemble_inflate: the selection differs from the snapshot's (member %d)", i);
-    if (p->x < snap->x || p->y < snap->y || p->x + p->w > snap->x + snap->w || p->y + p->h > snap->y + snap->h)
-      return efail(e, WX_E_STATE, "wx_ensemble_inflate: rect (%d,%d %dx%d) is not inside the snapshot's (%d,%d %dx%d)", p->x, p->y, p->w, p->h, snap->x, snap->y, snap->w,
-                   snap->h);
-  }
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
+  if (relax)
+    if (int rc = ens_snapshot_for(e, call, p->field, member_mask, p->x, p->y, p->w, p->h, &snap)) return rc;
 
   const int n = (int)sel.size();
   const size_t lam_bytes = p->lambda_out ? (size_t)p->w * (size_t)p->h * sizeof(float4) : 0;
-  if (int rc = ens_stat_reserve(e, n, std::max<size_t>(lam_bytes, 16))) return rc;
-  EnsStatState *st = e->stat;
-  for (int k = 0; k < n; k++) {
-    wx_sim *m = e->member[sel[k]];
-    if (int rc = epass(e, sel[k], ens_perturb_prepare(m, p->field))) return rc;
-    st->tab_host[k] = wxe::Member{p->field == WX_FIELD_BASE_CUR ? m->base[0] : m->water[1], m->wall[0], sel[k], 0};
-  }
+  EnsCall c(e, call, K_ENS_INFLATE);
+  if (int rc = ens_begin(c, n, std::max<size_t>(lam_bytes, 16))) return rc;
+  EnsStage *st = c.st;
+  for (int i : sel)
+    if (int rc = epass(e, i, ens_perturb_prepare(e->member[i], p->field))) return rc;
+  ens_table_field(c, sel, p->field);
+
   wxi::Args a;
   memset(&a, 0, sizeof(a));
   a.X = e->X, a.x0 = p->x, a.y0 = p->y, a.w = p->w, a.h = p->h, a.n_sel = n;
-  for (int c = 0; c < 4; c++) a.on[c] = wxi::neutral(p->mode, p->coef[c]) ? 0 : 1, a.coef[c] = p->coef[c], a.lo[c] = p->lo[c], a.hi[c] = p->hi[c];
+  for (int ch = 0; ch < 4; ch++) a.on[ch] = wxi::neutral(p->mode, p->coef[ch]) ? 0 : 1, a.coef[ch] = p->coef[ch], a.lo[ch] = p->lo[ch], a.hi[ch] = p->hi[ch];
   a.lam_lo = p->lambda_lo, a.lam_hi = p->lambda_hi;
   a.tab = st->tab_dev;
   if (relax) a.prior = snap->buf, a.px0 = snap->x, a.py0 = snap->y, a.pw = snap->w, a.ph = snap->h;
   a.lambda_out = lam_bytes ? (float4 *)st->out_dev : nullptr;
-  // on the ensemble's stream, behind everything pending: table, kernel, the map to the pinned copy
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, (size_t)n * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    const unsigned chunks = (unsigned)((p->w + 63) / 64) * (unsigned)p->h;
-    const unsigned wgs = std::min<unsigned>((chunks + wxi::WAVES - 1) / wxi::WAVES, wxi::MAX_WGS);
-    {
-      ProfScope ps(e->member[0], K_ENS_INFLATE); // (wx_profile on member 0 sees the launch, whoever is selected)
-      if (p->mode == WX_INFLATE_CONST) hipLaunchKernelGGL(wxi::k_ens_inflate<WX_INFLATE_CONST>, dim3(wgs), dim3(wxi::WG), 0, e->stream, a);
-      else if (p->mode == WX_INFLATE_RTPS) hipLaunchKernelGGL(wxi::k_ens_inflate<WX_INFLATE_RTPS>, dim3(wgs), dim3(wxi::WG), 0, e->stream, a);
-      else hipLaunchKernelGGL(wxi::k_ens_inflate<WX_INFLATE_RTPP>, dim3(wgs), dim3(wxi::WG), 0, e->stream, a);
-    }
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess && lam_bytes) he = hipMemcpyAsync(st->out_host, st->out_dev, lam_bytes, hipMemcpyDeviceToHost, e->stream);
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_inflate (%s): %s", kKernelNames[K_ENS_INFLATE], hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_perturb, and like it a place where every member's pending report is looked at and consumed
-  const int rc = wx_ensemble_sync(e);
-  if (lam_bytes) memcpy(p->lambda_out, st->out_host, lam_bytes);
+
+  // behind the table: kernel, the map to the pinned copy
+  const dim3 grid(ens_wgs_wave_per_item(ens_chunks(p->w, p->h), wxi::WAVES, wxi::MAX_WGS)), wg(wxi::WG);
+  ens_launch(c, K_ENS_INFLATE, [&] {
+    if (p->mode == WX_INFLATE_CONST) hipLaunchKernelGGL(wxi::k_ens_inflate<WX_INFLATE_CONST>, grid, wg, 0, e->stream, a);
+    else if (p->mode == WX_INFLATE_RTPS) hipLaunchKernelGGL(wxi::k_ens_inflate<WX_INFLATE_RTPS>, grid, wg, 0, e->stream, a);
+    else hipLaunchKernelGGL(wxi::k_ens_inflate<WX_INFLATE_RTPP>, grid, wg, 0, e->stream, a);
+  });
+  if (c.he == hipSuccess && lam_bytes) c.he = hipMemcpyAsync(st->out_host, st->out_dev, lam_bytes, hipMemcpyDeviceToHost, e->stream);
+  const int rc = ens_finish(c);
+  // The members are changed by now, so the map of what was applied goes back even when the sync hands on a member's pending report:
+  // the report is about that member, not about this call. Not after a failed enqueue.
+  if (c.he == hipSuccess && lam_bytes) memcpy(p->lambda_out, st->out_host, lam_bytes);
   return rc;
 }

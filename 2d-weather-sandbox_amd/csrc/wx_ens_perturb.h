@@ -12,7 +12,7 @@
 //
 // The kernel: one lane per cell, the 64 lanes of a wave take 64 consecutive x of one row; per lane and member one 16-byte load of the
 // field's texel, the 4-byte wall texel, one 16-byte store -- 36 B per member-cell. Waves grid-stride over the (member, row, 64-column
-// chunk) triples with a capped grid. The selected members' {field, wall, index} triples come from the device table of wx_ens_stat.h
+// chunk) triples with a capped grid. The selected members' {field, wall, index} triples come from the device table of wx_ens_frame.h
 // (wxe::Member), read through the constant address space at wave-uniform addresses. The node values -- up to four integer hash chains
 // of four hashes per channel -- are computed between the loads and the store; a channel with amplitude 0 computes none. No LDS, no
 // atomics; lanes outside the rectangle and cells that are left alone do not store.
@@ -21,7 +21,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/wxsim.h"
-#include "wx_ens_stat.h"
+#include "wx_ens_frame.h"
 #include "wx_ens_perturb_cell.h"
 
 namespace wxp {
@@ -37,12 +37,6 @@ struct Args {
 enum { WG = 256, WAVES = WG / 64, MAX_WGS = 4096 };
 
 #if defined(__HIPCC__)
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __forceinline__ void st_field(wxe::CTab m, size_t off, wxe::f32x4 v) { ((__attribute__((address_space(1))) wxe::f32x4 *)(unsigned long long)m->field)[off] = v; }
-#else // host pass of the single-source compile: same meaning, never executed
-__device__ __forceinline__ void st_field(wxe::CTab m, size_t off, wxe::f32x4 v) { const_cast<float4 *>(m->field)[off] = make_float4(v.x, v.y, v.z, v.w); }
-#endif
-
 __global__ __launch_bounds__(WG) void k_ens_perturb(const Args a)
 {
   const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
@@ -94,45 +88,28 @@ static int ens_perturb_prepare(wx_sim *m, int field)
 
 int wx_ensemble_perturb(wx_ensemble *e, const wx_ens_perturb *p, const uint8_t *member_mask)
 {
+  static const char *const call = "wx_ensemble_perturb";
   if (!e || !p) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
   const char *why;
   if (int rc = wxp::check_desc(p, e->X, e->Y, &why)) return efail(e, rc, "wx_ensemble_perturb: %s", why);
-  const int B = (int)e->member.size();
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  const std::vector<int> sel = ens_select(e, member_mask);
   if (sel.empty()) return efail(e, WX_E_INVALID, "wx_ensemble_perturb: the member mask selects nobody");
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
+
+  EnsCall c(e, call, K_ENS_PERTURB);
+  if (int rc = ens_begin(c, (int)sel.size(), 16)) return rc;
   for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_perturb before wx_upload", i);
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
-  if (int rc = ens_stat_reserve(e, (int)sel.size(), 16)) return rc;
-  EnsStatState *st = e->stat;
-  for (size_t k = 0; k < sel.size(); k++) {
-    wx_sim *m = e->member[sel[k]];
-    if (int rc = epass(e, sel[k], ens_perturb_prepare(m, p->field))) return rc;
-    st->tab_host[k] = wxe::Member{p->field == WX_FIELD_BASE_CUR ? m->base[0] : m->water[1], m->wall[0], sel[k], 0};
-  }
+    if (int rc = epass(e, i, ens_perturb_prepare(e->member[i], p->field))) return rc;
+  ens_table_field(c, sel, p->field);
+
   wxp::Args a;
   memset(&a, 0, sizeof(a));
   a.X = e->X, a.x0 = p->x, a.y0 = p->y, a.w = p->w, a.h = p->h, a.n_sel = (int)sel.size();
-  a.tab = st->tab_dev;
+  a.tab = c.st->tab_dev;
   a.noise = wxp::noise_of(*p, e->X);
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, sel.size() * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    const unsigned long long items = (unsigned long long)((p->w + 63) / 64) * (unsigned)p->h * sel.size();
-    const unsigned wgs = (unsigned)std::min<unsigned long long>((items + wxp::WAVES - 1) / wxp::WAVES, wxp::MAX_WGS);
-    {
-      ProfScope ps(e->member[0], K_ENS_PERTURB); // (wx_profile on member 0 sees the launch, whoever is selected)
-      hipLaunchKernelGGL(wxp::k_ens_perturb, dim3(wgs), dim3(wxp::WG), 0, e->stream, a);
-    }
-    he = hipGetLastError();
-  }
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_perturb (%s): %s", kKernelNames[K_ENS_PERTURB], hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_statistics, and like it a place where every member's pending report is looked at and consumed
-  return wx_ensemble_sync(e);
+
+  const unsigned wgs = ens_wgs_wave_per_item((unsigned long long)ens_chunks(p->w, p->h) * sel.size(), wxp::WAVES, wxp::MAX_WGS);
+  ens_launch(c, K_ENS_PERTURB, [&] { hipLaunchKernelGGL(wxp::k_ens_perturb, dim3(wgs), dim3(wxp::WG), 0, e->stream, a); });
+  return ens_finish(c);
 }

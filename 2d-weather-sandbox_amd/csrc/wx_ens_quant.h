@@ -11,7 +11,7 @@
 // chunk of 64 consecutive x of one row (the chunk of k_ens_stat), workgroups grid-stride over the chunks; lane = cell, wave c = channel c.
 //   1. Staging. Wave w loads members w, w + 4, ... -- a member's float4 texel (16 B per lane, 1 KiB per wave, contiguous) and its
 //      wall texel, all of the wave's P / 4 members in flight at once (at most 8: 32 per workgroup), through the device table of {field,
-//      wall, index} (wx_ens_stat.h: constant address space, scalar loads) -- and writes the four keys to dynamic LDS as
+//      wall, index} (wx_ens_frame.h: constant address space, scalar loads) -- and writes the four keys to dynamic LDS as
 //      [member][channel][lane]: 1 KiB per member. Members past the selection and lanes beyond the rectangle's right edge get KEY_PAD.
 //   2. __syncthreads(). From here on wave c owns channel c: thread (c, lane) reads and writes ONLY the addresses [i][c][lane], its own
 //      column (bank = lane: conflict-free), so nothing below needs a barrier until the results are exchanged. The column goes into P
@@ -40,7 +40,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/wxsim.h"
-#include "wx_ens_stat.h"
+#include "wx_ens_frame.h"
 #include "wx_ens_quant_cell.h"
 
 namespace wxq {
@@ -66,13 +66,6 @@ struct Args {
 };
 
 #if defined(__HIPCC__)
-#if defined(__HIP_DEVICE_COMPILE__)
-// channel c of a member's texel (the streaming kernel and the rank member)
-__device__ __forceinline__ float ld_chan(wxe::CTab m, size_t off, unsigned c) { return ((const __attribute__((address_space(1))) float *)(unsigned long long)m->field)[4 * off + c]; }
-#else // host pass of the single-source compile: same meaning, never executed
-__device__ __forceinline__ float ld_chan(wxe::CTab m, size_t off, unsigned c) { return ((const float *)m->field)[4 * off + c]; }
-#endif
-
 // What k_ens_quant_staged<P> and k_ens_score<P> (wx_ens_score.h) share: the staging of one chunk's keys into the LDS image and the
 // register sort of a thread's column. P: the selection padded to a power of two, a template parameter so that a column's keys live in
 // registers with constant indices.
@@ -268,24 +261,17 @@ int wx_ens_quant_cells(int n_members, size_t n_cells, const float *const *field,
 
 int wx_ensemble_quantiles(wx_ensemble *e, int field, int x, int y, int w, int h, const uint8_t *member_mask, wx_ens_quant *out)
 {
+  static const char *const call = "wx_ensemble_quantiles";
   if (!e || !out) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
-  if (field != WX_FIELD_BASE_CUR && field != WX_FIELD_WATER_CUR)
-    return efail(e, WX_E_INVALID, "wx_ensemble_quantiles: field %d: WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR (the fields that are stored whole and interleaved)", field);
-  const int B = (int)e->member.size();
+  if (int rc = ens_check_state_field(e, call, field)) return rc;
   const char *why;
-  if (int rc = wxq::check_desc(out, B, member_mask, &why)) return efail(e, rc, "wx_ensemble_quantiles: %s", why);
-  if (w <= 0 || h <= 0 || x < 0 || y < 0 || (long long)x + w > e->X || (long long)y + h > e->Y)
-    return efail(e, WX_E_RANGE, "wx_ensemble_quantiles: rect (%d,%d %dx%d) outside %dx%d (no wrap)", x, y, w, h, e->X, e->Y);
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_quantiles before wx_upload", i);
+  if (int rc = wxq::check_desc(out, (int)e->member.size(), member_mask, &why)) return efail(e, rc, "wx_ensemble_quantiles: %s", why);
+  if (int rc = ens_check_rect(e, call, x, y, w, h)) return rc;
+  const std::vector<int> sel = ens_select(e, member_mask);
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
   const int rank = out->rank_member;
   if (rank >= 0 && !e->member[rank]->uploaded) return efail(e, WX_E_STATE, "member %d (rank_member): wx_ensemble_quantiles before wx_upload", rank);
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
 
   // the wanted planes back to back: q (n_q of them), count, n_below, n_equal, n_wall
   const size_t cells = (size_t)w * h;
@@ -297,16 +283,13 @@ int wx_ensemble_quantiles(wx_ensemble *e, int field, int x, int y, int w, int h,
     if (host_ptr[p]) out_bytes += bytes[p];
   }
   const int n_sel = (int)sel.size();
-  if (int rc = ens_stat_reserve(e, n_sel + 1, std::max<size_t>(out_bytes, 16))) return rc;
-  EnsStatState *st = e->stat;
+  EnsCall c(e, call, K_ENS_QUANT);
+  if (int rc = ens_begin(c, n_sel + 1, std::max<size_t>(out_bytes, 16))) return rc;
+  EnsStage *st = c.st;
+  // the rank member behind the selected ones (without one: an entry that is not looked at)
+  const int behind = rank >= 0 ? rank : sel[0];
+  ens_table_field(c, sel, field, e->member[behind], behind);
 
-  // the members' pointers as they are NOW (a step rotates the planes), the rank member behind the selected ones
-  auto entry = [&](int i) {
-    const wx_sim *m = e->member[i];
-    return wxe::Member{field == WX_FIELD_BASE_CUR ? m->base[0] : m->water[1], m->wall[0], i, 0};
-  };
-  for (int k = 0; k < n_sel; k++) st->tab_host[k] = entry(sel[k]);
-  st->tab_host[n_sel] = entry(rank >= 0 ? rank : sel[0]);
   wxq::Args a;
   memset(&a, 0, sizeof(a));
   a.X = e->X, a.x0 = x, a.y0 = y, a.w = w, a.h = h, a.n_sel = n_sel;
@@ -320,35 +303,24 @@ int wx_ensemble_quantiles(wx_ensemble *e, int field, int x, int y, int w, int h,
   a.P = 1;
   while (staged && a.P < n_sel) a.P <<= 1;
 
-  // on the ensemble's stream, behind everything pending: table, kernel, planes to the pinned copy
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, (size_t)(n_sel + 1) * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    const unsigned chunks = (unsigned)((w + 63) / 64) * (unsigned)h;
-    ProfScope ps(e->member[0], K_ENS_QUANT); // (wx_profile on member 0 sees the launch, whoever is selected)
-    if (staged) {
-      const size_t lds = (size_t)std::max<int>(a.P, wxq::RESULT_ROWS) * 1024;
-      const dim3 grid(std::min<unsigned>(chunks, wxq::MAX_WGS));
+  // behind the table: kernel, planes to the pinned copy
+  const dim3 grid(ens_wgs_wg_per_item(ens_chunks(w, h), wxq::MAX_WGS)), wg(wxq::WG); // (the streaming kernel: chunks x 4 waves)
+  ens_launch(c, K_ENS_QUANT, [&] {
+    const size_t lds = (size_t)std::max<int>(a.P, wxq::RESULT_ROWS) * 1024;
+    if (!staged) hipLaunchKernelGGL(wxq::k_ens_quant_stream, grid, wg, 0, e->stream, a);
+    else
       switch (a.P) {
-      case 1: hipLaunchKernelGGL(wxq::k_ens_quant_staged<1>, grid, dim3(wxq::WG), lds, e->stream, a); break;
-      case 2: hipLaunchKernelGGL(wxq::k_ens_quant_staged<2>, grid, dim3(wxq::WG), lds, e->stream, a); break;
-      case 4: hipLaunchKernelGGL(wxq::k_ens_quant_staged<4>, grid, dim3(wxq::WG), lds, e->stream, a); break;
-      case 8: hipLaunchKernelGGL(wxq::k_ens_quant_staged<8>, grid, dim3(wxq::WG), lds, e->stream, a); break;
-      case 16: hipLaunchKernelGGL(wxq::k_ens_quant_staged<16>, grid, dim3(wxq::WG), lds, e->stream, a); break;
-      case 32: hipLaunchKernelGGL(wxq::k_ens_quant_staged<32>, grid, dim3(wxq::WG), lds, e->stream, a); break;
-      default: hipLaunchKernelGGL(wxq::k_ens_quant_staged<wxq::STAGED_MEMBERS>, grid, dim3(wxq::WG), lds, e->stream, a); break;
+      case 1: hipLaunchKernelGGL(wxq::k_ens_quant_staged<1>, grid, wg, lds, e->stream, a); break;
+      case 2: hipLaunchKernelGGL(wxq::k_ens_quant_staged<2>, grid, wg, lds, e->stream, a); break;
+      case 4: hipLaunchKernelGGL(wxq::k_ens_quant_staged<4>, grid, wg, lds, e->stream, a); break;
+      case 8: hipLaunchKernelGGL(wxq::k_ens_quant_staged<8>, grid, wg, lds, e->stream, a); break;
+      case 16: hipLaunchKernelGGL(wxq::k_ens_quant_staged<16>, grid, wg, lds, e->stream, a); break;
+      case 32: hipLaunchKernelGGL(wxq::k_ens_quant_staged<32>, grid, wg, lds, e->stream, a); break;
+      default: hipLaunchKernelGGL(wxq::k_ens_quant_staged<wxq::STAGED_MEMBERS>, grid, wg, lds, e->stream, a); break;
       }
-    } else {
-      hipLaunchKernelGGL(wxq::k_ens_quant_stream, dim3(std::min<unsigned>(chunks, wxq::MAX_WGS)), dim3(wxq::WG), 0, e->stream, a); // (chunks x 4 waves)
-    }
-  }
-  if (he == hipSuccess) he = hipGetLastError();
-  if (he == hipSuccess && out_bytes) he = hipMemcpyAsync(st->out_host, st->out_dev, out_bytes, hipMemcpyDeviceToHost, e->stream);
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_quantiles (%s): %s", kKernelNames[K_ENS_QUANT], hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_sync, and like it a place where every member's pending report is looked at and consumed
-  if (int rc = wx_ensemble_sync(e)) return rc;
+  });
+  if (c.he == hipSuccess && out_bytes) c.he = hipMemcpyAsync(st->out_host, st->out_dev, out_bytes, hipMemcpyDeviceToHost, e->stream);
+  if (int rc = ens_finish(c)) return rc;
   for (int p = 0; p < 5; p++)
     if (host_ptr[p]) memcpy(host_ptr[p], st->out_host + at[p], bytes[p]);
   return WX_OK;

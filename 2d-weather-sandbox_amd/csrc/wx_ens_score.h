@@ -203,28 +203,23 @@ int wx_ens_score_cells(int n_members, size_t n_cells, const float *const *field,
 
 int wx_ensemble_scores(wx_ensemble *e, wx_sim *truth, int field, int x, int y, int w, int h, const uint8_t *member_mask, wx_ens_score *out)
 {
+  static const char *const call = "wx_ensemble_scores";
   if (!e || !truth || !out) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
-  if (field != WX_FIELD_BASE_CUR && field != WX_FIELD_WATER_CUR)
-    return efail(e, WX_E_INVALID, "wx_ensemble_scores: field %d: WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR (the fields that are stored whole and interleaved)", field);
-  const int B = (int)e->member.size();
+  if (int rc = ens_check_state_field(e, call, field)) return rc;
   const char *why;
-  if (int rc = wxs::check_selection(B, member_mask, &why)) return efail(e, rc, "wx_ensemble_scores: %s", why);
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  if (int rc = wxs::check_selection((int)e->member.size(), member_mask, &why)) return efail(e, rc, "wx_ensemble_scores: %s", why);
+  const std::vector<int> sel = ens_select(e, member_mask);
   for (int i : sel)
     if (e->member[i] == truth) return efail(e, WX_E_INVALID, "wx_ensemble_scores: truth is member %d, which is selected: the truth does not enter (mask it out)", i);
   if (truth->halo != 0 || truth->X != truth->Xg) return efail(e, WX_E_INVALID, "wx_ensemble_scores: truth is a slab handle (whole-domain handles only)");
   if (truth->X != e->X || truth->Y != e->Y) return efail(e, WX_E_INVALID, "wx_ensemble_scores: truth has %d x %d cells, the members %d x %d", truth->X, truth->Y, e->X, e->Y);
   if (truth->device != e->device) return efail(e, WX_E_INVALID, "wx_ensemble_scores: truth lives on device %d, the ensemble on device %d", truth->device, e->device);
-  if (w <= 0 || h <= 0 || x < 0 || y < 0 || (long long)x + w > e->X || (long long)y + h > e->Y)
-    return efail(e, WX_E_RANGE, "wx_ensemble_scores: rect (%d,%d %dx%d) outside %dx%d (no wrap)", x, y, w, h, e->X, e->Y);
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_scores before wx_upload", i);
+  if (int rc = ens_check_rect(e, call, x, y, w, h)) return rc;
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
   if (!truth->uploaded) return efail(e, WX_E_STATE, "truth: wx_ensemble_scores before wx_upload");
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
+  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept; in front of the wait for truth)
+  EnsCall c(e, call, K_ENS_SCORE);
 
   // behind everything pending on truth's stream, as wx_copy_state orders its two handles: truth's pending report is consumed and
   // returned here, and then nothing is launched (a member of this ensemble is on the ensemble's stream: wx_ensemble_sync below)
@@ -240,13 +235,10 @@ int wx_ensemble_scores(wx_ensemble *e, wx_sim *truth, int field, int x, int y, i
     if (host_ptr[p]) out_bytes += cells * 16;
   }
   const int n_sel = (int)sel.size();
-  if (int rc = ens_stat_reserve(e, n_sel + 1, out_bytes)) return rc;
-  EnsStatState *st = e->stat;
+  if (int rc = ens_begin(c, n_sel + 1, out_bytes)) return rc;
+  EnsStage *st = c.st;
+  ens_table_field(c, sel, field, truth, -1); // the truth behind the selected ones
 
-  // the members' pointers as they are NOW (a step rotates the planes), the truth behind the selected ones
-  auto entry = [&](const wx_sim *m, int i) { return wxe::Member{field == WX_FIELD_BASE_CUR ? m->base[0] : m->water[1], m->wall[0], i, 0}; };
-  for (int k = 0; k < n_sel; k++) st->tab_host[k] = entry(e->member[sel[k]], sel[k]);
-  st->tab_host[n_sel] = entry(truth, -1);
   wxs::Args a;
   memset(&a, 0, sizeof(a));
   a.X = e->X, a.x0 = x, a.y0 = y, a.w = w, a.h = h, a.n_sel = n_sel;
@@ -257,30 +249,22 @@ int wx_ensemble_scores(wx_ensemble *e, wx_sim *truth, int field, int x, int y, i
   int P = 1;
   while (P < n_sel) P <<= 1;
 
-  // on the ensemble's stream, behind everything pending: table of members, zeroed table of sums, kernel, everything to the pinned copy
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, (size_t)(n_sel + 1) * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) he = hipMemsetAsync(st->out_dev, 0, table_bytes, e->stream);
-  if (he == hipSuccess) {
-    const unsigned chunks = (unsigned)((w + 63) / 64) * (unsigned)h;
-    const unsigned wgs = std::min<unsigned>(chunks, wxs::MAX_WGS);
-    ProfScope ps(e->member[0], K_ENS_SCORE); // (wx_profile on member 0 sees the launch, whoever is selected)
+  // behind the table of members: the zeroed table of sums, kernel, everything to the pinned copy
+  if (c.he == hipSuccess) c.he = hipMemsetAsync(st->out_dev, 0, table_bytes, e->stream);
+  const unsigned wgs = ens_wgs_wg_per_item(ens_chunks(w, h), wxs::MAX_WGS);
+  ens_launch(c, K_ENS_SCORE, [&]() -> hipError_t {
     switch (P) {
-    case 1: he = wxs::launch<1>(a, wgs, e->stream); break;
-    case 2: he = wxs::launch<2>(a, wgs, e->stream); break;
-    case 4: he = wxs::launch<4>(a, wgs, e->stream); break;
-    case 8: he = wxs::launch<8>(a, wgs, e->stream); break;
-    case 16: he = wxs::launch<16>(a, wgs, e->stream); break;
-    case 32: he = wxs::launch<32>(a, wgs, e->stream); break;
-    default: he = wxs::launch<wxs::MAX_MEMBERS>(a, wgs, e->stream); break;
+    case 1: return wxs::launch<1>(a, wgs, e->stream);
+    case 2: return wxs::launch<2>(a, wgs, e->stream);
+    case 4: return wxs::launch<4>(a, wgs, e->stream);
+    case 8: return wxs::launch<8>(a, wgs, e->stream);
+    case 16: return wxs::launch<16>(a, wgs, e->stream);
+    case 32: return wxs::launch<32>(a, wgs, e->stream);
+    default: return wxs::launch<wxs::MAX_MEMBERS>(a, wgs, e->stream);
     }
-  }
-  if (he == hipSuccess) he = hipMemcpyAsync(st->out_host, st->out_dev, out_bytes, hipMemcpyDeviceToHost, e->stream);
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_scores (%s): %s", kKernelNames[K_ENS_SCORE], hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_sync, and like it a place where every member's pending report is looked at and consumed
-  if (int rc = wx_ensemble_sync(e)) return rc;
+  });
+  if (c.he == hipSuccess) c.he = hipMemcpyAsync(st->out_host, st->out_dev, out_bytes, hipMemcpyDeviceToHost, e->stream);
+  if (int rc = ens_finish(c)) return rc;
   wxs::Acc *acc = new wxs::Acc();
   wxs::acc_from_table((const wxs::u64 *)st->out_host, *acc);
   wxs::acc_finish(*acc, out);

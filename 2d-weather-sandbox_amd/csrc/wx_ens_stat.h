@@ -1,7 +1,7 @@
 // wx_ens_stat.h -- statistics over the MEMBER axis of an ensemble (include/wxsim.h: wx_ens_stat, wx_ensemble_statistics,
 // wx_ens_stat_cells): per cell and channel of a rectangle the mean, population variance, extremes with the member that holds them, the
 // number of values that entered, the number above a threshold, and per cell the number of members in which it is a wall cell. Included
-// at the end of wxsim.hip, behind wx_ensemble.h (the entry points are declared extern "C" by include/wxsim.h). What wx_diag.h does for
+// at the end of wxsim.hip, behind wx_ens_frame.h (the entry points are declared extern "C" by include/wxsim.h). What wx_diag.h does for
 // the space axis this does for the member axis -- with one difference that the header comment states: the sums are NOT exact sums but
 // sums IN MEMBER ORDER, one double addition per entered value (a 320-bit accumulator per cell and channel would cost more than the
 // fields it summarises), so the definition fixes the order and every implementation of it -- k_ens_stat, wx_ens_stat_cells, the
@@ -22,8 +22,8 @@
 // latency is to have the loads of UNROLL members in flight before the first is consumed: the loop body loads UNROLL members into
 // registers, then consumes them in order (the compiler's counted s_waitcnt vmcnt(N) in front of each consumer), with a one-by-one
 // remainder. Pass 1: sum, count, extremes, exceedance, walls. Pass 2 (only if the variance is wanted): the members again for
-// Q = sum (v - mean)^2. The members' {field, wall, index} triples come from a device table read through the constant address space
-// (wave-uniform addresses: scalar loads). Only the wanted planes are written, with 16-byte (n_wall: 4-byte) vector stores; nothing
+// Q = sum (v - mean)^2. The members' {field, wall, index} triples come from the ensemble's device table (wx_ens_frame.h: constant address
+// space, wave-uniform addresses: scalar loads). Only the wanted planes are written, with 16-byte (n_wall: 4-byte) vector stores; nothing
 // else is written, no atomics, no LDS. profiles/ensemble_statistics_isa.txt records the loads and waits of one gfx950 build.
 // What it does not try: a w x h rectangle is ceil(w / 64) * h waves whatever the number of members (100 x 100: 200 waves on a chip
 // with 1024 SIMDs). Splitting one cell's members over lanes would change the defined order of summation.
@@ -36,6 +36,7 @@
 #include "../../include/wxsim.h"
 #include "wx_diag.h"
 #include "wx_rounded.h"
+#include "wx_ens_frame.h"
 
 namespace wxe {
 
@@ -131,13 +132,6 @@ __host__ __device__ inline float variance_of(const Spread &s, const Cell &a, int
 // a zero extreme is +0.0
 __host__ __device__ inline float extreme_of(float e, int n) { return n ? (e == 0.0f ? 0.0f : e) : __builtin_nanf(""); }
 
-// a selected member, as the kernel sees it
-struct Member {
-  const float4 *field;
-  const char4 *wall;
-  int index, pad;
-};
-
 struct Args {
   int X;              // cells per row of the members' arrays
   int x0, y0, w, h;   // the rectangle
@@ -153,31 +147,6 @@ struct Args {
 enum { WG = 256, WAVES = WG / 64, MAX_WGS = 2048, UNROLL = 8 };
 
 #if defined(__HIPCC__)
-// One member's texel. The table is read through the constant address space (as k_march_wet_ens reads its slots: scalar loads, the entry
-// index is wave-uniform), and the pointers it holds are turned into global-address-space pointers by an integer round trip -- a pointer
-// loaded from memory is otherwise a generic one, whose loads may become flat loads that count on both wait counters. The table holds
-// hipMalloc'ed addresses only, so the cast states a fact. (The record under profiles/: global_load only, the table by s_load.)
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef const __attribute__((address_space(4))) Member *CTab;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ CTab const_table(const Member *tab) { return (CTab)(unsigned long long)tab; }
-__device__ __forceinline__ f32x4 ld_field(CTab m, size_t off) { return ((const __attribute__((address_space(1))) f32x4 *)(unsigned long long)m->field)[off]; }
-// (the whole 4-byte wall texel; only "is channel 1 zero" is looked at)
-__device__ __forceinline__ int ld_wall_dist(CTab m, size_t off) { return (((const __attribute__((address_space(1))) unsigned *)(unsigned long long)m->wall)[off] >> 8) & 0xFF; }
-// between a group's loads and its consumers: the instruction scheduler moves nothing across (it is otherwise free to interleave the
-// loads with the consumers to save registers -- one round trip per member again)
-#define WX_ENS_STAT_LOADS_ISSUED() __builtin_amdgcn_sched_barrier(0)
-#else // host pass of the single-source compile: same meaning, never executed
-typedef const Member *CTab;
-struct f32x4 {
-  float x, y, z, w;
-};
-__device__ __forceinline__ CTab const_table(const Member *tab) { return tab; }
-__device__ __forceinline__ f32x4 ld_field(CTab m, size_t off) { return f32x4{m->field[off].x, m->field[off].y, m->field[off].z, m->field[off].w}; }
-__device__ __forceinline__ int ld_wall_dist(CTab m, size_t off) { return m->wall[off].y; }
-#define WX_ENS_STAT_LOADS_ISSUED() ((void)0)
-#endif
-
 __global__ __launch_bounds__(WG) void k_ens_stat(const Args a)
 {
   const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
@@ -196,7 +165,7 @@ __global__ __launch_bounds__(WG) void k_ens_stat(const Args a)
       int wd[UNROLL];
 #pragma unroll
       for (int j = 0; j < UNROLL; j++) v[j] = ld_field(tab + k + j, off), wd[j] = ld_wall_dist(tab + k + j, off);
-      WX_ENS_STAT_LOADS_ISSUED();
+      WX_ENS_LOADS_ISSUED();
 #pragma unroll
       for (int j = 0; j < UNROLL; j++) {
         const float f[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
@@ -217,7 +186,7 @@ __global__ __launch_bounds__(WG) void k_ens_stat(const Args a)
         int wd[UNROLL];
 #pragma unroll
         for (int j = 0; j < UNROLL; j++) v[j] = ld_field(tab + k + j, off), wd[j] = ld_wall_dist(tab + k + j, off);
-        WX_ENS_STAT_LOADS_ISSUED();
+        WX_ENS_LOADS_ISSUED();
 #pragma unroll
         for (int j = 0; j < UNROLL; j++) {
           const float f[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
@@ -243,7 +212,6 @@ __global__ __launch_bounds__(WG) void k_ens_stat(const Args a)
     if (a.n_wall) a.n_wall[o] = cell.n_wall;
   }
 }
-#undef WX_ENS_STAT_LOADS_ISSUED
 #endif // __HIPCC__
 
 // the nine planes of wx_ens_stat in the order of the struct: bytes per cell, and the caller's pointer
@@ -302,56 +270,6 @@ inline int stat_cells(int n_members, size_t n_cells, const float *const *field, 
 
 } // namespace wxe
 
-// ---- the ensemble's side: the device table of the selected members, the output planes and their pinned copies ----
-struct EnsStatState {
-  wxe::Member *tab_host = nullptr, *tab_dev = nullptr; // pinned staging + device table, tab_cap entries
-  int tab_cap = 0;
-  char *out_dev = nullptr, *out_host = nullptr;         // the wanted planes of one call back to back, out_cap bytes
-  size_t out_cap = 0;
-};
-
-static void ens_stat_release(wx_ensemble *e)
-{
-  EnsStatState *st = e->stat;
-  if (!st) return;
-  if (st->tab_host) hipHostFree(st->tab_host);
-  hipFree(st->tab_dev);
-  if (st->out_host) hipHostFree(st->out_host);
-  hipFree(st->out_dev);
-  delete st;
-  e->stat = nullptr;
-}
-
-static int ens_stat_reserve(wx_ensemble *e, int n_sel, size_t out_bytes)
-{
-  if (!e->stat) e->stat = new EnsStatState();
-  EnsStatState *st = e->stat;
-  if (n_sel > st->tab_cap) {
-    if (st->tab_host) hipHostFree(st->tab_host);
-    hipFree(st->tab_dev);
-    st->tab_host = st->tab_dev = nullptr;
-    st->tab_cap = 0;
-    const size_t bytes = (size_t)n_sel * sizeof(wxe::Member);
-    if (hipHostMalloc((void **)&st->tab_host, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&st->tab_dev, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return efail(e, WX_E_NOMEM, "wx_ensemble_statistics: %zu bytes for the table of %d members", bytes, n_sel);
-    }
-    st->tab_cap = n_sel;
-  }
-  if (out_bytes > st->out_cap) {
-    if (st->out_host) hipHostFree(st->out_host);
-    hipFree(st->out_dev);
-    st->out_host = st->out_dev = nullptr;
-    st->out_cap = 0;
-    if (hipHostMalloc((void **)&st->out_host, out_bytes, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&st->out_dev, out_bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return efail(e, WX_E_NOMEM, "wx_ensemble_statistics: %zu bytes (device and pinned host) for the planes of the rectangle", out_bytes);
-    }
-    st->out_cap = out_bytes;
-  }
-  return WX_OK;
-}
-
 int wx_ens_stat_cells(int n_members, size_t n_cells, const float *const *field, const int8_t *const *wall, const uint8_t *member_mask, wx_ens_stat *out)
 {
   return wxe::stat_cells(n_members, n_cells, field, wall, member_mask, out);
@@ -359,21 +277,14 @@ int wx_ens_stat_cells(int n_members, size_t n_cells, const float *const *field, 
 
 int wx_ensemble_statistics(wx_ensemble *e, int field, int x, int y, int w, int h, const uint8_t *member_mask, wx_ens_stat *out)
 {
+  static const char *const call = "wx_ensemble_statistics";
   if (!e || !out) return WX_E_INVALID;
   // the arguments first: nothing below this block is reached with a bad one, and nothing in it touches the device
-  if (field != WX_FIELD_BASE_CUR && field != WX_FIELD_WATER_CUR)
-    return efail(e, WX_E_INVALID, "wx_ensemble_statistics: field %d: WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR (the fields that are stored whole and interleaved)", field);
-  if (w <= 0 || h <= 0 || x < 0 || y < 0 || (long long)x + w > e->X || (long long)y + h > e->Y)
-    return efail(e, WX_E_RANGE, "wx_ensemble_statistics: rect (%d,%d %dx%d) outside %dx%d (no wrap)", x, y, w, h, e->X, e->Y);
-  const int B = (int)e->member.size();
-  std::vector<int> sel;
-  for (int i = 0; i < B; i++)
-    if (!member_mask || member_mask[i]) sel.push_back(i);
+  if (int rc = ens_check_state_field(e, call, field)) return rc;
+  if (int rc = ens_check_rect(e, call, x, y, w, h)) return rc;
+  const std::vector<int> sel = ens_select(e, member_mask);
   if (sel.empty()) return efail(e, WX_E_INVALID, "wx_ensemble_statistics: the member mask selects nobody");
-  for (int i : sel)
-    if (!e->member[i]->uploaded) return efail(e, WX_E_STATE, "member %d: wx_ensemble_statistics before wx_upload", i);
-  if (e->broken) return WX_E_STATE; // (the message of the failed step is kept)
-  DeviceScope dev_scope(e->member[0]);
+  if (int rc = ens_require_uploaded(e, call, sel)) return rc;
 
   const size_t cells = (size_t)w * h;
   size_t at[wxe::N_PLANES], out_bytes = 0;
@@ -381,14 +292,11 @@ int wx_ensemble_statistics(wx_ensemble *e, int field, int x, int y, int w, int h
     at[p] = out_bytes;
     if (wxe::plane_ptr(out, p)) out_bytes += cells * wxe::plane_bytes(p);
   }
-  if (int rc = ens_stat_reserve(e, (int)sel.size(), std::max<size_t>(out_bytes, 16))) return rc;
-  EnsStatState *st = e->stat;
+  EnsCall c(e, call, K_ENS_STAT);
+  if (int rc = ens_begin(c, (int)sel.size(), std::max<size_t>(out_bytes, 16))) return rc;
+  EnsStage *st = c.st;
+  ens_table_field(c, sel, field);
 
-  // the members' pointers as they are NOW (a step rotates the planes): base_0 / water_1 and wall_0, what wx_diag reads
-  for (size_t k = 0; k < sel.size(); k++) {
-    const wx_sim *m = e->member[sel[k]];
-    st->tab_host[k] = wxe::Member{field == WX_FIELD_BASE_CUR ? m->base[0] : m->water[1], m->wall[0], sel[k], 0};
-  }
   wxe::Args a;
   memset(&a, 0, sizeof(a));
   a.X = e->X, a.x0 = x, a.y0 = y, a.w = w, a.h = h, a.n_sel = (int)sel.size();
@@ -399,24 +307,11 @@ int wx_ensemble_statistics(wx_ensemble *e, int field, int x, int y, int w, int h
   a.amn = (int4 *)dev_plane(4), a.amx = (int4 *)dev_plane(5), a.count = (int4 *)dev_plane(6), a.above = (int4 *)dev_plane(7);
   a.n_wall = (int *)dev_plane(8);
 
-  // on the ensemble's stream, behind everything pending: table, kernel, planes to the pinned copy
-  hipError_t he = hipMemcpyAsync(st->tab_dev, st->tab_host, sel.size() * sizeof(wxe::Member), hipMemcpyHostToDevice, e->stream);
-  if (he == hipSuccess) {
-    const unsigned chunks = (unsigned)((w + 63) / 64) * (unsigned)h;
-    const unsigned wgs = std::min<unsigned>((chunks + wxe::WAVES - 1) / wxe::WAVES, wxe::MAX_WGS);
-    {
-      ProfScope ps(e->member[0], K_ENS_STAT); // (wx_profile on member 0 sees the launch, whoever is selected)
-      hipLaunchKernelGGL(wxe::k_ens_stat, dim3(wgs), dim3(wxe::WG), 0, e->stream, a);
-    }
-    he = hipGetLastError();
-  }
-  if (he == hipSuccess && out_bytes) he = hipMemcpyAsync(st->out_host, st->out_dev, out_bytes, hipMemcpyDeviceToHost, e->stream);
-  if (he != hipSuccess) {
-    (void)hipStreamSynchronize(e->stream); // (the pinned table is not rewritten while a copy may still read it)
-    return efail(e, WX_E_DEVICE, "wx_ensemble_statistics (%s): %s", kKernelNames[K_ENS_STAT], hipGetErrorString(he));
-  }
-  // blocking like wx_ensemble_sync, and like it a place where every member's pending report is looked at and consumed
-  if (int rc = wx_ensemble_sync(e)) return rc;
+  // behind the table: kernel, planes to the pinned copy
+  const unsigned wgs = ens_wgs_wave_per_item(ens_chunks(w, h), wxe::WAVES, wxe::MAX_WGS);
+  ens_launch(c, K_ENS_STAT, [&] { hipLaunchKernelGGL(wxe::k_ens_stat, dim3(wgs), dim3(wxe::WG), 0, e->stream, a); });
+  if (c.he == hipSuccess && out_bytes) c.he = hipMemcpyAsync(st->out_host, st->out_dev, out_bytes, hipMemcpyDeviceToHost, e->stream);
+  if (int rc = ens_finish(c)) return rc;
   for (int p = 0; p < wxe::N_PLANES; p++)
     if (void *dst = wxe::plane_ptr(out, p)) memcpy(dst, st->out_host + at[p], cells * wxe::plane_bytes(p));
   return WX_OK;

@@ -14,7 +14,7 @@
 // the chunk's launches; an event behind the last of them guards the pair of buffers, and the host waits for it only when it comes round
 // to the same buffer again (ENS_BUFS chunks later).
 
-struct EnsStatState; // wx_ens_stat.h
+struct EnsStage; // wx_ens_frame.h
 struct EnsPriorState; // wx_ens_inflate.h
 
 struct wx_ensemble {
@@ -31,13 +31,13 @@ struct wx_ensemble {
   int next = 0;
   int64_t iters_batched = 0, iters_solo = 0, march_launches = 0; // wx_ensemble_stats
   int64_t iters_particles = 0, particle_launches = 0;            // wx_ensemble_particle_stats
-  EnsStatState *stat = nullptr; // wx_ensemble_statistics: its device table, output planes and pinned copies (made by the first call)
+  EnsStage *stage = nullptr; // the member-axis calls: their device table of members, output buffer and pinned copies (made by the first call)
   EnsPriorState *prior = nullptr; // wx_ensemble_prior_save: one device-side snapshot per field (made by the first call)
   bool broken = false; // a step failed half-way: members' host state ran ahead of what was launched (wx_ensemble_step refuses from then on)
   std::string err;
 };
 
-static void ens_stat_release(wx_ensemble *e); // wx_ens_stat.h
+static void ens_stage_release(wx_ensemble *e); // wx_ens_frame.h
 static void ens_prior_release(wx_ensemble *e); // wx_ens_inflate.h
 
 static int efail(wx_ensemble *e, int code, const char *fmt, ...)
@@ -82,7 +82,7 @@ void wx_ensemble_destroy(wx_ensemble *e)
     if (e->host[b]) hipHostFree(e->host[b]);
     hipFree(e->dev[b]);
   }
-  ens_stat_release(e);
+  ens_stage_release(e);
   ens_prior_release(e);
   if (e->stream) hipStreamDestroy(e->stream);
   (void)hipSetDevice(prev);

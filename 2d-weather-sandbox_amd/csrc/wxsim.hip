@@ -2951,6 +2951,7 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 #include "wx_comm.h" // (its entry points are declared extern "C" by include/wxsim.h)
 #include "wx_ensemble.h" // (likewise)
 #include "wx_state_copy.h" // (likewise)
+#include "wx_ens_frame.h" // (likewise)
 #include "wx_ens_stat.h" // (likewise)
 #include "wx_ens_perturb.h" // (likewise)
 #include "wx_ens_quant.h" // (likewise)

@@ -17,7 +17,8 @@ is the droplet-free run.
 --statistics FIELD (BASE_CUR or WATER_CUR; --mode ensemble): instead of the stepping time, what ONE wx_ensemble_statistics call over the
 whole grid costs (all nine planes, host to host: the call blocks) against the route it replaces -- B read_rect calls of the field and B of
 WALL_CUR plus the same arithmetic in numpy, member by member in member order as include/wxsim.h defines it -- after --frame iterations;
---repeats calls of each, the slowest and the median reported under the shape's "statistics" key, with the kernel's own time (wx_profile
+--repeats calls of each, the slowest and the median (of the device call also the fastest: slowest - fastest is the run's own noise figure)
+reported under the shape's "statistics" key, with the kernel's own time (wx_profile
 on member 0) and the bytes it reads per second (members x 20 B per cell and pass, two passes).
 --quantiles FIELD (BASE_CUR or WATER_CUR; --mode ensemble): what ONE wx_ensemble_quantiles call over the whole grid costs (p = 0.1, 0.5,
 0.9, linear, with count and n_wall; host to host) against the route it replaces -- B read_rect pairs, np.sort along the member axis
@@ -210,7 +211,7 @@ def time_statistics(a, ens, X, Y, B):
     kernel_us = 1e3 * kernel_ms / max(launches, 1)
     ms = lambda t: round(1e3 * t, 3)
     return {"field": field, "members": B, "calls": a.repeats, "same_numbers": True,
-            "statistics_call_ms": {"slowest": ms(max(t_dev)), "median": ms(statistics.median(t_dev))},
+            "statistics_call_ms": {"slowest": ms(max(t_dev)), "median": ms(statistics.median(t_dev)), "fastest": ms(min(t_dev))},
             "read_rect_route_ms": {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))},
             "speedup_slowest": round(max(t_host) / max(t_dev), 2),
             "kernel_us": round(kernel_us, 2), "kernel_launches_timed": launches,
@@ -548,7 +549,7 @@ def time_inflate(a, pkg, ens, X, Y, B):
         nbytes = INFLATE_BYTES[mode] * X * Y * B
         gbs = nbytes / (k_us * 1e-6) / 1e9 if k_us > 0 else None
         once = INFLATE_BYTES_ONCE[mode] * X * Y * B / (k_us * 1e-6) / 1e9 if k_us > 0 else None
-        rec["modes"][mode] = {"coef": kw["coef"], "one_call_ms": {"slowest": ms(max(t_call)), "median": ms(statistics.median(t_call))},
+        rec["modes"][mode] = {"coef": kw["coef"], "one_call_ms": {"slowest": ms(max(t_call)), "median": ms(statistics.median(t_call)), "fastest": ms(min(t_call))},
                               "kernel_us": round(k_us, 2), "kernel_launches_timed": k_n, "bytes_per_member_cell_at_most": INFLATE_BYTES[mode],
                               "kernel_gb_per_s_at_most": round(gbs, 1) if gbs else None, "kernel_fraction_of_peak_at_most": round(gbs / a.peak_gbs, 4) if gbs else None,
                               "bytes_per_member_cell_read_once": INFLATE_BYTES_ONCE[mode], "kernel_gb_per_s_read_once": round(once, 1) if once else None,
