@@ -1036,7 +1036,37 @@ def fx_crash64(case):
 TOOLS64_RUNS = [(t, s, h, "disc") for t in WALL_TOOLS for s in (+1, -1) for h in (1, 3)] + [(t, s, h, m) for m, t, s, h in TOOLS64_EXTRA]
 
 
+# ------------------------------------------------------------------------------------------------
+# sun64: the sun at the angles where the lighting pass's bilinear tap changes its columns and rows (tests/light_scenes.py has the
+# classes): GUI 180 and GUI 0 (sin = +-1 in float32: columns x + 1, x + 2 / x - 1, x), the floats next below +-pi/2, -1e-30 (floor(sin a) = -1
+# with weight 1.0 on the right column of the two) and +-float32(pi). No other family has them. 64 x 48 WITHOUT walls (light_scenes.light_scene:
+# below 50 rows a ceiling would grow down as fast as the light enters), drawn as GL_POINTS; 48 iterations under GUI 60 let the light
+# in -- it travels one row per iteration, and below the horizon nothing enters at all -- then `uniform_changes` turns the sun to the
+# specimen (the angle alone: sunIntensity stays GUI 60's) and 8 more iterations run; the last two are dumped.
+# ------------------------------------------------------------------------------------------------
+SUN64 = ("gui180", "gui0", "below_half_pi", "neg_below_half_pi", "neg_tiny", "pi", "neg_pi")
+SUN64_FILL, SUN64_UNDER = 48, 8
+# a domain 3 km high instead of 12: without a floor the top row's upper neighbour is row 0 (REPEAT), and the step of the initial profile
+# across that seam -- 40 K at 12 km -- is what the reference's fixed-point filter weights act on
+SUN64_SIM_HEIGHT = 3000.0
+
+
+def fx_sun64(name):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import light_scenes as L
+    X, Y = 64, 48
+    # (without the cells of smoke beyond 4: the bounds the fixtures are compared with are absolute, and the reference's fixed-point filter
+    # weights move an advected 17 by 1e-5 within these 56 iterations)
+    base, water, wall = L.light_scene(X, Y, thick_smoke=False, sim_height=SUN64_SIM_HEIGHT)
+    u = L.scene_uniforms(Y, sim_height=SUN64_SIM_HEIGHT)
+    n = SUN64_FILL + SUN64_UNDER
+    return run_fixture("sun64_" + name, X, Y, base, water, wall, None, u, niter=n, dump_iters=[n - 1, n], precip=False, iter0=0,
+                       keep=("base_cur", "water_cur", "wall_cur", "light_0", "light_1"), points=True,
+                       uniform_changes={SUN64_FILL: {"sunAngle": float(L.angle_of(L.SPECIMENS[name][0]))}})
+
+
 FIXTURES = {
+    **{"sun64_" + n: (lambda n=n: fx_sun64(n)) for n in SUN64},
     "randwalls64": fx_randwalls64,
     "brush64": fx_brush64,
     "save100qa": lambda: fx_save100(False),

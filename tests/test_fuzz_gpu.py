@@ -72,6 +72,29 @@ def test_fuzz_surface_life_cycle_against_the_oracle(pkg, oracle, fuzz, seed):
     assert compared >= 90 and smoothing >= 15, (compared, smoothing)
 
 
+@pytest.mark.parametrize("mode,seed", [("oracle", 31), ("oracle", 32), ("group", 33), ("group", 34)])
+def test_fuzz_sun_at_exact_slider_positions(pkg, oracle, fuzz, mode, seed):
+    """Drawn cases with fuzz_parity.draw_sun_exact on top: from the second step on the sun stands at GUI -10, 0, 90, 180, 190 or within
+    1e-6 degrees of 90 / 180 -- the positions the continuum of draw_case never hits, where the lighting pass's tap reads columns x + 1, x + 2
+    or rows y + 1, y + 2 (tests/light_scenes.py). Seeds of their own: the cases of the tests above are what they were."""
+    rng = np.random.default_rng(seed)
+    compared, wet, seen = 0, 0, set()
+    for k in range(60):
+        c = fuzz.draw_more_sliders(fuzz.draw_case(rng, 60000))
+        if mode == "group":
+            c = fuzz.draw_group(rng, c)
+        c = fuzz.draw_sun_exact(c)
+        assert c["sun_exact"] in fuzz.SUN_EXACT and len(c["steps"]) >= 2
+        bad, info = fuzz.run_group_case(pkg, pkg.engine, c) if mode == "group" else fuzz.run_case(pkg, pkg.engine, oracle, c)
+        if info.get("error") or info.get("blown_up"):
+            continue
+        compared += 1
+        wet += int(not c["dry"])
+        seen.add(c["sun_exact"]) if not c["dry"] else None
+        assert not bad, json.dumps({"mode": mode, "seed": seed, "case": k, "recipe": c, "mismatches": bad})
+    assert compared >= 40 and wet >= 20 and len(seen) >= 7, (compared, wet, sorted(seen))
+
+
 def test_fuzz_regressions_of_round_6(pkg, fuzz):
     recs = json.load(open(os.path.join(ROOT, "tests", "golden", "fuzz_group_regressions.json")))
     assert len(recs) >= 3

@@ -26,7 +26,7 @@ ran the passes that store them). The recipe, script included, is printed and flu
 A WxError other than the exact path's reported overflow is not expected: the run ends there (exit 2). This is not a tool to provoke
 faults with: run it under `timeout`, and find the cause of a fault or hang from the recipe before starting the case again.
 
-    python tools/fuzz_parity.py [--mode M] [--seed S] [--cases N] [--seconds T] [--max-cells C] [--only K] [--override JSON] [--check-launches]
+    python tools/fuzz_parity.py [--mode M] [--seed S] [--cases N] [--seconds T] [--max-cells C] [--only K] [--override JSON] [--sun-exact] [--check-launches]
 
 Every case prints one line; a mismatch prints the case's recipe (the seed reproduces it: --seed S --only K) and the run exits 1 at the
 end. The oracle is the checker (test infrastructure); nothing here is a product path."""
@@ -105,6 +105,31 @@ def draw_clone(c):
         c["clone"] = {"after_step": int(r.integers(0, len(c["steps"]))), "pairs": int(r.random() < 0.7), "bands": int(r.choice([0, 1, 2])),
                       "water0_on_demand": int(r.random() < 0.7), "used": bool(r.random() < 0.5)}
     return c
+
+
+# The sun at an EXACT slider position: draw_case takes the angle from a continuum, which never hits GUI 0, 90 or 180 -- the positions at which
+# sinf / cosf of the uniform are exactly +-1 or 0 and the bilinear tap of the lighting pass changes its columns (x + 1, x + 2 at GUI 180) and rows
+# (y + 1, y + 2 at GUI 90); tests/light_scenes.py has the classes. Drawn like draw_more_sliders, as a function of the case (recipe key
+# "sun_exact"; recipes without it run as they always did). The case keeps its drawn sun for the first step, which lets light in where that sun
+# is up, and takes the exact position -- the angle alone, sunIntensity stays the drawn sun's: at GUI 0 and 180 it would be 0 -- from the second
+# step on; a case of one step gets a second one.
+SUN_EXACT = (-10.0, 0.0, 90.0, 180.0, 190.0, 90.0 - 1e-6, 90.0 + 1e-6, 180.0 - 1e-6, 180.0 + 1e-6)
+
+
+def draw_sun_exact(c):
+    """Adds c["sun_exact"] (degrees, one of SUN_EXACT). No draw from the case's generator."""
+    r = np.random.default_rng([int(c["data_seed"]) & 0x7FFFFFFF, 0x50A])
+    c["sun_exact"] = float(SUN_EXACT[int(r.integers(0, len(SUN_EXACT)))])
+    if len(c["steps"]) == 1:
+        c["steps"] = c["steps"] + [int(r.integers(1, 12))]
+    return c
+
+
+def sun_exact_uniforms(pkg, c, u, k_step):
+    """``u`` with the exact angle from the case's second step on (None: nothing changes at this step)."""
+    if c.get("sun_exact") is None or k_step != 1:
+        return None
+    return dict(u, sunAngle=float(np.float32(pkg.params.sun_from_angle(c["sun_exact"], 1.0)[0])))
 
 
 CLONE_FIELDS = ["BASE_CUR", "BASE_DISP", "WATER_0", "WATER_CUR", "WALL_CUR", "WALL_DISP", "LIGHT_0", "LIGHT_1", "CURL", "PRECIP_FB", "PRECIP_DEP", "LIGHTNING", "EMITTED"]
@@ -294,6 +319,11 @@ def case_steps(pkg, E, wx_oracle, c):
             h.set_option(h.OPT_SPLAT_ORDER, 1)
         rng = np.random.default_rng(c["data_seed"] ^ 0x5EED)
         for k_step, n in enumerate(c["steps"]):
+            if sun_exact_uniforms(pkg, c, u, k_step) is not None:
+                u = sun_exact_uniforms(pkg, c, u, k_step)
+                for hh_ in (h, h2) if h2 is not None else (h,):
+                    hh_.set_params(pkg.params.fill_struct(pkg.params.WxParams(), u), u["initial_T"])
+                o.set_params(u)
             if c.get("brush_toggle") and c["brush"] and k_step > 0:  # mouse up / down between two steps: new parameters on both sides
                 u2 = dict(u, userInputType=(c["brush"]["type"] if k_step % 2 == 0 else -1))
                 for hh_ in (h, h2) if h2 is not None else (h,):  # (a clone is given every call its source is given)
@@ -725,6 +755,11 @@ def run_group_case(pkg, E, c):
                 st = [whole.read_rect(f) for f in ("BASE_CUR", "WATER_CUR", "WALL_CUR")]
                 g.upload(*st)
                 whole.upload(*st)
+            if sun_exact_uniforms(pkg, c, u, k_step) is not None:
+                u = sun_exact_uniforms(pkg, c, u, k_step)
+                p = pkg.params.fill_struct(pkg.params.WxParams(), u)
+                g.set_params(p, u["initial_T"])
+                whole.set_params(p, u["initial_T"])
             if c.get("brush_toggle") and c["brush"] and k_step > 0:  # mouse up / down between two steps
                 u2 = dict(u, userInputType=(c["brush"]["type"] if k_step % 2 == 0 else -1))
                 p2 = pkg.params.fill_struct(pkg.params.WxParams(), u2)
@@ -962,6 +997,7 @@ def main():
     ap.add_argument("--first", type=int, default=0, help="skip the cases before this one (they are still drawn: same sequence)")
     ap.add_argument("--last", type=int, default=1 << 30)
     ap.add_argument("--override", default="", help="JSON object merged into the recipe of every case that runs (bisecting a failure)")
+    ap.add_argument("--sun-exact", action="store_true", help="oracle / group mode: draw_sun_exact on top of every case (the sun at an exact slider position from the second step on)")
     ap.add_argument("--check-launches", action="store_true", help="WX_OPT_CHECK_LAUNCHES 1: synchronise and check after every launch")
     a = ap.parse_args()
     pkg = wxpkg.load_package()
@@ -997,6 +1033,8 @@ def main():
         c = draw_clone(draw_surface(draw_more_sliders(draw_case(rng, a.max_cells, a.big))))
         if a.mode == "group":
             c = draw_group(rng, c)
+        if a.sun_exact and a.mode in ("oracle", "group"):
+            c = draw_sun_exact(c)
         if a.mode == "script":
             c = draw_script(rng_script, c)
         if (a.only >= 0 and k != a.only) or k < a.first:
