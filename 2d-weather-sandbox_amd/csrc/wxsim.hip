@@ -62,6 +62,8 @@ enum KernelId {
   K_ENS_INFLATE, // covariance inflation / relaxation to the prior over the members of an ensemble (wx_ens_inflate.h)
   K_ENS_COV_PRED, // covariance maps: the predictors' chains, the pre-pass (wx_ens_cov.h)
   K_ENS_COV,    // covariance, correlation and sensitivity maps over the members of an ensemble (wx_ens_cov.h)
+  K_ENS_NBHD_POINTS,  // neighbourhood probabilities: the members' event counts per cell (wx_ens_nbhd.h)
+  K_ENS_NBHD_WINDOWS, // the box sums, the fractions and the sums of the fractions skill score (wx_ens_nbhd.h)
   K_ENS_ASSIM_OBS, // point observations assimilated into the members: the observation-space pre-pass (wx_ens_assim.h)
   K_ENS_ASSIM,  // the state update of one field (wx_ens_assim.h)
   K_COUNT
@@ -70,7 +72,7 @@ const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "bou
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
                                            "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb",
                                            "ensemble_quantiles", "ensemble_scores", "ensemble_prior_save", "ensemble_inflate", "ensemble_covariance_pred", "ensemble_covariance",
-                                           "ensemble_assimilate_obs", "ensemble_assimilate"};
+                                           "ensemble_nbhd_points", "ensemble_nbhd_windows", "ensemble_assimilate_obs", "ensemble_assimilate"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -2959,3 +2961,4 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 #include "wx_ens_assim.h" // (likewise)
 #include "wx_ens_inflate.h" // (likewise)
 #include "wx_ens_cov.h" // (likewise)
+#include "wx_ens_nbhd.h" // (likewise)

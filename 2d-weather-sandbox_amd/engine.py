@@ -50,6 +50,7 @@ EXPORTS = [
     "wx_ensemble_assimilate", "wx_ens_assim_cells",
     "wx_ensemble_prior_save", "wx_ensemble_prior_drop", "wx_ensemble_inflate", "wx_ens_inflate_cells",
     "wx_ensemble_covariance", "wx_ens_cov_cells",
+    "wx_ensemble_neighbourhood", "wx_ens_nbhd_cells", "wx_ens_nbhd_max_radius",
 ]
 
 
@@ -625,6 +626,87 @@ def ens_score_cells(fields, walls, truth_field, truth_wall, *, members=None, wan
     return _ens_score_dict(st, maps)
 
 
+ENS_NBHD_MAX_RADIUS = 32
+ENS_NBHD_MAX_SCALES = 8
+ENS_NBHD_COUNTS = ("n_scored", "n_unscored")
+ENS_NBHD_SUMS = ("sum_d2", "sum_f2", "sum_o2")
+ENS_NBHD_TOTALS = ("ev_f", "n_f", "ev_o", "n_o")
+ENS_NBHD_MAPS = ("nep", "obs_fraction")
+
+
+class WxEnsNbhd(C.Structure):
+    """``wx_ens_nbhd`` of include/wxsim.h, member for member: the event, the rectangle, the scales and the caller-owned maps (NULL = not wanted)."""
+    _fields_ = [("field", C.c_int32), ("channel", C.c_int32), ("threshold", C.c_float), ("above", C.c_int32), ("wrap_x", C.c_int32),
+                ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("n_scales", C.c_int32),
+                ("rx", C.c_int32 * ENS_NBHD_MAX_SCALES), ("ry", C.c_int32 * ENS_NBHD_MAX_SCALES), ("nep", C.c_void_p), ("obs_fraction", C.c_void_p)]
+
+
+class WxEnsNbhdResult(C.Structure):
+    """``wx_ens_nbhd_result`` of include/wxsim.h: the counts and exact sums per scale, the point totals of the rectangle."""
+    _fields_ = ([(k, C.c_int64 * ENS_NBHD_MAX_SCALES) for k in ENS_NBHD_COUNTS] + [(k, C.c_double * ENS_NBHD_MAX_SCALES) for k in ENS_NBHD_SUMS]
+                + [(k, C.c_int64) for k in ENS_NBHD_TOTALS])
+
+
+def _ens_nbhd_struct(field, channel, threshold, scales, above, wrap_x, rect, want):
+    """A wx_ens_nbhd for ``scales`` = [(rx, ry), ...] (a single number r is (r, r)) whose maps named in ``want`` are fresh float32
+    arrays (n_scales, h, w), and those arrays by name."""
+    unknown = set(want) - set(ENS_NBHD_MAPS)
+    if unknown:
+        raise KeyError(f"no such map of wx_ens_nbhd: {sorted(unknown)} (there are {ENS_NBHD_MAPS})")
+    pairs = [(int(s), int(s)) if np.ndim(s) == 0 else (int(s[0]), int(s[1])) for s in scales]
+    a, maps = WxEnsNbhd(), {}
+    a.field, a.channel, a.threshold = int(FIELD_IDS.get(field, field)), int(channel), float(threshold)
+    a.above, a.wrap_x = int(bool(above)), int(bool(wrap_x))
+    a.x, a.y, a.w, a.h = [int(v) for v in rect]
+    a.n_scales = len(pairs)
+    for s, (rx, ry) in enumerate(pairs[:ENS_NBHD_MAX_SCALES]):
+        a.rx[s], a.ry[s] = rx, ry
+    for name in ENS_NBHD_MAPS:
+        if name in want:
+            maps[name] = np.zeros((max(min(len(pairs), ENS_NBHD_MAX_SCALES), 0), max(a.h, 0), max(a.w, 0)), np.float32)
+            setattr(a, name, maps[name].ctypes.data)
+    return a, maps
+
+
+def _ens_nbhd_dict(a: WxEnsNbhd, res: WxEnsNbhdResult, maps: dict) -> dict:
+    n = max(min(a.n_scales, ENS_NBHD_MAX_SCALES), 0)
+    out = {k: np.array(getattr(res, k), np.int64)[:n] for k in ENS_NBHD_COUNTS}
+    out.update({k: np.array(getattr(res, k), np.float64)[:n] for k in ENS_NBHD_SUMS})
+    out.update({k: int(getattr(res, k)) for k in ENS_NBHD_TOTALS})
+    out.update(maps)
+    return out
+
+
+def ens_nbhd_cells(fields, walls, X: int, Y: int, field, channel, threshold, scales, truth_field=None, truth_wall=None, *, above=True, rect=None,
+                   members=None, wrap_x=False, want=ENS_NBHD_MAPS) -> dict:
+    """wx_ens_nbhd_cells: neighbourhood ensemble probabilities and the sums of the fractions skill score on the CPU, literally as
+    include/wxsim.h defines them. ``fields[i]`` / ``walls[i]``: member i's whole grid, float32 (Y, X, 4) and int8 (Y, X, 4) (an
+    unselected member's entries may be None); ``truth_field`` / ``truth_wall``: the truth's, or None for the forecast product alone.
+    ``scales``: up to 8 (rx, ry) half-widths, 0 .. 32. Returns per scale n_scored, n_unscored (int64), sum_d2, sum_f2, sum_o2
+    (float64), the totals ev_f, n_f, ev_o, n_o of ``rect`` = (x, y, w, h) (None: the whole grid), and the maps named in ``want`` (nep,
+    obs_fraction: (n_scales, h, w) float32, NaN where the window holds no counted cell)."""
+    f = [None if a is None else np.ascontiguousarray(a, np.float32) for a in fields]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    tf = None if truth_field is None else np.ascontiguousarray(truth_field, np.float32)
+    tw = None if truth_wall is None else np.ascontiguousarray(truth_wall, np.int8)
+    n = len(f)
+    have = [a for a in f + wl + [tf, tw] if a is not None]
+    if n < 1 or len(wl) != n or any(a.shape != (Y, X, 4) for a in have):
+        raise ValueError("one (Y, X, 4) field and one (Y, X, 4) wall array per member and for the truth")
+    if tf is None:
+        want = tuple(k for k in want if k != "obs_fraction")
+    a, maps = _ens_nbhd_struct(field, channel, threshold, scales, above, wrap_x, (0, 0, X, Y) if rect is None else rect, want)
+    res = WxEnsNbhdResult()
+    fp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in f])
+    wp = (C.c_void_p * n)(*[None if x is None else x.ctypes.data for x in wl])
+    mask = _member_mask(n, members)
+    rc = lib().wx_ens_nbhd_cells(C.byref(a), C.byref(res), int(X), int(Y), n, fp, wp, None if tf is None else tf.ctypes.data, None if tw is None else tw.ctypes.data,
+                                 None if mask is None else mask.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_ens_nbhd_cells: a bad field, channel, threshold, scale or rectangle, a wrapped window wider than the grid, an absent member, or no member selected")
+    return _ens_nbhd_dict(a, res, maps)
+
+
 def build(force: bool = False, fast: bool = False) -> str:
     """Compile libwxsim.so (``fast``: the tolerance build libwxsim_fast.so) for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
@@ -791,6 +873,10 @@ def lib() -> C.CDLL:
     L.wx_ens_inflate_cells.argtypes = [C.POINTER(WxEnsInflate), i32, C.c_size_t, vp, vp, vp, vp]
     L.wx_ensemble_covariance.argtypes = [vp, C.POINTER(WxEnsCov), vp, vp, vp]
     L.wx_ens_cov_cells.argtypes = [C.POINTER(WxEnsCov), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.wx_ensemble_neighbourhood.argtypes = [vp, vp, C.POINTER(WxEnsNbhd), vp, C.POINTER(WxEnsNbhdResult)]
+    L.wx_ens_nbhd_cells.argtypes = [C.POINTER(WxEnsNbhd), C.POINTER(WxEnsNbhdResult), i32, i32, i32, vp, vp, vp, vp, vp]
+    L.wx_ens_nbhd_max_radius.argtypes = []
+    L.wx_ens_nbhd_max_radius.restype = i32
     _lib = L
     return L
 
@@ -1496,6 +1582,29 @@ class Ensemble:
         planes["results"] = _cov_results(res, len(predictors))
         del keep
         return planes
+
+    def neighbourhood(self, field: str, channel: int, threshold: float, scales, truth: Optional["Handle"] = None, *, above: bool = True, rect=None,
+                      members=None, wrap_x: bool = False, want=("nep",)) -> dict:
+        """wx_ensemble_neighbourhood: the event "channel ``channel`` of ``field`` (BASE_CUR or WATER_CUR) above (``above`` False:
+        below) ``threshold``" counted over the selected members (None: all but ``truth`` if it is a member of this ensemble; any
+        number) and summed over boxes of the ``scales`` -- up to 8 (rx, ry) half-widths, 0 .. 32; a single number r is (r, r) -- around
+        every cell of ``rect`` = (x, y, w, h) (None: the whole grid); windows reach outside the rectangle, around the seam with
+        ``wrap_x``. Against ``truth`` -- a lone ``Handle``, an unselected member, a member of another ensemble -- the raw material of
+        the fractions skill score per scale: n_scored, n_unscored, the exact sums sum_d2, sum_f2, sum_o2, and the point totals ev_f,
+        n_f, ev_o, n_o. The maps named in ``want``: ``nep`` (n_scales, h, w), the neighbourhood ensemble probability, and
+        ``obs_fraction``, the truth's fraction (NaN where a window holds no counted cell). ``truth`` None: nep and ev_f / n_f alone.
+        The members are read once, two launches; changes nothing; blocks like ``sync``."""
+        rect = (0, 0, self.X, self.Y) if rect is None else rect
+        a, maps = _ens_nbhd_struct(field, channel, threshold, scales, above, wrap_x, rect, want)
+        res = WxEnsNbhdResult()
+        mask = _member_mask(self.n, members)
+        if members is None and truth is not None:
+            inside = [i for i, m in enumerate(self.members) if m is truth or (m._h.value == truth._h.value)]
+            if inside:
+                mask = np.ones(self.n, np.uint8)
+                mask[inside] = 0
+        self._chk(lib().wx_ensemble_neighbourhood(self._e, None if truth is None else truth._h, C.byref(a), None if mask is None else mask.ctypes.data, C.byref(res)))
+        return _ens_nbhd_dict(a, res, maps)
 
     def close(self):
         if getattr(self, "_e", None):

@@ -473,6 +473,31 @@ class WeatherEnsemble:
         out["rank_histogram"] = (out["rank_low"] + out["rank_high"]).astype(np.float64) / 2.0
         return out
 
+    def neighbourhood(self, field: str, channel: int, threshold: float, scales, truth=None, *, wrap_x=None, **kw) -> dict:
+        """``engine.Ensemble.neighbourhood``: neighbourhood ensemble probabilities of the event "channel of ``field`` above
+        ``threshold``" at the ``scales`` ((rx, ry) half-widths in cells) and, against ``truth`` -- a ``WeatherSim`` or an
+        ``engine.Handle`` --, the fractions skill score (Roberts and Lean 2008), on the device (above, rect, members, want). On top of
+        the raw sums, in plain float64: ``fss`` = 1 - sum_d2 / (sum_f2 + sum_o2) per scale, NaN where the denominator is 0;
+        ``base_rate`` = ev_o / n_o; ``frequency_bias`` = (ev_f / n_f) / base_rate; ``fss_useful`` = 0.5 + base_rate / 2, the FSS above
+        which a forecast is useful at that scale. ``wrap_x`` defaults to the members' ``wrapHorizontally``. The maps asked for with
+        ``want`` (nep, obs_fraction) come back under ``maps``."""
+        from .engine import ENS_NBHD_MAPS
+        if wrap_x is None:
+            wrap_x = bool(self.members[0].gui.get("wrapHorizontally", True))
+        out = self._e.neighbourhood(field, channel, threshold, scales, None if truth is None else getattr(truth, "handle", truth), wrap_x=wrap_x, **kw)
+        out["maps"] = {k: out.pop(k) for k in ENS_NBHD_MAPS if k in out}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            den = out["sum_f2"] + out["sum_o2"]
+            out["fss"] = np.where(den > 0, 1.0 - out["sum_d2"] / den, np.nan)
+            out["base_rate"] = np.float64(out["ev_o"]) / np.float64(out["n_o"])
+            out["frequency_bias"] = (np.float64(out["ev_f"]) / np.float64(out["n_f"])) / out["base_rate"]
+            out["fss_useful"] = 0.5 + out["base_rate"] / 2.0
+        return out
+
+    def fss(self, field: str, channel: int, threshold: float, scales, truth, **kw) -> list:
+        """The fractions skill score of the members against ``truth`` at each of the ``scales``: ``neighbourhood(...)["fss"]`` as a list."""
+        return [float(v) for v in self.neighbourhood(field, channel, threshold, scales, truth, want=(), **kw)["fss"]]
+
     @property
     def engine(self):
         return self._e

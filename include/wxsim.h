@@ -1105,6 +1105,79 @@ int wx_ens_cov_cells(const wx_ens_cov *c, const wx_ens_cov_pred *pred, wx_ens_co
                      const float *const *prior /* w*h cells of the rectangle per member; WX_COV_SOURCE_PRIOR only */,
                      const uint8_t *member_mask);   /* host only, pure */
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_NEIGHBOURHOOD) Neighbourhood ensemble probabilities and the fractions skill score (FSS, Roberts and
+ * Lean 2008) on the device: verification at a SCALE. Cloud and precipitation are intermittent; a convective cell forecast a few
+ * columns off is penalised twice by every point-wise score of wx_ensemble_scores, although the forecast was good at the scale anyone
+ * would use it. This call counts, per cell, in how many selected members an event (one channel above or below a threshold) holds,
+ * sums the counts over boxes of up to WX_ENS_NBHD_MAX_SCALES sizes at once, compares the forecast fraction with the truth's and
+ * returns the three domain sums the FSS is made of, per scale, with the two fraction maps if they are wanted. The members are read
+ * once per grid cell, whatever the number of scales; there is no cap on the number of members beyond the ensemble's own.
+ *
+ * THE DEFINITION (the kernels, wx_ens_nbhd_cells and the tests all evaluate it). Everything up to one division per cell is integer
+ * arithmetic, so the result does not depend on the order of the members, the launch shape or the build.
+ *   Event. For a value v of channel `channel` of `field`: above != 0: v > threshold (the float compare of wx_ens_stat's n_above);
+ *   above == 0: v < threshold. A NaN threshold gives no event anywhere; -0.0 == 0.0.
+ *   Point counts, for every cell of the GRID. Nf = the number of selected members in which the cell is an air cell (channel 1 of its
+ *   WX_FIELD_WALL_CUR texel != 0: wx_diag's test) and the channel's value is finite; Ef = the number of those in which the event
+ *   holds. No and Eo: the same for `truth`, each 0 or 1 (both 0 everywhere if truth is NULL).
+ *   Window of scale s = (rx, ry) around output cell (cx, cy): columns cx-rx .. cx+rx, rows cy-ry .. cy+ry. Rows outside 0 .. Y-1
+ *   contribute nothing. Columns outside 0 .. X-1 contribute nothing without wrap_x; with wrap_x they are taken modulo X, and then
+ *   2*rx+1 > X is WX_E_RANGE, so that no cell is counted twice. Windows reach outside the rectangle into the grid: a cell's result
+ *   does not depend on the rectangle. Af, Bf, Ao, Bo are the window sums of Ef, Nf, Eo, No: integers, at most
+ *   (2*32+1)^2 * 65535 = 276 885 375 (a window of 4225 cells, an ensemble of at most 65535 members), which fits int32.
+ *   Per cell and scale. The cell is SCORED when Bf > 0 and Bo > 0; otherwise it counts into n_unscored[s]. In double, each operation
+ *   rounded once: pf = (double)Af / (double)Bf, po = (double)Ao / (double)Bo, d = pf - po; three floats d2 = (float)(d*d),
+ *   f2 = (float)(pf*pf), o2 = (float)(po*po). They lie in [0, 1]: always finite. (No product feeds a sum: nothing a build could fuse.)
+ *   Domain sums per scale, over the scored cells of the rectangle: n_scored[s]; sum_d2[s], sum_f2[s], sum_o2[s], the EXACT sums of
+ *   those floats rounded to double once -- what Python's math.fsum returns --, taken with wx_diag's integer bins and its 320-bit
+ *   finish as wx_ens_score's sums are. FSS(s) = 1 - sum_d2 / (sum_f2 + sum_o2) is the host's one line.
+ *   Point-level totals over the rectangle, independent of scale: ev_f, n_f, ev_o, n_o = the sums of Ef, Nf, Eo, No (int64).
+ *   Optional maps, laid out [s][h][w] in float32, rows bottom-up: nep = (float)pf, NaN where Bf == 0 (the neighbourhood ensemble
+ *   probability); obs_fraction = (float)po, NaN where Bo == 0.
+ *   truth may be NULL: the forecast product alone -- nep, ev_f, n_f. Every truth-side number is 0, n_scored is 0 (every cell counts
+ *   into n_unscored), and obs_fraction must not be requested.
+ *
+ * wx_ensemble_neighbourhood. Answered before the device is touched -- WX_E_INVALID: e, args or out NULL; a field other than
+ * WX_FIELD_BASE_CUR / WX_FIELD_WATER_CUR; a channel outside 0 .. 3; n_scales outside 1 .. WX_ENS_NBHD_MAX_SCALES; a radius outside
+ * 0 .. WX_ENS_NBHD_MAX_RADIUS; a threshold that is +-Inf (NaN is taken); obs_fraction wanted without a truth; nobody selected;
+ * `truth` is a selected member of e; `truth` is a slab handle, a handle of another X or Y, or a handle on another device.
+ * WX_E_RANGE: the rectangle does not lie inside the grid (no wrap of the rectangle itself), or wrap_x with a window wider than X.
+ * WX_E_STATE: a selected member, or `truth`, was never uploaded (the message names it). `truth` is any whole-domain handle: a lone
+ * one, an unselected member of e, a member of another ensemble. Ordering behind both streams, blocking, consumption of pending
+ * reports ("truth: ...", "member i: ...") and "changes nothing" exactly as for wx_ensemble_scores; member_mask has one byte per
+ * member (NULL = all); any number of selected members from 1 up. Two launches: the point counts (kernel name
+ * "ensemble_nbhd_points", the member walk of wx_ensemble_statistics, 5 bytes per cell written to the ensemble's device staging),
+ * then the windows (kernel name "ensemble_nbhd_windows"); wx_profile on member 0 times them; DESIGN.md section 4.
+ * wx_ens_nbhd_cells (host only, pure): the same definition over whole X x Y grids the caller holds, because windows leave the
+ * rectangle -- member i's at field[i] (4 floats per cell) and wall[i] (4 bytes per cell), the truth's at truth_field / truth_wall
+ * (both NULL: no truth). WX_E_INVALID / WX_E_RANGE as above, and WX_E_INVALID for n_members < 1, X or Y < 1, a NULL table, a NULL
+ * entry of a selected member, one truth array without the other. A refused call writes nothing. */
+#define WX_HAVE_ENSEMBLE_NEIGHBOURHOOD 1
+#define WX_ENS_NBHD_MAX_RADIUS 32
+#define WX_ENS_NBHD_MAX_SCALES 8
+typedef struct wx_ens_nbhd {
+  int32_t field;            /* WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR */
+  int32_t channel;          /* 0 .. 3 */
+  float   threshold;        /* finite or NaN (no event anywhere) */
+  int32_t above;            /* non-zero: the event is v > threshold; 0: v < threshold */
+  int32_t wrap_x;           /* window columns are taken modulo X */
+  int32_t x, y, w, h;       /* the output cells; the rectangle itself does not wrap (WX_E_RANGE) */
+  int32_t n_scales;         /* 1 .. WX_ENS_NBHD_MAX_SCALES */
+  int32_t rx[WX_ENS_NBHD_MAX_SCALES], ry[WX_ENS_NBHD_MAX_SCALES];  /* half-widths of scale s in cells, 0 .. WX_ENS_NBHD_MAX_RADIUS */
+  float  *nep, *obs_fraction;  /* optional n_scales*h*w maps, NaN where the window holds no counted cell; NULL: not wanted */
+} wx_ens_nbhd;
+typedef struct wx_ens_nbhd_result {
+  int64_t n_scored[WX_ENS_NBHD_MAX_SCALES], n_unscored[WX_ENS_NBHD_MAX_SCALES];
+  double  sum_d2[WX_ENS_NBHD_MAX_SCALES], sum_f2[WX_ENS_NBHD_MAX_SCALES], sum_o2[WX_ENS_NBHD_MAX_SCALES];  /* entries >= n_scales: 0 */
+  int64_t ev_f, n_f, ev_o, n_o;
+} wx_ens_nbhd_result;
+int wx_ensemble_neighbourhood(wx_ensemble *e, wx_sim *truth /* or NULL */, const wx_ens_nbhd *args,
+                              const uint8_t *member_mask /* n_members bytes, NULL = all */, wx_ens_nbhd_result *out);
+int wx_ens_nbhd_cells(const wx_ens_nbhd *args, wx_ens_nbhd_result *out, int X, int Y, int n_members,
+                      const float *const *field, const int8_t *const *wall, const float *truth_field, const int8_t *truth_wall,
+                      const uint8_t *member_mask);   /* host only, pure */
+int wx_ens_nbhd_max_radius(void);  /* == WX_ENS_NBHD_MAX_RADIUS */
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

@@ -87,13 +87,14 @@ def parse():
     ap.add_argument("--assimilate", default="", metavar="FIELD", help="time one assimilation call of --observations point observations against N calls of one and against read_rect + host function + uploads (BASE_CUR or WATER_CUR)")
     ap.add_argument("--inflate", default="", metavar="FIELD", help="time one inflation call per mode over the whole grid against read_rect + the host function (BASE_CUR or WATER_CUR)")
     ap.add_argument("--covariance", default="", metavar="FIELD", help="time one covariance call with 1 and with 8 point predictors over the whole grid against read_rect + numpy and the statistics kernel (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--neighbourhood", default="", metavar="FIELD", help="time one neighbourhood call (B members against member B of B + 1, five scales up to (16, 8), channel 1) against statistics planes + read_rect of the truth + numpy summed-area tables (BASE_CUR or WATER_CUR)")
     ap.add_argument("--observations", type=int, default=40, help="observations per call with --assimilate (1 .. 256)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = "100x100x64,2500x300x8" if a.scores or a.inflate or a.covariance else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
+        a.shapes = "100x100x64,2500x300x8" if a.scores or a.inflate or a.covariance or a.neighbourhood else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
     return a
 
 
@@ -375,6 +376,107 @@ def time_scores(a, pkg, ens, X, Y, B):
             "kernel_gb_read_per_s": round(20 * X * Y * (B + 1) / (kernel_us * 1e-6) / 1e9, 1) if kernel_us > 0 else None,
             "quantiles_kernel_us": round(quant_us, 2), "quantiles_kernel_launches_timed": quant_launches,
             "scores_kernel_over_quantiles_kernel": round(kernel_us / quant_us, 3) if quant_us > 0 else None}
+
+
+NBHD_SCALES = [(0, 0), (1, 1), (4, 2), (8, 4), (16, 8)]
+NBHD_CHANNEL = 1
+
+
+def numpy_neighbourhood(count, above, truth, truth_wall, threshold, scales, wrap):
+    """What a host does with the statistics planes today: one summed-area table per quantity and scale (windows clipped in y, wrapped
+    in x by padding), the fractions, the three sums in plain float64 (np.sum, not exact)."""
+    import numpy as np
+    Y, X = count.shape
+    v = truth[..., NBHD_CHANNEL]
+    no = ((truth_wall[..., 1] != 0) & np.isfinite(v)).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        eo = no * (v > np.float32(threshold))
+    out = {k: [] for k in ("n_scored", "sum_d2", "sum_f2", "sum_o2", "nep")}
+    for rx, ry in scales:
+        def box(q):
+            p = np.pad(np.pad(q.astype(np.int64), ((ry, ry), (0, 0))), ((0, 0), (rx, rx)), mode="wrap" if wrap else "constant")
+            sat = np.zeros((p.shape[0] + 1, p.shape[1] + 1), np.int64)
+            sat[1:, 1:] = p.cumsum(0).cumsum(1)
+            h, w = 2 * ry + 1, 2 * rx + 1
+            return sat[h:h + Y, w:w + X] - sat[:Y, w:w + X] - sat[h:h + Y, :X] + sat[:Y, :X]
+        Af, Bf, Ao, Bo = box(above), box(count), box(eo), box(no)
+        with np.errstate(all="ignore"):
+            pf, po = Af / Bf, Ao / Bo
+            d = pf - po
+        ok = (Bf > 0) & (Bo > 0)
+        out["n_scored"].append(int(ok.sum()))
+        for name, t in (("sum_d2", d * d), ("sum_f2", pf * pf), ("sum_o2", po * po)):
+            out[name].append(float(t.astype(np.float32)[ok].astype(np.float64).sum()))
+        out["nep"].append(pf.astype(np.float32))
+    return out
+
+
+def time_neighbourhood(a, pkg, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    field, sel, wrap = a.neighbourhood, list(range(B)), True
+    ens.step(a.frame)
+    ens.sync()
+    truth_now = ens[B].read_rect(field)[..., NBHD_CHANNEL]
+    air = ens[B].read_rect("WALL_CUR")[..., 1] != 0
+    pos = truth_now[air & (truth_now > 0)]
+    threshold = float(np.median(pos)) if pos.size else float(np.median(truth_now[air]))  # an event in about half of the cells that hold any
+
+    def device(want=()):
+        return ens.neighbourhood(field, NBHD_CHANNEL, threshold, NBHD_SCALES, ens[B], members=sel, wrap_x=wrap, want=want)
+
+    def host():
+        t0 = time.perf_counter()
+        st = ens.statistics(field, members=sel, threshold=(threshold,) * 4, want=("count", "n_above"))
+        truth, truth_wall = ens[B].read_rect(field), ens[B].read_rect("WALL_CUR")
+        t1 = time.perf_counter()
+        return numpy_neighbourhood(st["count"][..., NBHD_CHANNEL], st["n_above"][..., NBHD_CHANNEL], truth, truth_wall, threshold, NBHD_SCALES, wrap), t1 - t0
+
+    got, (want, _) = device(("nep",)), host()
+    if got["n_scored"].tolist() != want["n_scored"] or not all(np.array_equal(got["nep"][s], want["nep"][s], equal_nan=True) for s in range(len(NBHD_SCALES))):
+        sys.exit("--neighbourhood %s %dx%dx%d: wx_ensemble_neighbourhood and the host route disagree in the counts or in nep" % (field, X, Y, B))
+    for k in ("sum_d2", "sum_f2", "sum_o2"):  # (the host's sums are running float64 sums: close, not equal)
+        if not np.allclose(got[k], want[k], rtol=1e-9, atol=1e-9):
+            sys.exit("--neighbourhood %s %dx%dx%d: the two routes disagree in %s: %r / %r" % (field, X, Y, B, k, got[k], want[k]))
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed
+        device()
+    ens[0].profile(True)
+    t_dev, t_host, t_calls = [], [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        device()
+        t_dev.append(time.perf_counter() - t0)
+    prof = ens[0].profile_read()
+    (points_ms, launches), (windows_ms, _) = prof.get("ensemble_nbhd_points", (0.0, 0)), prof.get("ensemble_nbhd_windows", (0.0, 0))
+    for _ in range(a.repeats):  # the comparison OF THE SAME RUN: the statistics kernel reads the same bytes and computes more
+        ens.statistics(field, members=sel, threshold=(threshold,) * 4, want=("count", "n_above"))
+    stat_ms, stat_launches = ens[0].profile_read().get("ensemble_statistics", (0.0, 0))
+    per_scale = []
+    for sc in NBHD_SCALES:  # the windows kernel scale by scale
+        for _ in range(a.repeats):
+            ens.neighbourhood(field, NBHD_CHANNEL, threshold, [sc], ens[B], members=sel, wrap_x=wrap, want=())
+        ms_s, n_s = ens[0].profile_read().get("ensemble_nbhd_windows", (0.0, 0))
+        per_scale.append(round(1e3 * ms_s / max(n_s, 1), 2))
+    ens[0].profile(False)
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        _, calls = host()
+        t_calls.append(calls)
+        t_host.append(time.perf_counter() - t0)
+    points_us, windows_us, stat_us = 1e3 * points_ms / max(launches, 1), 1e3 * windows_ms / max(launches, 1), 1e3 * stat_ms / max(stat_launches, 1)
+    ms = lambda t: round(1e3 * t, 3)
+    den = got["sum_f2"] + got["sum_o2"]
+    return {"field": field, "channel": NBHD_CHANNEL, "threshold": threshold, "members": B, "calls": a.repeats, "scales": NBHD_SCALES, "wrap_x": wrap, "same_numbers": True,
+            "n_scored": [int(v) for v in got["n_scored"]], "fss": [round(float(1 - d / q), 4) if q > 0 else None for d, q in zip(got["sum_d2"], den)],
+            "neighbourhood_call_ms": {"slowest": ms(max(t_dev)), "median": ms(statistics.median(t_dev))},
+            "host_route_ms": {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_statistics_and_read_rect_median": ms(statistics.median(t_calls))},
+            "speedup_slowest": round(max(t_host) / max(t_dev), 2),
+            "points_kernel_us": round(points_us, 2), "windows_kernel_us_all_scales": round(windows_us, 2), "kernel_launches_timed": launches,
+            "windows_kernel_us_per_scale_alone": per_scale,
+            "points_kernel_gb_read_per_s": round(20 * X * Y * (B + 1) / (points_us * 1e-6) / 1e9, 1) if points_us > 0 else None,
+            "statistics_kernel_us": round(stat_us, 2), "statistics_kernel_launches_timed": stat_launches,
+            "points_kernel_over_statistics_kernel": round(points_us / stat_us, 3) if stat_us > 0 else None}
 
 
 def time_spawn(a, pkg, ens, X, Y, B):
@@ -697,6 +799,8 @@ def main():
         sys.exit("--quantiles BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.scores and (a.mode != "ensemble" or a.scores not in ("BASE_CUR", "WATER_CUR")):
         sys.exit("--scores BASE_CUR | WATER_CUR needs --mode ensemble")
+    if a.neighbourhood and (a.mode != "ensemble" or a.neighbourhood not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--neighbourhood BASE_CUR | WATER_CUR needs --mode ensemble")
     sys.path.insert(0, a.root)
     if a.share > 0:
         if "debug" not in os.environ.get("WXSIM_LIB", ""):
@@ -721,6 +825,12 @@ def main():
             ens = E.Ensemble(B + 1, X, Y)
             make_members(pkg, X, Y, B + 1, lambda i: ens[i], a.flow, 0)
             out["shapes"][spec] = {"members": B, "scores": time_scores(a, pkg, ens, X, Y, B)}
+            ens.close()
+            continue
+        if a.neighbourhood:  # B members and the truth behind them
+            ens = E.Ensemble(B + 1, X, Y)
+            make_members(pkg, X, Y, B + 1, lambda i: ens[i], a.flow, 0)
+            out["shapes"][spec] = {"members": B, "neighbourhood": time_neighbourhood(a, pkg, ens, X, Y, B)}
             ens.close()
             continue
         if a.mode == "ensemble":
