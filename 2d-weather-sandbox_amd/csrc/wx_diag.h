@@ -21,13 +21,8 @@
 #include <string.h>
 #include <algorithm>
 #include <cmath>
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXD_HD __host__ __device__
-#else // a host compiler takes the binning function and the 320-bit finish without the HIP headers (wx_ens_score_cell.h)
-#define WXD_HD
-#endif
 #include "../../include/wxsim.h"
+#include "wx_ens_cell_common.h" // (plain C++: a host compiler takes the binning function and the 320-bit finish without the HIP headers)
 
 namespace wxd {
 
@@ -43,10 +38,11 @@ struct Term {
   long long addend; // 0: nothing to add (a zero, a non-finite value, a value outside the quantity's set of cells)
 };
 
-WXD_HD inline uint32_t f32_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+using wxcell::f32_bits;
+using wxcell::f32_finite;
 
 // THE binning function: the kernel, wx_diag_accumulate and wx_diag_accumulate_cells all go through it
-WXD_HD inline Term term_of(float v, bool take)
+WX_HD inline Term term_of(float v, bool take)
 {
   const uint32_t b = f32_bits(v), e = (b >> 23) & 255u, frac = b & 0x7FFFFFu;
   const uint32_t m = e ? (frac | 0x800000u) : frac, e1 = e ? e : 1u;
@@ -55,10 +51,9 @@ WXD_HD inline Term term_of(float v, bool take)
   if (e == 255u || !take) a = 0;
   return Term{(int)(e1 >> 4), a};
 }
-WXD_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
-WXD_HD inline bool f32_nan(float v) { return (f32_bits(v) & 0x7FFFFFFFu) > 0x7F800000u; }
+WX_HD inline bool f32_nan(float v) { return (f32_bits(v) & 0x7FFFFFFFu) > 0x7F800000u; }
 // order-preserving key of a non-NaN float: a < b <=> ord(a) < ord(b); -0.0 and 0.0 share a key; never 0 and never 0xFFFFFFFF
-WXD_HD inline uint32_t ord_of(float v)
+WX_HD inline uint32_t ord_of(float v)
 {
   uint32_t b = f32_bits(v);
   if (b == 0x80000000u) b = 0;
@@ -76,7 +71,7 @@ struct CellOut {
   uint32_t kmax[8], kmin[8]; // 0: no candidate
   int cnt[7];                // C_AIR .. C_VEG
 };
-WXD_HD inline void classify(const float v[8], int wall_dist, int wall_veg, bool in, CellOut &o)
+WX_HD inline void classify(const float v[8], int wall_dist, int wall_veg, bool in, CellOut &o)
 {
   const bool wall = in && wall_dist == 0, air = in && wall_dist != 0;
   bool nfb = false, nfw = false;

@@ -20,8 +20,7 @@
 // k_ens_assim (one launch per state field with a non-zero gain). One lane per cell of the rectangle, a wave takes 64 consecutive x of
 // one row, waves grid-stride over the (row, chunk) pairs with a capped grid -- k_ens_stat's shape. Per cell the observations in order;
 // an observation that was not applied, whose row weight is 0 (wave-uniform, tested first) or whose rho is 0 in this lane is skipped.
-// Otherwise three walks over the members, as the definition says: Sx and the entry test; Cq; the write -- each with the loads of UNROLL
-// members issued before the first is consumed, the member table, the headers and e(j) read at wave-uniform addresses through the constant
+// Otherwise three walks over the members (wxe::member_walk), as the definition says: Sx and the entry test; Cq; the write -- the member table, the headers and e(j) read at wave-uniform addresses through the constant
 // address space (scalar loads; the pre-pass wrote them in an EARLIER launch), and 16-byte stores in place, only of texels whose bits
 // change. The lane re-reads its own stores for the next observation: same thread, same address, program order. 20 B read three times
 // and 16 B written per member-cell and observation in range, at most.
@@ -149,18 +148,29 @@ __global__ __launch_bounds__(OBS_WG) void k_ens_assim_obs(const ObsArgs a)
   }
 }
 
+// what pass 1 and pass 2 accumulate
+struct Sum4 {
+  double S[4];
+  bool ok[4];
+};
+struct Cov4 {
+  double Cq[4];
+};
+
 __global__ __launch_bounds__(WG) void k_ens_assim(const Args a)
 {
-  const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
+  const wxe::WaveOfGrid wg = wxe::wave_of_grid(WAVES);
+  const unsigned chunks = wxe::chunks_per_row(a.w) * (unsigned)a.h;
   const wxe::CTab tab = wxe::const_table(a.tab);
   const CHdr hdr = const_hdr(a.hdr);
   const int n = a.n_sel;
-  for (unsigned ch = wave; ch < chunks; ch += n_waves) {
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    if (x >= (unsigned)a.w) continue;
-    const int gx = a.x0 + (int)x, gy = a.y0 + (int)y;
-    const size_t off = (size_t)gy * (size_t)a.X + (size_t)gx;
+  for (unsigned ch = wg.wave; ch < chunks; ch += wg.n_waves) {
+    const wxe::Chunk at = wxe::chunk_at(ch, wg.lane, a.x0, a.y0, a.w);
+    if (!at.valid) continue;
+    const int gx = at.gx, gy = at.gy;
+    const size_t off = wxe::texel_at(a.X, gx, gy);
+    const auto load = [&](int k) { return wxe::ld_field(tab + k, off); };
+    const auto load_wall = [&](int k) { return wxe::ld_field_wall(tab + k, off); };
     for (int j = 0; j < a.n_obs; j++) {
       if (!hdr[j].applied) continue; // (uniform)
       const double wy = axis_weight(dist_y(gy, hdr[j].y), a.loc.loc_y);
@@ -171,80 +181,42 @@ __global__ __launch_bounds__(WG) void k_ens_assim(const Args a)
       p.hm = hdr[j].p.hm, p.V = hdr[j].p.V, p.D = hdr[j].p.D, p.innovation = hdr[j].p.innovation, p.alpha = hdr[j].p.alpha;
       const CE e = const_e(a.e) + (size_t)j * (size_t)n;
       // pass 1: Sx and the entry test
-      double S[4] = {0.0, 0.0, 0.0, 0.0};
-      bool ok[4] = {true, true, true, true};
-      int k = 0;
-      for (; k + UNROLL <= n; k += UNROLL) { // the loads of UNROLL members are issued before the first of them is consumed
-        wxe::f32x4 v[UNROLL];
-        int wd[UNROLL];
-#pragma unroll
-        for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
-        WX_ENS_LOADS_ISSUED();
-#pragma unroll
-        for (int i = 0; i < UNROLL; i++) {
-          const bool air = wd[i] != 0;
-          sum_add(S[0], ok[0], v[i].x, air), sum_add(S[1], ok[1], v[i].y, air), sum_add(S[2], ok[2], v[i].z, air), sum_add(S[3], ok[3], v[i].w, air);
-        }
-      }
-      for (; k < n; k++) {
-        const wxe::f32x4 v = wxe::ld_field(tab + k, off);
-        const bool air = wxe::ld_wall_dist(tab + k, off) != 0;
-        sum_add(S[0], ok[0], v.x, air), sum_add(S[1], ok[1], v.y, air), sum_add(S[2], ok[2], v.z, air), sum_add(S[3], ok[3], v.w, air);
-      }
-      double xm[4], Cq[4] = {0.0, 0.0, 0.0, 0.0};
-      bool any = false;
+      const Sum4 s = wxe::member_walk<UNROLL>(n, Sum4{{0.0, 0.0, 0.0, 0.0}, {true, true, true, true}}, load_wall, [](Sum4 &q, int, const wxe::TexelWall &m) {
+        const bool air = m.wd != 0;
+        sum_add(q.S[0], q.ok[0], m.v.x, air), sum_add(q.S[1], q.ok[1], m.v.y, air), sum_add(q.S[2], q.ok[2], m.v.z, air), sum_add(q.S[3], q.ok[3], m.v.w, air);
+      });
+      double xm[4];
+      bool ok[4], any = false;
 #pragma unroll
       for (int c = 0; c < 4; c++) {
-        ok[c] = ok[c] && a.gain[c] != 0.0f;
-        xm[c] = S[c] / (double)n;
+        ok[c] = s.ok[c] && a.gain[c] != 0.0f;
+        xm[c] = s.S[c] / (double)n;
         any = any || ok[c];
       }
       if (!any) continue;
       // pass 2: Cq
-      for (k = 0; k + UNROLL <= n; k += UNROLL) {
-        wxe::f32x4 v[UNROLL];
-#pragma unroll
-        for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off);
-        WX_ENS_LOADS_ISSUED();
-#pragma unroll
-        for (int i = 0; i < UNROLL; i++) {
-          const double ek = e[k + i];
-          cov_add(Cq[0], v[i].x, xm[0], ek), cov_add(Cq[1], v[i].y, xm[1], ek), cov_add(Cq[2], v[i].z, xm[2], ek), cov_add(Cq[3], v[i].w, xm[3], ek);
-        }
-      }
-      for (; k < n; k++) {
-        const wxe::f32x4 v = wxe::ld_field(tab + k, off);
+      const Cov4 cq = wxe::member_walk<UNROLL>(n, Cov4{{0.0, 0.0, 0.0, 0.0}}, load, [&](Cov4 &q, int k, const wxe::f32x4 &v) {
         const double ek = e[k];
-        cov_add(Cq[0], v.x, xm[0], ek), cov_add(Cq[1], v.y, xm[1], ek), cov_add(Cq[2], v.z, xm[2], ek), cov_add(Cq[3], v.w, xm[3], ek);
-      }
+        cov_add(q.Cq[0], v.x, xm[0], ek), cov_add(q.Cq[1], v.y, xm[1], ek), cov_add(q.Cq[2], v.z, xm[2], ek), cov_add(q.Cq[3], v.w, xm[3], ek);
+      });
       Gain g[4];
       any = false;
 #pragma unroll
       for (int c = 0; c < 4; c++) {
-        g[c] = gain_of(ok[c], Cq[c], n, (double)a.gain[c] * rho, p);
+        g[c] = gain_of(ok[c], cq.Cq[c], n, (double)a.gain[c] * rho, p);
         any = any || g[c].on;
       }
       if (!any) continue;
       // pass 3: the write; a texel whose bits do not change is not stored
-      auto write = [&](int m, const wxe::f32x4 v) {
-        const double ek = e[m];
+      wxe::member_walk<UNROLL>(n, wxe::Nothing{}, load, [&](wxe::Nothing &, int k, const wxe::f32x4 &v) {
+        const double ek = e[k];
         wxe::f32x4 o;
         o.x = g[0].on ? post_value(v.x, g[0], ek, a.lo[0], a.hi[0]) : v.x;
         o.y = g[1].on ? post_value(v.y, g[1], ek, a.lo[1], a.hi[1]) : v.y;
         o.z = g[2].on ? post_value(v.z, g[2], ek, a.lo[2], a.hi[2]) : v.z;
         o.w = g[3].on ? post_value(v.w, g[3], ek, a.lo[3], a.hi[3]) : v.w;
-        if (f32_bits(o.x) != f32_bits(v.x) || f32_bits(o.y) != f32_bits(v.y) || f32_bits(o.z) != f32_bits(v.z) || f32_bits(o.w) != f32_bits(v.w))
-          wxp::st_field(tab + m, off, o);
-      };
-      for (k = 0; k + UNROLL <= n; k += UNROLL) {
-        wxe::f32x4 v[UNROLL];
-#pragma unroll
-        for (int i = 0; i < UNROLL; i++) v[i] = wxe::ld_field(tab + k + i, off);
-        WX_ENS_LOADS_ISSUED();
-#pragma unroll
-        for (int i = 0; i < UNROLL; i++) write(k + i, v[i]);
-      }
-      for (; k < n; k++) write(k, wxe::ld_field(tab + k, off));
+        if (wxcell::texel_changed(o, v)) wxp::st_field(tab + k, off, o);
+      });
     }
   }
 }

@@ -11,34 +11,19 @@
 #include <string.h>
 #include "../../include/wxsim.h"
 #include "wx_rounded.h"
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXA_HD __host__ __device__
-#else
-#define WXA_HD
-#endif
+#include "wx_ens_cell_common.h"
 #include <vector>
 
 namespace wxa {
 
 using wxr::rounded;
 
-WXA_HD inline uint32_t f32_bits(float v)
-{
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  return u;
-}
-WXA_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
-WXA_HD inline bool f64_finite(double v)
-{
-  uint64_t u;
-  memcpy(&u, &v, 8);
-  return ((u >> 52) & 2047u) != 2047u;
-}
+using wxcell::f32_bits;
+using wxcell::f32_finite;
+using wxcell::f64_finite;
 
 // Gaspari and Cohn's fifth-order piecewise rational function of z = distance / half-width (z >= 0), by Horner
-WXA_HD inline double gc(double z)
+WX_HD inline double gc(double z)
 {
 #pragma clang fp contract(off)
   if (z >= 2.0) return 0.0;
@@ -65,19 +50,19 @@ struct Loc {
   int X, wrap_x;
   float loc_x, loc_y;
 };
-WXA_HD inline double axis_weight(int d, float loc)
+WX_HD inline double axis_weight(int d, float loc)
 {
 #pragma clang fp contract(off)
   return loc == 0.0f ? 1.0 : gc((double)d / (double)loc);
 }
-WXA_HD inline int dist_x(const Loc &l, int x, int ox)
+WX_HD inline int dist_x(const Loc &l, int x, int ox)
 {
   int dx = x > ox ? x - ox : ox - x;
   if (l.wrap_x && l.X - dx < dx) dx = l.X - dx;
   return dx;
 }
-WXA_HD inline int dist_y(int y, int oy) { return y > oy ? y - oy : oy - y; }
-WXA_HD inline double rho_of(const Loc &l, int x, int y, int ox, int oy)
+WX_HD inline int dist_y(int y, int oy) { return y > oy ? y - oy : oy - y; }
+WX_HD inline double rho_of(const Loc &l, int x, int y, int ox, int oy)
 {
 #pragma clang fp contract(off)
   return axis_weight(dist_x(l, x, ox), l.loc_x) * axis_weight(dist_y(y, oy), l.loc_y);
@@ -89,7 +74,7 @@ struct Prior {
 };
 
 // t: the n selected members' values of the observed channel, member order; every t_k finite
-WXA_HD inline Prior prior_of(int n, const float *t, float value, float error_var)
+WX_HD inline Prior prior_of(int n, const float *t, float value, float error_var)
 {
 #pragma clang fp contract(off)
   Prior p;
@@ -109,15 +94,10 @@ WXA_HD inline Prior prior_of(int n, const float *t, float value, float error_var
 }
 
 // ---- one channel of one cell, member by member (the kernel keeps four of each; selects, not branches, as wx_ens_stat.h's cell_add) ----
-// pass 1: Sx, and whether every member's value may enter
-WXA_HD inline void sum_add(double &S, bool &ok, float x, bool air)
-{
-#pragma clang fp contract(off)
-  ok = ok && air && f32_finite(x);
-  S = S + (double)x;
-}
+// pass 1: Sx, and whether every member's value may enter (wx_ens_cell_common.h)
+using wxcell::sum_add;
 // pass 2: Cq
-WXA_HD inline void cov_add(double &Cq, float x, double xm, double e)
+WX_HD inline void cov_add(double &Cq, float x, double xm, double e)
 {
 #pragma clang fp contract(off)
   const double d = (double)x - xm;
@@ -128,7 +108,7 @@ struct Gain {
   double a, b;
   bool on;
 };
-WXA_HD inline Gain gain_of(bool ok, double Cq, int n, double w, const Prior &p)
+WX_HD inline Gain gain_of(bool ok, double Cq, int n, double w, const Prior &p)
 {
 #pragma clang fp contract(off)
   const double C = Cq / (double)(n - 1);
@@ -140,7 +120,7 @@ WXA_HD inline Gain gain_of(bool ok, double Cq, int n, double w, const Prior &p)
   return g;
 }
 // pass 3: the member's new value, or x itself (bit for bit)
-WXA_HD inline float post_value(float x, const Gain &g, double e, float lo, float hi)
+WX_HD inline float post_value(float x, const Gain &g, double e, float lo, float hi)
 {
 #pragma clang fp contract(off)
   const double be = rounded(g.b * e);
@@ -154,7 +134,7 @@ WXA_HD inline float post_value(float x, const Gain &g, double e, float lo, float
 // The whole walk over an array: x[0 .. n) the members' values of one channel of one cell that is an air cell in all of them, t / p the
 // observation's values and header, w = (double)gain * rho (gain != 0, rho != 0). Returns whether any bits changed. The host entry
 // point and the observation-space pre-pass of the device (on its working copies of the observed channels) both call this.
-WXA_HD inline bool update_channel(int n, float *x, const float *t, const Prior &p, double w, float lo, float hi)
+WX_HD inline bool update_channel(int n, float *x, const float *t, const Prior &p, double w, float lo, float hi)
 {
 #pragma clang fp contract(off)
   double S = 0.0;
@@ -175,7 +155,7 @@ WXA_HD inline bool update_channel(int n, float *x, const float *t, const Prior &
   return changed;
 }
 
-WXA_HD inline bool in_rect(const wx_ens_assim &a, int x, int y) { return x >= a.x && x < a.x + a.w && y >= a.y && y < a.y + a.h; }
+WX_HD inline bool in_rect(const wx_ens_assim &a, int x, int y) { return x >= a.x && x < a.x + a.w && y >= a.y && y < a.y + a.h; }
 
 // the argument checks wx_ensemble_assimilate and wx_ens_assim_cells share (nothing here touches a device)
 inline int check_desc(const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs, int X, int Y, const char **why)
@@ -221,12 +201,12 @@ inline int check_desc(const wx_ens_assim *a, int n_obs, const wx_ens_obs *obs, i
   return WX_OK;
 }
 
-WXA_HD inline void result_skipped(wx_ens_obs_result &r)
+WX_HD inline void result_skipped(wx_ens_obs_result &r)
 {
   r.applied = 0, r.pad = 0;
   r.prior_mean = r.prior_var = r.innovation = r.alpha = (double)__builtin_nanf("");
 }
-WXA_HD inline void result_applied(wx_ens_obs_result &r, const Prior &p)
+WX_HD inline void result_applied(wx_ens_obs_result &r, const Prior &p)
 {
   r.applied = 1, r.pad = 0;
   r.prior_mean = p.hm, r.prior_var = p.V, r.innovation = p.innovation, r.alpha = p.alpha;

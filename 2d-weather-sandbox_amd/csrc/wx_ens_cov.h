@@ -14,7 +14,8 @@
 // k_ens_cov<SOURCE, NP>. k_ens_inflate's shape: one lane per cell of the rectangle, a wave takes 64 consecutive x of one row, waves
 // grid-stride over the (row, chunk) pairs with a capped grid. Walk 1: Sx and the entry test (16 B field or snapshot + 4 B wall). A cell
 // none of whose channels is eligible stores its NaNs and ends there. Walk 2: Qx and the NP Cq_j (16 B, the same lines again: L2, one expects). Each
-// walk has the loads of UNROLL members issued before the first is consumed; the member table, the headers and e[j][k] are read at
+// walk has the loads of UNROLL members issued before the first is consumed -- written out here, not wxe::member_walk: through the
+// template four instantiations need more registers and one is slower ("One member walk") --; the member table, the headers and e[j][k] are read at
 // wave-uniform addresses through the constant address space (scalar loads; the pre-pass wrote them in an EARLIER launch). Only the
 // wanted planes are stored, 16 B per lane. No LDS, no atomics, no device-side waiting. The template on the source keeps the snapshot
 // address arithmetic out of CURRENT; the template on the bucket NP = 1 / 2 / 4 / 8 of n_pred sizes the accumulators (4 NP doubles):
@@ -125,8 +126,8 @@ template <int SOURCE, int NP>
 __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
 {
   constexpr bool PRIOR = SOURCE == WX_COV_SOURCE_PRIOR;
-  const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
+  const wxe::WaveOfGrid wg = wxe::wave_of_grid(WAVES);
+  const unsigned chunks = wxe::chunks_per_row(a.w) * (unsigned)a.h;
   const wxe::CTab tab = wxe::const_table(a.tab);
   const CHdr hdr = const_hdr(a.hdr);
   const CE e = const_e(a.e);
@@ -134,13 +135,12 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
   const size_t pstride = PRIOR ? (size_t)a.pw * (size_t)a.ph : 0; // texels per member of the snapshot
   const size_t plane = (size_t)a.w * (size_t)a.h;
   const float nanf = __builtin_nanf("");
-  auto ld_x = [&](int k, size_t off, size_t poff) { return PRIOR ? wxi::ld_prior(a.prior, (size_t)k * pstride + poff) : wxe::ld_field(tab + k, off); };
-  for (unsigned ch = wave; ch < chunks; ch += n_waves) {
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    if (x >= (unsigned)a.w) continue;
-    const int gx = a.x0 + (int)x, gy = a.y0 + (int)y;
-    const size_t off = (size_t)gy * (size_t)a.X + (size_t)gx, o = (size_t)y * (size_t)a.w + x;
-    const size_t poff = PRIOR ? (size_t)(gy - a.py0) * (size_t)a.pw + (size_t)(gx - a.px0) : 0;
+  for (unsigned ch = wg.wave; ch < chunks; ch += wg.n_waves) {
+    const wxe::Chunk at = wxe::chunk_at(ch, wg.lane, a.x0, a.y0, a.w);
+    if (!at.valid) continue;
+    const size_t off = wxe::texel_at(a.X, at.gx, at.gy), o = wxe::plane_at(a.w, at.x, at.y);
+    const size_t poff = PRIOR ? (size_t)(at.gy - a.py0) * (size_t)a.pw + (size_t)(at.gx - a.px0) : 0;
+    const auto ld_x = [&](int k) { return PRIOR ? wxi::ld_prior(a.prior, (size_t)k * pstride + poff) : wxe::ld_field(tab + k, off); };
     // walk 1: Sx and the entry test
     double S[4] = {0.0, 0.0, 0.0, 0.0};
     bool ok[4] = {true, true, true, true};
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
       wxe::f32x4 v[UNROLL];
       int wd[UNROLL];
 #pragma unroll
-      for (int i = 0; i < UNROLL; i++) v[i] = ld_x(k + i, off, poff), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
+      for (int i = 0; i < UNROLL; i++) v[i] = ld_x(k + i), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
       WX_ENS_LOADS_ISSUED();
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) {
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
       }
     }
     for (; k < n; k++) {
-      const wxe::f32x4 v = ld_x(k, off, poff);
+      const wxe::f32x4 v = ld_x(k);
       const bool air = wxe::ld_wall_dist(tab + k, off) != 0;
       sum_add(S[0], ok[0], v.x, air), sum_add(S[1], ok[1], v.y, air), sum_add(S[2], ok[2], v.z, air), sum_add(S[3], ok[3], v.w, air);
     }
@@ -191,12 +191,12 @@ __global__ __launch_bounds__(WG) void k_ens_cov(const Args a)
     for (k = 0; k + UNROLL <= n; k += UNROLL) {
       wxe::f32x4 v[UNROLL];
 #pragma unroll
-      for (int i = 0; i < UNROLL; i++) v[i] = ld_x(k + i, off, poff);
+      for (int i = 0; i < UNROLL; i++) v[i] = ld_x(k + i);
       WX_ENS_LOADS_ISSUED();
 #pragma unroll
       for (int i = 0; i < UNROLL; i++) take(k + i, v[i]);
     }
-    for (; k < n; k++) take(k, ld_x(k, off, poff));
+    for (; k < n; k++) take(k, ld_x(k));
     if (a.variance) {
       o_var.x = ok[0] ? variance_of(Qx[0], n) : nanf, o_var.y = ok[1] ? variance_of(Qx[1], n) : nanf;
       o_var.z = ok[2] ? variance_of(Qx[2], n) : nanf, o_var.w = ok[3] ? variance_of(Qx[3], n) : nanf;

@@ -11,32 +11,17 @@
 #include <string.h>
 #include "../../include/wxsim.h"
 #include "wx_rounded.h"
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXC_HD __host__ __device__
-#else
-#define WXC_HD
-#endif
+#include "wx_ens_cell_common.h"
 #include <vector>
 
 namespace wxc {
 
 using wxr::rounded;
 
-WXC_HD inline uint32_t f32_bits(float v)
-{
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  return u;
-}
-WXC_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
-WXC_HD inline bool f64_finite(double v)
-{
-  uint64_t u;
-  memcpy(&u, &v, 8);
-  return ((u >> 52) & 2047u) != 2047u;
-}
-WXC_HD inline double f64_nan() { return (double)__builtin_nanf(""); }
+using wxcell::f32_bits;
+using wxcell::f32_finite;
+using wxcell::f64_finite;
+WX_HD inline double f64_nan() { return (double)__builtin_nanf(""); }
 
 // ---- a predictor: the chain over its n values t[0 .. n), member order ----
 struct Pred {
@@ -45,7 +30,7 @@ struct Pred {
 };
 // t: one double per selected member (a point's value converted, or the host's number); a t that is not finite makes the predictor
 // invalid (the caller turns "wall in this member" into such a t). e[0 .. n) receives e_k = t_k - jm (0 if invalid); e may be t.
-WXC_HD inline Pred pred_of(int n, const double *t, double *e)
+WX_HD inline Pred pred_of(int n, const double *t, double *e)
 {
 #pragma clang fp contract(off)
   Pred p;
@@ -71,7 +56,7 @@ WXC_HD inline Pred pred_of(int n, const double *t, double *e)
   p.Q = Q;
   return p;
 }
-WXC_HD inline void result_of(wx_ens_cov_result &r, const Pred &p, int n)
+WX_HD inline void result_of(wx_ens_cov_result &r, const Pred &p, int n)
 {
 #pragma clang fp contract(off)
   r.valid = p.valid ? 1 : 0, r.pad = 0;
@@ -80,46 +65,41 @@ WXC_HD inline void result_of(wx_ens_cov_result &r, const Pred &p, int n)
 }
 
 // ---- one channel of one cell, member by member (the kernel keeps four of each; selects, not branches, as wx_ens_stat.h's cell_add) ----
-// walk 1: Sx, and whether every member's value may enter
-WXC_HD inline void sum_add(double &S, bool &ok, float x, bool air)
-{
-#pragma clang fp contract(off)
-  ok = ok && air && f32_finite(x);
-  S = S + (double)x;
-}
+// walk 1: Sx, and whether every member's value may enter (wx_ens_cell_common.h)
+using wxcell::sum_add;
 // walk 2: Qx and one Cq_j per predictor, from the same d_k
-WXC_HD inline double dev_of(float x, double xm)
+WX_HD inline double dev_of(float x, double xm)
 {
 #pragma clang fp contract(off)
   return (double)x - xm;
 }
-WXC_HD inline void q_add(double &Q, double d)
+WX_HD inline void q_add(double &Q, double d)
 {
 #pragma clang fp contract(off)
   Q = Q + rounded(d * d);
 }
-WXC_HD inline void c_add(double &Cq, double d, double e)
+WX_HD inline void c_add(double &Cq, double d, double e)
 {
 #pragma clang fp contract(off)
   Cq = Cq + rounded(d * e);
 }
 // the finishers (a double beyond the float range converts to +-Inf)
-WXC_HD inline float variance_of(double Qx, int n)
+WX_HD inline float variance_of(double Qx, int n)
 {
 #pragma clang fp contract(off)
   return (float)(Qx / (double)(n - 1));
 }
-WXC_HD inline float cov_of(double Cq, int n)
+WX_HD inline float cov_of(double Cq, int n)
 {
 #pragma clang fp contract(off)
   return (float)(Cq / (double)(n - 1));
 }
-WXC_HD inline float slope_of(double Cq, double Qx)
+WX_HD inline float slope_of(double Cq, double Qx)
 {
 #pragma clang fp contract(off)
   return Qx == 0.0 ? __builtin_nanf("") : (float)(Cq / Qx);
 }
-WXC_HD inline float corr_of(double Cq, double Qx, double Qj)
+WX_HD inline float corr_of(double Cq, double Qx, double Qj)
 {
 #pragma clang fp contract(off)
   const double den = __builtin_sqrt(rounded(Qx * Qj));
@@ -132,7 +112,7 @@ WXC_HD inline float corr_of(double Cq, double Qx, double Qj)
 
 // The whole walk over an array: x[0 .. n) the members' values of one channel of one cell, air: the cell is an air cell in all of them,
 // p[j] / e[j * n + k] the predictors. variance: one float or NULL; cov / corr / slope: n_pred floats each or NULL.
-WXC_HD inline void cov_channel(int n, const float *x, bool air, int n_pred, const Pred *p, const double *e, float *variance, float *cov, float *corr,
+WX_HD inline void cov_channel(int n, const float *x, bool air, int n_pred, const Pred *p, const double *e, float *variance, float *cov, float *corr,
                                float *slope)
 {
 #pragma clang fp contract(off)

@@ -1,6 +1,6 @@
 // wx_ens_frame.h -- what every member-axis call of an ensemble (wx_ensemble_statistics, _perturb, _quantiles, _scores, _assimilate,
-// _prior_save, _inflate, _covariance) shares: the member table and its device-side accessors, the ensemble's staging buffers, and the
-// host frame of a call. Included at the end of wxsim.hip behind wx_ensemble.h and in front of the wx_ens_*.h call headers; the
+// _prior_save, _inflate, _covariance, _neighbourhood) shares: the member table and its device-side accessors, the chunk cursor and the
+// member walk of the kernels, the ensemble's staging buffers, and the host frame of a call. Included at the end of wxsim.hip behind wx_ensemble.h and in front of the wx_ens_*.h call headers; the
 // definition headers (wx_ens_*_cell.h) and the host-only test drivers do not include it: it needs HIP.
 //
 // A call is five parts: its own argument checks, in its own order (the pieces below are used where two calls refuse with the same
@@ -55,6 +55,75 @@ __device__ __forceinline__ f32x4 ld_field(CTab m, size_t off) { return f32x4{m->
 __device__ __forceinline__ int ld_wall_dist(CTab m, size_t off) { return m->wall[off].y; }
 #define WX_ENS_LOADS_ISSUED() ((void)0)
 #endif
+
+// ---- the chunk cursor: where a lane stands ----
+// The items of a rectangle are its chunks of 64 consecutive x of one row, row-major (ens_chunks: below 2^31, 16 Ki chunks per row x
+// 64 Ki rows); lane l of whoever takes chunk ch -- a wave, or the four waves of a workgroup alike -- stands on cell (x, y) of the
+// rectangle. A lane past the ragged edge (x >= w) is not valid: its offsets are numbers, not places to touch.
+struct Chunk {
+  unsigned x, y; // the cell in the rectangle
+  int gx, gy;    // the cell in the grid
+  bool valid;
+};
+__device__ __forceinline__ unsigned chunks_per_row(int w) { return ((unsigned)w + 63u) / 64u; }
+__device__ __forceinline__ Chunk chunk_at(unsigned ch, unsigned lane, int x0, int y0, int w)
+{
+  const unsigned cpr = chunks_per_row(w);
+  Chunk c;
+  c.y = ch / cpr, c.x = (ch - c.y * cpr) * 64u + lane;
+  c.valid = c.x < (unsigned)w;
+  c.gx = x0 + (int)c.x, c.gy = y0 + (int)c.y;
+  return c;
+}
+// item `it` of n_members x chunks (member, chunk) pairs, member-major (a 64-bit count): the member into k
+__device__ __forceinline__ Chunk member_chunk_at(unsigned long long it, unsigned lane, int x0, int y0, int w, int h, unsigned &k)
+{
+  const unsigned per_member = chunks_per_row(w) * (unsigned)h;
+  k = (unsigned)(it / per_member);
+  return chunk_at((unsigned)(it - (unsigned long long)k * per_member), lane, x0, y0, w);
+}
+// The two offsets of a cell: its texel in a member's array of X cells per row, and in a w * h plane of the rectangle. Functions, not
+// fields of the cursor: they are computed where they are asked for -- behind the valid test.
+__device__ __forceinline__ size_t texel_at(int X, int gx, int gy) { return (size_t)gy * (size_t)X + (size_t)gx; }
+__device__ __forceinline__ size_t plane_at(int w, unsigned x, unsigned y) { return (size_t)y * (size_t)w + x; }
+// a wave of a grid of `waves`-wave workgroups that grid-strides over items: its lane, its first item, its stride
+struct WaveOfGrid {
+  unsigned lane, wave, n_waves;
+};
+__device__ __forceinline__ WaveOfGrid wave_of_grid(unsigned waves) { return WaveOfGrid{threadIdx.x & 63u, blockIdx.x * waves + (threadIdx.x >> 6), gridDim.x * waves}; }
+
+// ---- the member walk ----
+// Per cell a walk over the members is serial BY DEFINITION (a dependent double add chain per channel, member 0 first), so what a
+// kernel can do about latency is to have the loads of UNROLL members in flight before the first is consumed: `load(k)` returns what
+// member k's step needs from memory, a group's loads are issued, then `take(acc, k, loaded)` consumes them in member order (the
+// compiler's counted s_waitcnt vmcnt(N) in front of each consumer), and the remainder (n % UNROLL members) goes one by one through the
+// same two. The walk OWNS what it accumulates -- acc goes in and comes back by value -- and that is not a matter of taste: with the
+// accumulator behind a reference the optimiser unrolls the group before it has turned the consumer's short-circuit tests into selects,
+// and the last member of k_ens_stat's group keeps four branches ("One member walk"). `take` is meant to stay
+// free of branches: a group is one basic block (wx_ens_stat.h, over cell_add). A walk that only writes passes Nothing.
+// k_ens_inflate and k_ens_cov keep their walks written out: through this template they need more registers (same place).
+struct Nothing {};
+template <int UNROLL, class Acc, class Load, class Take>
+__device__ __forceinline__ Acc member_walk(int n, Acc acc, const Load &load, const Take &take)
+{
+  int k = 0;
+  for (; k + UNROLL <= n; k += UNROLL) {
+    decltype(load(0)) m[UNROLL];
+#pragma unroll
+    for (int i = 0; i < UNROLL; i++) m[i] = load(k + i);
+    WX_ENS_LOADS_ISSUED();
+#pragma unroll
+    for (int i = 0; i < UNROLL; i++) take(acc, k + i, m[i]);
+  }
+  for (; k < n; k++) take(acc, k, load(k));
+  return acc;
+}
+// what most walks load: a member's texel, and its wall texel's channel 1 with it
+struct TexelWall {
+  f32x4 v;
+  int wd;
+};
+__device__ __forceinline__ TexelWall ld_field_wall(CTab m, size_t off) { return TexelWall{ld_field(m, off), ld_wall_dist(m, off)}; }
 #endif // __HIPCC__
 
 } // namespace wxe

@@ -5,12 +5,13 @@
 //
 // k_ens_prior_save. The snapshot the relaxation modes read: the rectangle of one field of every selected member into one buffer laid
 // out [k][h][w] float4. k_ens_perturb's walk: one lane per cell, waves grid-stride over the (member, row, 64-column chunk) triples with
-// a capped grid. 16 B read and 16 B written per member-cell.
+// a capped grid (its head written out, not wxe::member_chunk_at: DESIGN.md section 4, "One member walk"). 16 B read and 16 B written per member-cell.
 //
 // k_ens_inflate<MODE>. k_ens_assim's shape without the observation loop: one lane per cell of the rectangle, a wave takes 64
 // consecutive x of one row, waves grid-stride over the (row, chunk) pairs with a capped grid. Per cell the walks over the members that
-// the definition names, each with the loads of UNROLL members issued before the first is consumed, the member table read at
-// wave-uniform addresses through the constant address space, and 16-byte stores in place, only of texels whose bits change:
+// the definition names, each with the loads of UNROLL members issued before the first is consumed (written out here, not
+// wxe::member_walk: through the template the RTPS instantiation spills scalar registers; DESIGN.md section 4, "One member walk"), the
+// member table read at wave-uniform addresses through the constant address space, and 16-byte stores in place, only of texels whose bits change:
 //   CONST  walk 1: S and the entry test (16 B field + 4 B wall)        walk 2: the write (16 B read, 16 B written)
 //   RTPS   walk 1: S, Sb and the entry test (16 + 4 + 16 B snapshot)   walk 2: Qa, Qb (16 + 16 B)   walk 3: the write (16 B, 16 B)
 //   RTPP   walk 1: S, Sb and the entry test (16 + 4 + 16 B)            walk 2: the write (16 + 16 B read, 16 B written)
@@ -71,17 +72,16 @@ template <int MODE>
 __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
 {
   constexpr bool RELAX = MODE != WX_INFLATE_CONST;
-  const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
+  const wxe::WaveOfGrid wg = wxe::wave_of_grid(WAVES);
+  const unsigned chunks = wxe::chunks_per_row(a.w) * (unsigned)a.h;
   const wxe::CTab tab = wxe::const_table(a.tab);
   const int n = a.n_sel;
   const size_t pstride = RELAX ? (size_t)a.pw * (size_t)a.ph : 0; // texels per member of the snapshot
-  for (unsigned ch = wave; ch < chunks; ch += n_waves) {
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    if (x >= (unsigned)a.w) continue;
-    const int gx = a.x0 + (int)x, gy = a.y0 + (int)y;
-    const size_t off = (size_t)gy * (size_t)a.X + (size_t)gx;
-    const size_t poff = RELAX ? (size_t)(gy - a.py0) * (size_t)a.pw + (size_t)(gx - a.px0) : 0;
+  for (unsigned ch = wg.wave; ch < chunks; ch += wg.n_waves) {
+    const wxe::Chunk at = wxe::chunk_at(ch, wg.lane, a.x0, a.y0, a.w);
+    if (!at.valid) continue;
+    const size_t off = wxe::texel_at(a.X, at.gx, at.gy);
+    const size_t poff = RELAX ? (size_t)(at.gy - a.py0) * (size_t)a.pw + (size_t)(at.gx - a.px0) : 0;
     Lambda l[4];
 #pragma unroll
     for (int c = 0; c < 4; c++) l[c] = lambda_tail(false, 1.0);
@@ -129,8 +129,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
           o.y = ok[1] ? post_rtpp(v.y, p.y, m[1], mb[1], ca[1], cg[1], a.lo[1], a.hi[1]) : v.y;
           o.z = ok[2] ? post_rtpp(v.z, p.z, m[2], mb[2], ca[2], cg[2], a.lo[2], a.hi[2]) : v.z;
           o.w = ok[3] ? post_rtpp(v.w, p.w, m[3], mb[3], ca[3], cg[3], a.lo[3], a.hi[3]) : v.w;
-          if (f32_bits(o.x) != f32_bits(v.x) || f32_bits(o.y) != f32_bits(v.y) || f32_bits(o.z) != f32_bits(v.z) || f32_bits(o.w) != f32_bits(v.w))
-            wxp::st_field(tab + mi, off, o);
+          if (wxcell::texel_changed(o, v)) wxp::st_field(tab + mi, off, o);
         };
         for (k = 0; k + UNROLL <= n; k += UNROLL) {
           wxe::f32x4 v[UNROLL], p[UNROLL];
@@ -175,8 +174,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
             o.y = l[1].on ? post_scale(v.y, m[1], l[1].v, a.lo[1], a.hi[1]) : v.y;
             o.z = l[2].on ? post_scale(v.z, m[2], l[2].v, a.lo[2], a.hi[2]) : v.z;
             o.w = l[3].on ? post_scale(v.w, m[3], l[3].v, a.lo[3], a.hi[3]) : v.w;
-            if (f32_bits(o.x) != f32_bits(v.x) || f32_bits(o.y) != f32_bits(v.y) || f32_bits(o.z) != f32_bits(v.z) || f32_bits(o.w) != f32_bits(v.w))
-              wxp::st_field(tab + mi, off, o);
+            if (wxcell::texel_changed(o, v)) wxp::st_field(tab + mi, off, o);
           };
           for (k = 0; k + UNROLL <= n; k += UNROLL) {
             wxe::f32x4 v[UNROLL];
@@ -193,7 +191,7 @@ __global__ __launch_bounds__(WG) void k_ens_inflate(const Args a)
     if (a.lambda_out) { // (uniform; never with RTPP)
       wxe::f32x4 lf;
       lf.x = lambda_float(l[0]), lf.y = lambda_float(l[1]), lf.z = lambda_float(l[2]), lf.w = lambda_float(l[3]);
-      st_texel(a.lambda_out, (size_t)y * (size_t)a.w + x, lf);
+      st_texel(a.lambda_out, wxe::plane_at(a.w, at.x, at.y), lf);
     }
   }
 }

@@ -11,52 +11,32 @@
 #include <string.h>
 #include "../../include/wxsim.h"
 #include "wx_rounded.h"
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXI_HD __host__ __device__
-#else
-#define WXI_HD
-#endif
+#include "wx_ens_cell_common.h"
 #include <vector>
 
 namespace wxi {
 
 using wxr::rounded;
 
-WXI_HD inline uint32_t f32_bits(float v)
-{
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  return u;
-}
-WXI_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
-WXI_HD inline bool f64_finite(double v)
-{
-  uint64_t u;
-  memcpy(&u, &v, 8);
-  return ((u >> 52) & 2047u) != 2047u;
-}
+using wxcell::f32_bits;
+using wxcell::f32_finite;
+using wxcell::f64_finite;
 
 // a channel whose coefficient is neutral is not looked at
-WXI_HD inline bool neutral(int mode, float coef) { return mode == WX_INFLATE_CONST ? coef == 1.0f : coef == 0.0f; }
+WX_HD inline bool neutral(int mode, float coef) { return mode == WX_INFLATE_CONST ? coef == 1.0f : coef == 0.0f; }
 
 // ---- one channel of one cell, member by member (the kernel keeps four of each; selects, not branches, as wx_ens_stat.h's cell_add) ----
-// walk 1: S, and whether every member's value may enter
-WXI_HD inline void sum_add(double &S, bool &ok, float x, bool air)
-{
-#pragma clang fp contract(off)
-  ok = ok && air && f32_finite(x);
-  S = S + (double)x;
-}
+// walk 1: S, and whether every member's value may enter (wx_ens_cell_common.h)
+using wxcell::sum_add;
 // walk 1, the relaxation modes: Sb over the snapshot
-WXI_HD inline void prior_add(double &Sb, bool &ok, float p)
+WX_HD inline void prior_add(double &Sb, bool &ok, float p)
 {
 #pragma clang fp contract(off)
   ok = ok && f32_finite(p);
   Sb = Sb + (double)p;
 }
 // walk 2 (RTPS): Qa about m, Qb about mb
-WXI_HD inline void q_add(double &Q, float v, double mean)
+WX_HD inline void q_add(double &Q, float v, double mean)
 {
 #pragma clang fp contract(off)
   const double d = (double)v - mean;
@@ -69,14 +49,14 @@ struct Lambda {
   bool on;
 };
 // the common tail: a factor that is not finite, or is 1, changes nothing
-WXI_HD inline Lambda lambda_tail(bool ok, double lam)
+WX_HD inline Lambda lambda_tail(bool ok, double lam)
 {
   Lambda l;
   l.v = lam;
   l.on = ok && f64_finite(lam) && lam != 1.0;
   return l;
 }
-WXI_HD inline Lambda lambda_rtps(bool ok, double Qa, double Qb, int n, float alpha, float lam_lo, float lam_hi)
+WX_HD inline Lambda lambda_rtps(bool ok, double Qa, double Qb, int n, float alpha, float lam_lo, float lam_hi)
 {
 #pragma clang fp contract(off)
   const double sa = __builtin_sqrt(Qa / (double)(n - 1)), sb = __builtin_sqrt(Qb / (double)(n - 1));
@@ -87,17 +67,17 @@ WXI_HD inline Lambda lambda_rtps(bool ok, double Qa, double Qb, int n, float alp
   if (lam_hi == lam_hi && lam > (double)lam_hi) lam = (double)lam_hi;
   return lambda_tail(ok, lam);
 }
-WXI_HD inline float lambda_float(const Lambda &l) { return l.on ? (float)l.v : __builtin_nanf(""); }
+WX_HD inline float lambda_float(const Lambda &l) { return l.on ? (float)l.v : __builtin_nanf(""); }
 
 // wx_ens_perturb's clamp; a result that is not finite keeps the member's bits
-WXI_HD inline float clamp_or_keep(float o, float x, float lo, float hi)
+WX_HD inline float clamp_or_keep(float o, float x, float lo, float hi)
 {
   if (lo == lo && o < lo) o = lo;
   if (hi == hi && o > hi) o = hi;
   return f32_finite(o) ? o : x;
 }
 // walk 3, CONST and RTPS: the member's new value, or x itself (bit for bit)
-WXI_HD inline float post_scale(float x, double m, double lam, float lo, float hi)
+WX_HD inline float post_scale(float x, double m, double lam, float lo, float hi)
 {
 #pragma clang fp contract(off)
   const double d = (double)x - m;
@@ -105,7 +85,7 @@ WXI_HD inline float post_scale(float x, double m, double lam, float lo, float hi
   return clamp_or_keep((float)(m + ld), x, lo, hi);
 }
 // walk 2, RTPP
-WXI_HD inline float post_rtpp(float x, float p, double m, double mb, double a, double g, float lo, float hi)
+WX_HD inline float post_rtpp(float x, float p, double m, double mb, double a, double g, float lo, float hi)
 {
 #pragma clang fp contract(off)
   const double d = (double)x - m, b = (double)p - mb;
@@ -116,7 +96,7 @@ WXI_HD inline float post_rtpp(float x, float p, double m, double mb, double a, d
 
 // The whole walk over an array: x[0 .. n) the members' values of one channel of one cell, p[0 .. n) their snapshot values (not looked
 // at in CONST), air: the cell is an air cell in all of them. *lambda_out: the factor applied, or NaN. Returns whether any bits changed.
-WXI_HD inline bool inflate_channel(int mode, float coef, float lam_lo, float lam_hi, float lo, float hi, int n, float *x, const float *p, bool air, float *lambda_out)
+WX_HD inline bool inflate_channel(int mode, float coef, float lam_lo, float lam_hi, float lo, float hi, int n, float *x, const float *p, bool air, float *lambda_out)
 {
 #pragma clang fp contract(off)
   *lambda_out = __builtin_nanf("");

@@ -6,8 +6,8 @@
 //
 // k_ens_nbhd_points. One lane per cell of the GROWN rectangle -- the output rectangle grown by the largest rx / ry, rows clipped to
 // the grid, columns clipped (no wrap) or continued around the seam (wrap_x; at most X columns) --, the launch shape and the member
-// walk of k_ens_stat: a wave takes 64 consecutive column slots of one row, waves grid-stride over the chunks, the loads of UNROLL
-// members are in flight before the first is consumed, the truth is the table entry behind the selection. One channel is looked at, so
+// walk of k_ens_stat: a wave takes 64 consecutive column slots of one row, waves grid-stride over the chunks (wxe::chunk_at, the column wrap
+// behind it; wxe::member_walk), the truth is the table entry behind the selection. One channel is looked at, so
 // a member costs a 4-byte load of its value and the 4-byte wall texel (the same cache lines k_ens_stat's 16-byte loads touch). Out:
 // Nf | Ef << 16 in a 32-bit word and No | Eo << 1 in a byte per cell, in the ensemble's device staging: 5 bytes per cell.
 //
@@ -79,43 +79,40 @@ struct WinArgs {
 };
 
 #if defined(__HIPCC__)
+// what the points pass loads of a member: one channel's value and the wall texel's channel 1
+struct ChanWall {
+  float v;
+  int wd;
+};
+// ... and accumulates: the members that enter, and those with the event
+struct Counts {
+  unsigned n, ev;
+};
+
 __global__ __launch_bounds__(WG) void k_ens_nbhd_points(const PointArgs a)
 {
-  const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
-  const unsigned cpr = ((unsigned)a.gw + 63u) / 64u, chunks = cpr * (unsigned)a.gh; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
+  const wxe::WaveOfGrid wg = wxe::wave_of_grid(WAVES);
+  const unsigned chunks = wxe::chunks_per_row(a.gw) * (unsigned)a.gh;
   const wxe::CTab tab = wxe::const_table(a.tab);
   const unsigned c = (unsigned)a.channel;
   const float thr = a.thr;
   const int above = a.above;
-  for (unsigned ch = wave; ch < chunks; ch += n_waves) {
-    const unsigned y = ch / cpr, j = (ch - y * cpr) * 64u + lane;
-    if (j >= (unsigned)a.gw) continue;
-    int col = a.gx0 + (int)j; // in (-X, 2X): gx0 > -X and j < gw <= X
+  for (unsigned ch = wg.wave; ch < chunks; ch += wg.n_waves) {
+    const wxe::Chunk at = wxe::chunk_at(ch, wg.lane, a.gx0, a.gy0, a.gw); // (of column SLOTS)
+    if (!at.valid) continue;
+    int col = at.gx; // in (-X, 2X): gx0 > -X and the slot is below gw <= X
     col += col < 0 ? a.X : 0;
     col -= col >= a.X ? a.X : 0;
-    const size_t off = (size_t)(a.gy0 + (int)y) * (size_t)a.X + (size_t)col, o = (size_t)y * (size_t)a.gw + j;
-    unsigned n = 0, ev = 0, no = 0, eo = 0;
-    int k = 0;
-    for (; k + UNROLL <= a.n_sel; k += UNROLL) { // the loads of UNROLL members are issued before the first of them is consumed
-      float v[UNROLL];
-      int wd[UNROLL];
-#pragma unroll
-      for (int i = 0; i < UNROLL; i++) v[i] = wxq::ld_chan(tab + k + i, off, c), wd[i] = wxe::ld_wall_dist(tab + k + i, off);
-      WX_ENS_LOADS_ISSUED();
-#pragma unroll
-      for (int i = 0; i < UNROLL; i++) point_add(n, ev, v[i], wd[i], thr, above);
-    }
-    for (; k < a.n_sel; k++) {
-      const float v = wxq::ld_chan(tab + k, off, c);
-      const int wd = wxe::ld_wall_dist(tab + k, off);
-      point_add(n, ev, v, wd, thr, above);
-    }
+    const size_t off = wxe::texel_at(a.X, col, at.gy), o = wxe::plane_at(a.gw, at.x, at.y);
+    const Counts f = wxe::member_walk<UNROLL>(a.n_sel, Counts{0u, 0u}, [&](int k) { return ChanWall{wxq::ld_chan(tab + k, off, c), wxe::ld_wall_dist(tab + k, off)}; },
+                                              [&](Counts &q, int, const ChanWall &m) { point_add(q.n, q.ev, m.v, m.wd, thr, above); });
+    unsigned no = 0, eo = 0;
     if (a.has_truth) { // (uniform: a kernel argument)
       const float v = wxq::ld_chan(tab + a.n_sel, off, c);
       const int wd = wxe::ld_wall_dist(tab + a.n_sel, off);
       point_add(no, eo, v, wd, thr, above);
     }
-    a.cf[o] = pack_f(n, ev);
+    a.cf[o] = pack_f(f.n, f.ev);
     a.co[o] = pack_o(no, eo);
   }
 }

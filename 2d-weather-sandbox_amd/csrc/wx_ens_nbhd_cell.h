@@ -22,18 +22,18 @@ enum { MAX_RADIUS = WX_ENS_NBHD_MAX_RADIUS, MAX_SCALES = WX_ENS_NBHD_MAX_SCALES,
 static_assert((long long)(2 * MAX_RADIUS + 1) * (2 * MAX_RADIUS + 1) * 65535 < 0x7FFFFFFFll, "window sums fit int32");
 
 // the event of one value (a NaN threshold: false both ways; -0.0 == 0.0)
-WXD_HD inline bool event_of(float v, float thr, int above) { return above ? v > thr : v < thr; }
+WX_HD inline bool event_of(float v, float thr, int above) { return above ? v > thr : v < thr; }
 // one member's (or the truth's) value of the channel and channel 1 of its wall texel: n counts it if it is an air cell with a finite
 // value, ev if the event holds there too. Selects, no branches (the kernel's group of loads stays one basic block, as in wx_ens_stat.h)
-WXD_HD inline void point_add(unsigned &n, unsigned &ev, float v, int wall_dist, float thr, int above)
+WX_HD inline void point_add(unsigned &n, unsigned &ev, float v, int wall_dist, float thr, int above)
 {
   const bool take = wall_dist != 0 && wxd::f32_finite(v);
   n += take ? 1u : 0u;
   ev += (take && event_of(v, thr, above)) ? 1u : 0u;
 }
 // what the points pass leaves per cell: Nf | Ef << 16 (both <= 65535) and, in a byte of its own, No | Eo << 1
-WXD_HD inline uint32_t pack_f(unsigned n, unsigned ev) { return n | (ev << 16); }
-WXD_HD inline uint8_t pack_o(unsigned n, unsigned ev) { return (uint8_t)(n | (ev << 1)); }
+WX_HD inline uint32_t pack_f(unsigned n, unsigned ev) { return n | (ev << 16); }
+WX_HD inline uint8_t pack_o(unsigned n, unsigned ev) { return (uint8_t)(n | (ev << 1)); }
 
 // one output cell of one scale
 struct Cell {
@@ -41,7 +41,7 @@ struct Cell {
   float t[NT];   // d2, f2, o2 (meaningful where scored)
   bool scored;
 };
-WXD_HD inline Cell window_cell(int Af, int Bf, int Ao, int Bo)
+WX_HD inline Cell window_cell(int Af, int Bf, int Ao, int Bo)
 {
 #pragma clang fp contract(off)
   Cell r;

@@ -39,16 +39,15 @@ enum { WG = 256, WAVES = WG / 64, MAX_WGS = 4096 };
 #if defined(__HIPCC__)
 __global__ __launch_bounds__(WG) void k_ens_perturb(const Args a)
 {
-  const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, per_member = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
-  const unsigned long long items = (unsigned long long)per_member * (unsigned)a.n_sel;
+  const wxe::WaveOfGrid wg = wxe::wave_of_grid(WAVES);
+  const unsigned long long items = (unsigned long long)(wxe::chunks_per_row(a.w) * (unsigned)a.h) * (unsigned)a.n_sel;
   const wxe::CTab tab = wxe::const_table(a.tab);
-  for (unsigned long long it = wave; it < items; it += n_waves) {
-    const unsigned k = (unsigned)(it / per_member), ch = (unsigned)(it - (unsigned long long)k * per_member);
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    if (x >= (unsigned)a.w) continue;
-    const int gx = a.x0 + (int)x, gy = a.y0 + (int)y;
-    const size_t off = (size_t)gy * (size_t)a.X + (size_t)gx;
+  for (unsigned long long it = wg.wave; it < items; it += wg.n_waves) {
+    unsigned k;
+    const wxe::Chunk at = wxe::member_chunk_at(it, wg.lane, a.x0, a.y0, a.w, a.h, k);
+    if (!at.valid) continue;
+    const int gx = at.gx, gy = at.gy;
+    const size_t off = wxe::texel_at(a.X, gx, gy);
     const wxe::f32x4 v = wxe::ld_field(tab + k, off);
     const int wd = wxe::ld_wall_dist(tab + k, off);
     float f[4] = {v.x, v.y, v.z, v.w};

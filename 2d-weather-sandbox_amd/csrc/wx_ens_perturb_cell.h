@@ -7,27 +7,17 @@
 #include <string.h>
 #include "../../include/wxsim.h"
 #include "wx_rounded.h"
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXP_HD __host__ __device__
-#else
-#define WXP_HD
-#endif
+#include "wx_ens_cell_common.h"
 
 namespace wxp {
 
-WXP_HD inline uint32_t f32_bits(float v)
-{
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  return u;
-}
-WXP_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
+using wxcell::f32_bits;
+using wxcell::f32_finite;
 
 using wxr::rounded; // (wx_rounded.h: a product that feeds a sum is a value of its own, in every build)
 
 // the shaders' integer hash (common.glsl:103-111; wx_kernels.h hash_u32), here for the host as well
-WXP_HD inline uint32_t hash32(uint32_t x)
+WX_HD inline uint32_t hash32(uint32_t x)
 {
   x += (x << 10u);
   x ^= (x >> 6u);
@@ -55,7 +45,7 @@ inline Noise noise_of(const wx_ens_perturb &p, int X)
 }
 
 // value of lattice node (gx, gy) for (member, channel): 24 hashed bits as a double in [-1, 1)
-WXP_HD inline double node_value(uint32_t seed_h, int member, int c, uint32_t gx, uint32_t gy)
+WX_HD inline double node_value(uint32_t seed_h, int member, int c, uint32_t gx, uint32_t gy)
 {
 #pragma clang fp contract(off)
   const uint32_t h = hash32(gx + hash32(gy + hash32(4u * (uint32_t)member + (uint32_t)c + seed_h)));
@@ -67,7 +57,7 @@ struct Lattice {
   uint32_t gx0, gx1, gy0, gy1;
   double tx, ty;
 };
-WXP_HD inline Lattice lattice_of(const Noise &n, int x, int y)
+WX_HD inline Lattice lattice_of(const Noise &n, int x, int y)
 {
 #pragma clang fp contract(off)
   Lattice l;
@@ -85,7 +75,7 @@ WXP_HD inline Lattice lattice_of(const Noise &n, int x, int y)
 }
 
 // r of the header: every operation rounded to double separately
-WXP_HD inline double noise_at(const Noise &n, const Lattice &l, int member, int c)
+WX_HD inline double noise_at(const Noise &n, const Lattice &l, int member, int c)
 {
 #pragma clang fp contract(off)
   const double u00 = node_value(n.seed_h, member, c, l.gx0, l.gy0), u10 = node_value(n.seed_h, member, c, l.gx1, l.gy0);
@@ -98,7 +88,7 @@ WXP_HD inline double noise_at(const Noise &n, const Lattice &l, int member, int 
 }
 
 // one channel: the new value, or v itself (bit for bit) where the header says "untouched"
-WXP_HD inline float perturb_value(const Noise &n, float v, double r, int c)
+WX_HD inline float perturb_value(const Noise &n, float v, double r, int c)
 {
 #pragma clang fp contract(off)
   const float a = n.amp[c];
@@ -118,7 +108,7 @@ WXP_HD inline float perturb_value(const Noise &n, float v, double r, int c)
 }
 
 // one cell of one member; returns whether any channel's bits changed (a lane that changed nothing does not store)
-WXP_HD inline bool perturb_cell(const Noise &n, int member, int x, int y, int wall_dist, float v[4])
+WX_HD inline bool perturb_cell(const Noise &n, int member, int x, int y, int wall_dist, float v[4])
 {
   if (wall_dist == 0) return false;
   const Lattice l = lattice_of(n, x, y);

@@ -13,28 +13,18 @@
 #include <vector>
 #include "../../include/wxsim.h"
 #include "wx_rounded.h"
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXQ_HD __host__ __device__
-#else
-#define WXQ_HD
-#endif
+#include "wx_ens_cell_common.h"
 
 namespace wxq {
 
-WXQ_HD inline uint32_t f32_bits(float v)
-{
-  uint32_t u;
-  memcpy(&u, &v, 4);
-  return u;
-}
-WXQ_HD inline float f32_of(uint32_t u)
+using wxcell::f32_bits;
+using wxcell::f32_finite;
+WX_HD inline float f32_of(uint32_t u)
 {
   float v;
   memcpy(&v, &u, 4);
   return v;
 }
-WXQ_HD inline bool f32_finite(float v) { return ((f32_bits(v) >> 23) & 255u) != 255u; }
 
 // Keys. A finite float's key: sign bit flipped for v >= 0, all bits flipped for v < 0 -- unsigned order == float order, equal floats
 // have equal keys once -0.0 is +0.0. The largest finite key is 0xFF7FFFFF (FLT_MAX); the three values at the top of the range are the
@@ -46,16 +36,16 @@ enum : uint32_t {
   KEY_NONFINITE = 0xFFFFFFFEu, // NaN, +Inf, -Inf in an air cell
   KEY_WALL = 0xFFFFFFFFu,      // the cell is a wall cell in this member
 };
-WXQ_HD inline uint32_t key_of(float v) // v finite
+WX_HD inline uint32_t key_of(float v) // v finite
 {
   uint32_t u = f32_bits(v);
   u = (u << 1) == 0u ? 0u : u; // -0.0 is taken as +0.0
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-WXQ_HD inline float value_of(uint32_t key) { return f32_of((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key); }
-WXQ_HD inline bool key_entered(uint32_t key) { return key < KEY_PAD; }
+WX_HD inline float value_of(uint32_t key) { return f32_of((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key); }
+WX_HD inline bool key_entered(uint32_t key) { return key < KEY_PAD; }
 // one member's value of a cell and channel; wall_dist = channel 1 of its WX_FIELD_WALL_CUR texel
-WXQ_HD inline uint32_t cell_key(float v, int wall_dist) { return wall_dist == 0 ? (uint32_t)KEY_WALL : (f32_finite(v) ? key_of(v) : (uint32_t)KEY_NONFINITE); }
+WX_HD inline uint32_t cell_key(float v, int wall_dist) { return wall_dist == 0 ? (uint32_t)KEY_WALL : (f32_finite(v) ? key_of(v) : (uint32_t)KEY_NONFINITE); }
 
 using wxr::rounded; // (wx_rounded.h: a product that feeds a sum or a difference is a value of its own, in every build)
 
@@ -64,7 +54,7 @@ struct Position {
   int k, k1;
   double g;
 };
-WXQ_HD inline Position position_of(float p, int n)
+WX_HD inline Position position_of(float p, int n)
 {
 #pragma clang fp contract(off)
   const double h = rounded((double)p * (double)(n - 1)); // one rounded product; 0 <= h <= n - 1 for p in [0, 1]
@@ -76,7 +66,7 @@ WXQ_HD inline Position position_of(float p, int n)
   return q;
 }
 // the quantile from the two order statistics
-WXQ_HD inline float quantile_of(int interp, float vk, float vk1, double g)
+WX_HD inline float quantile_of(int interp, float vk, float vk1, double g)
 {
 #pragma clang fp contract(off)
   if (interp == WX_QUANT_LOWER) return vk;
@@ -92,15 +82,15 @@ WXQ_HD inline float quantile_of(int interp, float vk, float vk1, double g)
 struct Tally {
   int n, n_wall, below, equal;
 };
-WXQ_HD inline void tally_add(Tally &t, uint32_t key, uint32_t t_key)
+WX_HD inline void tally_add(Tally &t, uint32_t key, uint32_t t_key)
 {
   t.n += key_entered(key) ? 1 : 0;
   t.n_wall += key == KEY_WALL ? 1 : 0;
   t.below += key < t_key ? 1 : 0;
   t.equal += key == t_key ? 1 : 0;
 }
-WXQ_HD inline uint32_t rank_key(uint32_t member_key) { return key_entered(member_key) ? member_key : (uint32_t)KEY_PAD; }
-WXQ_HD inline int rank_count(uint32_t t_key, int c) { return t_key == KEY_PAD ? -1 : c; }
+WX_HD inline uint32_t rank_key(uint32_t member_key) { return key_entered(member_key) ? member_key : (uint32_t)KEY_PAD; }
+WX_HD inline int rank_count(uint32_t t_key, int c) { return t_key == KEY_PAD ? -1 : c; }
 
 // the argument checks wx_ensemble_quantiles and wx_ens_quant_cells share (nothing here touches a device). n_members: of the ensemble /
 // of the tables; mask: NULL = all

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(WG) void k_ens_score(const Args a)
   unsigned *const tabs = wxq_lds + ROWS * 256u;
   u64 *const bins = (u64 *)(tabs + L_BINS);
   const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h;
+  const unsigned chunks = wxe::chunks_per_row(a.w) * (unsigned)a.h;
   const wxe::CTab tab = wxe::const_table(a.tab);
   const unsigned n_sel = (unsigned)a.n_sel;
   unsigned *const col = wxq_lds + wv * 64u + lane; // this thread's column: row i at col[i * 256]
@@ -83,13 +83,12 @@ __global__ __launch_bounds__(WG) void k_ens_score(const Args a)
   const float nan = __builtin_nanf("");
   const bool maps = a.error || a.variance || a.crps;
   for (unsigned ch = blockIdx.x; ch < chunks; ch += gridDim.x) { // (workgroup-uniform trip count: every barrier below is reached by all)
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    const bool valid = x < (unsigned)a.w;
-    const size_t off = valid ? (size_t)(a.y0 + (int)y) * (size_t)a.X + (size_t)(a.x0 + (int)x) : 0, o = valid ? (size_t)y * (size_t)a.w + x : 0;
-    wxq::Staged<P>::stage(wxq_lds, tab, n_sel, off, valid, lane, wv); // 1.
+    const wxe::Chunk at = wxe::chunk_at(ch, lane, a.x0, a.y0, a.w); // (a lane past the edge stays for the barriers, with offsets 0)
+    const size_t off = at.valid ? wxe::texel_at(a.X, at.gx, at.gy) : 0, o = at.valid ? wxe::plane_at(a.w, at.x, at.y) : 0;
+    wxq::Staged<P>::stage(wxq_lds, tab, n_sel, off, at.valid, lane, wv); // 1.
     // the truth's value of this thread's channel (in flight across the barrier)
     unsigned t_key = KEY_PAD;
-    if (valid) t_key = truth_key(wxq::ld_chan(tab + n_sel, off, wv), wxe::ld_wall_dist(tab + n_sel, off));
+    if (at.valid) t_key = truth_key(wxq::ld_chan(tab + n_sel, off, wv), wxe::ld_wall_dist(tab + n_sel, off));
     __syncthreads();
     unsigned key[P];
     wxq::Staged<P>::sorted_column(key, col);
@@ -115,12 +114,12 @@ __global__ __launch_bounds__(WG) void k_ens_score(const Args a)
       five_of(s, n, m, t, r.f);
     }
     r.reason = reason_of(t_key, n, r.f);
-    const bool scored = valid && r.reason == SCORED;
+    const bool scored = at.valid && r.reason == SCORED;
     // 3. the terms, the counters, the histograms (every lane of the wave is here)
 #pragma unroll
     for (int k = 0; k < NT; k++) wxd::wave_add(cur[k], acc[k], wxd::term_of(r.f[k], scored), bins + (k * 4 + (int)wv) * wxd::NB);
 #pragma unroll
-    for (int q = 0; q < 4; q++) cnt[q] += (unsigned)__popcll(__ballot(valid && r.reason == q));
+    for (int q = 0; q < 4; q++) cnt[q] += (unsigned)__popcll(__ballot(at.valid && r.reason == q));
     sum_n += scored ? (unsigned)n : 0u;
     if (scored) {
       atomicAdd(&tabs[L_LOW + wv * BINS + (unsigned)tl.below], 1u);
@@ -134,7 +133,7 @@ __global__ __launch_bounds__(WG) void k_ens_score(const Args a)
       __syncthreads();
       if (wv < 3u) {
         uint4 *dst = (uint4 *)(wv == 0u ? a.error : (wv == 1u ? a.variance : a.crps)); // (uniform)
-        if (dst && valid) {
+        if (dst && at.valid) {
           const unsigned *src = wxq_lds + wv * 256u + lane;
           dst[o] = make_uint4(src[0], src[64], src[128], src[192]);
         }

@@ -28,21 +28,21 @@ static_assert(BINS == MAX_MEMBERS + 1, "n_below + n_equal reaches the number of 
 enum { SCORED = 0, TRUTH_EXCLUDED, EMPTY, OVERFLOW_ };
 
 // the truth's key: KEY_PAD if the cell is a wall cell in `truth` or its value is not finite
-WXQ_HD inline uint32_t truth_key(float v, int wall_dist) { return wxq::rank_key(wxq::cell_key(v, wall_dist)); }
+WX_HD inline uint32_t truth_key(float v, int wall_dist) { return wxq::rank_key(wxq::cell_key(v, wall_dist)); }
 
 // the running sums over the ascending values, all starting at +0.0
 struct Sums {
   double S, Q, A, G;
 };
-WXQ_HD inline void sums_init(Sums &s) { s.S = s.Q = s.A = s.G = 0.0; }
+WX_HD inline void sums_init(Sums &s) { s.S = s.Q = s.A = s.G = 0.0; }
 // pass 1, value i
-WXQ_HD inline void sum_step(Sums &s, uint32_t key)
+WX_HD inline void sum_step(Sums &s, uint32_t key)
 {
 #pragma clang fp contract(off)
   s.S = s.S + (double)wxq::value_of(key);
 }
 // pass 2, value i of n, around the mean m = S / n and the truth t
-WXQ_HD inline void dev_step(Sums &s, uint32_t key, int i, int n, double m, double t)
+WX_HD inline void dev_step(Sums &s, uint32_t key, int i, int n, double m, double t)
 {
 #pragma clang fp contract(off)
   const double v = (double)wxq::value_of(key);
@@ -54,7 +54,7 @@ WXQ_HD inline void dev_step(Sums &s, uint32_t key, int i, int n, double m, doubl
   const double gu = rounded((double)(2 * i - n + 1) * u);
   s.G = s.G + gu;
 }
-WXQ_HD inline double mean_of(const Sums &s, int n)
+WX_HD inline double mean_of(const Sums &s, int n)
 {
 #pragma clang fp contract(off)
   return s.S / (double)n;
@@ -66,7 +66,7 @@ struct Cell {
   int reason;  // SCORED or why not
 };
 // n >= 1 ascending values summed into s, the truth t finite
-WXQ_HD inline void five_of(const Sums &s, int n, double m, double t, float f[NT])
+WX_HD inline void five_of(const Sums &s, int n, double m, double t, float f[NT])
 {
 #pragma clang fp contract(off)
   const double err = m - t;
@@ -78,7 +78,7 @@ WXQ_HD inline void five_of(const Sums &s, int n, double m, double t, float f[NT]
   const double sq = err * err; // (feeds a conversion, no sum: nothing a build could fuse it with)
   f[0] = (float)err, f[1] = (float)__builtin_fabs(err), f[2] = (float)sq, f[3] = (float)var, f[4] = (float)crps;
 }
-WXQ_HD inline int reason_of(uint32_t t_key, int n, const float f[NT])
+WX_HD inline int reason_of(uint32_t t_key, int n, const float f[NT])
 {
   if (t_key == KEY_PAD) return TRUTH_EXCLUDED;
   if (n < 1) return EMPTY;

@@ -18,11 +18,9 @@
 //
 // The kernel: one lane per cell of the rectangle; the 64 lanes of a wave take 64 consecutive x of one row (a member's float4 load is
 // 16 B per lane, 1 KiB per wave, contiguous; its wall texel 4 B per lane), waves grid-stride over the (row, 64-column chunk) pairs.
-// Per cell the member loop is serial BY DEFINITION -- a dependent double add chain per channel --, so what the kernel can do about
-// latency is to have the loads of UNROLL members in flight before the first is consumed: the loop body loads UNROLL members into
-// registers, then consumes them in order (the compiler's counted s_waitcnt vmcnt(N) in front of each consumer), with a one-by-one
-// remainder. Pass 1: sum, count, extremes, exceedance, walls. Pass 2 (only if the variance is wanted): the members again for
-// Q = sum (v - mean)^2. The members' {field, wall, index} triples come from the ensemble's device table (wx_ens_frame.h: constant address
+// Per cell the member loop is serial BY DEFINITION -- a dependent double add chain per channel --: the chunk cursor and the member walk
+// are wx_ens_frame.h's (wxe::chunk_at, wxe::member_walk). Pass 1: sum, count, extremes, exceedance, walls. Pass 2 (only if the variance
+// is wanted): the members again for Q = sum (v - mean)^2. The members' {field, wall, index} triples come from the ensemble's device table (wx_ens_frame.h: constant address
 // space, wave-uniform addresses: scalar loads). Only the wanted planes are written, with 16-byte (n_wall: 4-byte) vector stores; nothing
 // else is written, no atomics, no LDS. profiles/ensemble_statistics_isa.txt records the loads and waits of one gfx950 build.
 // What it does not try: a w x h rectangle is ceil(w / 64) * h waves whatever the number of members (100 x 100: 200 waves on a chip
@@ -149,56 +147,28 @@ enum { WG = 256, WAVES = WG / 64, MAX_WGS = 2048, UNROLL = 8 };
 #if defined(__HIPCC__)
 __global__ __launch_bounds__(WG) void k_ens_stat(const Args a)
 {
-  const unsigned lane = threadIdx.x & 63u, wave = blockIdx.x * WAVES + (threadIdx.x >> 6), n_waves = gridDim.x * WAVES;
-  const unsigned cpr = ((unsigned)a.w + 63u) / 64u, chunks = cpr * (unsigned)a.h; // (below 2^31: 16 Ki chunks per row x 64 Ki rows)
+  const WaveOfGrid g = wave_of_grid(WAVES);
+  const unsigned chunks = chunks_per_row(a.w) * (unsigned)a.h;
   const CTab tab = const_table(a.tab);
   const float thr[4] = {a.thr[0], a.thr[1], a.thr[2], a.thr[3]};
-  for (unsigned ch = wave; ch < chunks; ch += n_waves) {
-    const unsigned y = ch / cpr, x = (ch - y * cpr) * 64u + lane;
-    if (x >= (unsigned)a.w) continue;
-    const size_t off = (size_t)(a.y0 + (int)y) * (size_t)a.X + (size_t)(a.x0 + (int)x), o = (size_t)y * (size_t)a.w + x;
+  for (unsigned ch = g.wave; ch < chunks; ch += g.n_waves) {
+    const Chunk at = chunk_at(ch, g.lane, a.x0, a.y0, a.w);
+    if (!at.valid) continue;
+    const size_t off = texel_at(a.X, at.gx, at.gy), o = plane_at(a.w, at.x, at.y);
+    const auto load = [&](int k) { return ld_field_wall(tab + k, off); };
     Cell cell;
     cell_init(cell);
-    int k = 0;
-    for (; k + UNROLL <= a.n_sel; k += UNROLL) { // the loads of UNROLL members are issued before the first of them is consumed
-      f32x4 v[UNROLL];
-      int wd[UNROLL];
-#pragma unroll
-      for (int j = 0; j < UNROLL; j++) v[j] = ld_field(tab + k + j, off), wd[j] = ld_wall_dist(tab + k + j, off);
-      WX_ENS_LOADS_ISSUED();
-#pragma unroll
-      for (int j = 0; j < UNROLL; j++) {
-        const float f[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-        cell_add(cell, f, wd[j], tab[k + j].index, thr);
-      }
-    }
-    for (; k < a.n_sel; k++) {
-      const f32x4 v = ld_field(tab + k, off);
-      const int wd = ld_wall_dist(tab + k, off);
-      const float f[4] = {v.x, v.y, v.z, v.w};
-      cell_add(cell, f, wd, tab[k].index, thr);
-    }
+    cell = member_walk<UNROLL>(a.n_sel, cell, load, [&](Cell &c, int k, const TexelWall &m) {
+      const float f[4] = {m.v.x, m.v.y, m.v.z, m.v.w};
+      cell_add(c, f, m.wd, tab[k].index, thr);
+    });
     Spread sp;
     spread_init(sp, cell);
     if (a.variance) { // (wave-uniform)
-      for (k = 0; k + UNROLL <= a.n_sel; k += UNROLL) {
-        f32x4 v[UNROLL];
-        int wd[UNROLL];
-#pragma unroll
-        for (int j = 0; j < UNROLL; j++) v[j] = ld_field(tab + k + j, off), wd[j] = ld_wall_dist(tab + k + j, off);
-        WX_ENS_LOADS_ISSUED();
-#pragma unroll
-        for (int j = 0; j < UNROLL; j++) {
-          const float f[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-          spread_add(sp, f, wd[j]);
-        }
-      }
-      for (; k < a.n_sel; k++) {
-        const f32x4 v = ld_field(tab + k, off);
-        const int wd = ld_wall_dist(tab + k, off);
-        const float f[4] = {v.x, v.y, v.z, v.w};
-        spread_add(sp, f, wd);
-      }
+      sp = member_walk<UNROLL>(a.n_sel, sp, load, [&](Spread &s, int, const TexelWall &m) {
+        const float f[4] = {m.v.x, m.v.y, m.v.z, m.v.w};
+        spread_add(s, f, m.wd);
+      });
       a.variance[o] = make_float4(variance_of(sp, cell, 0), variance_of(sp, cell, 1), variance_of(sp, cell, 2), variance_of(sp, cell, 3));
     }
     const Chan *q = cell.c;

@@ -3,18 +3,13 @@
 // lets the code generator fuse ANY multiply with a dependent add, pragma or not, so on the device the product additionally passes
 // through an empty statement the code generator cannot look through: it is rounded to double before the sum sees it, in every build.
 // Plain C++ that a host compiler takes without the HIP headers (there it is the identity). Shared by the per-cell functions of the
-// ensemble calls: wx_ens_perturb_cell.h, wx_ens_quant_cell.h, wx_ens_stat.h, wx_ens_assim_cell.h.
+// ensemble calls: wx_ens_perturb_cell.h, wx_ens_quant_cell.h, wx_ens_stat.h, wx_ens_assim_cell.h. (WX_HD: wx_ens_cell_common.h.)
 #pragma once
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define WXR_HD __host__ __device__
-#else
-#define WXR_HD
-#endif
+#include "wx_ens_cell_common.h"
 
 namespace wxr {
 
-WXR_HD inline double rounded(double x)
+WX_HD inline double rounded(double x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm("" : "+v"(x));
