@@ -164,6 +164,8 @@ struct EnsStage {
   int tab_cap = 0;
   char *out_dev = nullptr, *out_host = nullptr;         // what one call wants back (and its device-side tables), out_cap bytes
   size_t out_cap = 0;
+  char *aux_dev = nullptr;                              // device-only scratch of one call (wx_ensemble_gram's planes of centres): no pinned copy
+  size_t aux_cap = 0;
 };
 
 static void ens_stage_release(wx_ensemble *e)
@@ -174,6 +176,7 @@ static void ens_stage_release(wx_ensemble *e)
   hipFree(st->tab_dev);
   if (st->out_host) hipHostFree(st->out_host);
   hipFree(st->out_dev);
+  hipFree(st->aux_dev);
   delete st;
   e->stage = nullptr;
 }
@@ -206,6 +209,21 @@ static int ens_stage_reserve(wx_ensemble *e, const char *call, int entries, size
     }
     st->out_cap = out_bytes;
   }
+  return WX_OK;
+}
+
+// device-only scratch, behind ens_begin; only grows
+static int ens_aux_reserve(wx_ensemble *e, const char *call, size_t bytes)
+{
+  EnsStage *st = e->stage;
+  if (bytes <= st->aux_cap) return WX_OK;
+  hipFree(st->aux_dev);
+  st->aux_dev = nullptr, st->aux_cap = 0;
+  if (hipMalloc((void **)&st->aux_dev, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return efail(e, WX_E_NOMEM, "%s: %zu bytes of device scratch", call, bytes);
+  }
+  st->aux_cap = bytes;
   return WX_OK;
 }
 

@@ -64,6 +64,8 @@ enum KernelId {
   K_ENS_COV,    // covariance, correlation and sensitivity maps over the members of an ensemble (wx_ens_cov.h)
   K_ENS_NBHD_POINTS,  // neighbourhood probabilities: the members' event counts per cell (wx_ens_nbhd.h)
   K_ENS_NBHD_WINDOWS, // the box sums, the fractions and the sums of the fractions skill score (wx_ens_nbhd.h)
+  K_ENS_GRAM_CENTRE,  // the members' Gram matrix: the centres and the entry test of every cell-channel, the pre-pass (wx_ens_gram.h)
+  K_ENS_GRAM,         // the exact sums of the pair terms, a thread per pair (wx_ens_gram.h)
   K_ENS_ASSIM_OBS, // point observations assimilated into the members: the observation-space pre-pass (wx_ens_assim.h)
   K_ENS_ASSIM,  // the state update of one field (wx_ens_assim.h)
   K_COUNT
@@ -72,7 +74,7 @@ const char *const kKernelNames[K_COUNT] = {"velocity", "curl", "vorticity", "bou
                                            "precipitation", "lightning", "splat_box", "copy", "halo", "fused_dry_vel_advect_pressure", "march_dry_vel_advect_pressure",
                                            "march_wet_full_iteration", "march_dry2_two_iterations_per_launch", "ensemble_statistics", "ensemble_perturb",
                                            "ensemble_quantiles", "ensemble_scores", "ensemble_prior_save", "ensemble_inflate", "ensemble_covariance_pred", "ensemble_covariance",
-                                           "ensemble_nbhd_points", "ensemble_nbhd_windows", "ensemble_assimilate_obs", "ensemble_assimilate"};
+                                           "ensemble_nbhd_points", "ensemble_nbhd_windows", "ensemble_gram_centre", "ensemble_gram", "ensemble_assimilate_obs", "ensemble_assimilate"};
 
 struct ProfRec {
   hipEvent_t a, b;
@@ -2962,3 +2964,4 @@ int wx_profile_read(wx_sim *s, int cap, float *ms, int *launches)
 #include "wx_ens_inflate.h" // (likewise)
 #include "wx_ens_cov.h" // (likewise)
 #include "wx_ens_nbhd.h" // (likewise)
+#include "wx_ens_gram.h" // (likewise)

@@ -51,6 +51,7 @@ EXPORTS = [
     "wx_ensemble_prior_save", "wx_ensemble_prior_drop", "wx_ensemble_inflate", "wx_ens_inflate_cells",
     "wx_ensemble_covariance", "wx_ens_cov_cells",
     "wx_ensemble_neighbourhood", "wx_ens_nbhd_cells", "wx_ens_nbhd_max_radius",
+    "wx_ensemble_gram", "wx_ens_gram_cells", "wx_ens_gram_max_members",
 ]
 
 
@@ -498,6 +499,64 @@ def ens_cov_cells(bases, waters, walls, X: int, Y: int, field, predictors, *, so
     return planes
 
 
+ENS_GRAM_MAX_MEMBERS = 64
+GRAM_CENTERS = {"mean": 0, "none": 1}
+
+
+class WxEnsGram(C.Structure):
+    """``wx_ens_gram`` of include/wxsim.h, member for member: what is asked for, the caller-owned matrix and the counts."""
+    _fields_ = [
+        ("field", C.c_int32), ("center", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+        ("gram", C.c_void_p),
+        ("n_entered", C.c_int64 * 4), ("n_excluded", C.c_int64 * 4), ("n_overflow", C.c_int64 * 4),
+        ("n_selected", C.c_int32), ("pad", C.c_int32),
+    ]
+
+
+def _gram_struct(field, center, rect, n_sel: int):
+    """A wx_ens_gram whose matrix is a fresh (4, n_sel, n_sel) float64 array. Returns (the struct, the array)."""
+    g = WxEnsGram()
+    g.field, g.center = int(FIELD_IDS.get(field, field)), int(GRAM_CENTERS.get(center, center))
+    g.x, g.y, g.w, g.h = [int(v) for v in rect]
+    gram = np.zeros((4, n_sel, n_sel), np.float64)
+    g.gram = gram.ctypes.data
+    return g, gram
+
+
+def _gram_dict(g: WxEnsGram, gram: np.ndarray, sel) -> dict:
+    return {"gram": gram, "n_entered": np.array(g.n_entered[:], np.int64), "n_excluded": np.array(g.n_excluded[:], np.int64),
+            "n_overflow": np.array(g.n_overflow[:], np.int64), "members": [int(i) for i in sel]}
+
+
+def _selected(n: int, members) -> list:
+    mask = _member_mask(n, members)
+    return list(range(n)) if mask is None else [i for i in range(n) if mask[i]]
+
+
+def ens_gram_cells(fields, walls, X: int, Y: int, field, *, rect=None, members=None, center="mean") -> dict:
+    """wx_ens_gram_cells: the members' Gram matrix of include/wxsim.h on the CPU, literally as defined. ``fields[i]`` / ``walls[i]``:
+    member i's WHOLE grid of ``field``, float32 (Y, X, 4), and its wall texels, int8 (Y, X, 4); an unselected member's entries may be
+    None. Returns ``gram`` (4, n, n) float64 over the selected members in ascending index, ``n_entered`` / ``n_excluded`` /
+    ``n_overflow`` (4 each) and ``members``."""
+    rect = (0, 0, int(X), int(Y)) if rect is None else tuple(int(v) for v in rect)
+    n = len(walls)
+    if n < 1 or len(fields) != n:
+        raise ValueError("one field and one wall array per member")
+    shape = (int(Y), int(X), 4)
+    fl = [None if a is None else np.ascontiguousarray(a, np.float32) for a in fields]
+    wl = [None if a is None else np.ascontiguousarray(a, np.int8) for a in walls]
+    if any(a is not None and a.shape != shape for a in fl + wl):
+        raise ValueError(f"one {shape} field and wall array per member")
+    mask = _member_mask(n, members)
+    sel = _selected(n, members)
+    g, gram = _gram_struct(field, center, rect, len(sel))
+    ptrs = lambda arrs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
+    rc = lib().wx_ens_gram_cells(C.byref(g), int(X), int(Y), n, ptrs(fl), ptrs(wl), None if mask is None else mask.ctypes.data)
+    if rc != 0:
+        raise WxError(rc, "wx_ens_gram_cells: a bad field or centre, a rectangle outside the grid, a missing array, or too few or too many members selected")
+    return _gram_dict(g, gram, sel)
+
+
 ENS_QUANT_MAX = 8
 QUANT_INTERP = {"linear": 0, "lower": 1, "higher": 2}
 
@@ -877,6 +936,10 @@ def lib() -> C.CDLL:
     L.wx_ens_nbhd_cells.argtypes = [C.POINTER(WxEnsNbhd), C.POINTER(WxEnsNbhdResult), i32, i32, i32, vp, vp, vp, vp, vp]
     L.wx_ens_nbhd_max_radius.argtypes = []
     L.wx_ens_nbhd_max_radius.restype = i32
+    L.wx_ensemble_gram.argtypes = [vp, C.POINTER(WxEnsGram), vp]
+    L.wx_ens_gram_cells.argtypes = [C.POINTER(WxEnsGram), i32, i32, i32, vp, vp, vp]
+    L.wx_ens_gram_max_members.argtypes = []
+    L.wx_ens_gram_max_members.restype = i32
     _lib = L
     return L
 
@@ -1582,6 +1645,21 @@ class Ensemble:
         planes["results"] = _cov_results(res, len(predictors))
         del keep
         return planes
+
+    def gram(self, field: str, rect=None, members=None, center="mean") -> dict:
+        """wx_ensemble_gram: the selected members (at most 64) seen in member space -- per channel the n x n matrix of the exact sums,
+        over the cells of ``rect`` = (x, y, w, h) (None: the whole grid) of ``field`` (BASE_CUR or WATER_CUR), of the float terms
+        (d_a d_b) of the members' deviations from their mean (``center`` "mean"; at least two members) or of their raw values
+        ("none"). A cell-channel enters if the cell is an air cell and the value finite in every selected member and no squared
+        deviation overflows a float. Returns ``gram`` (4, n, n) float64, exactly symmetric, the members in ascending index;
+        ``n_entered`` / ``n_excluded`` / ``n_overflow`` (4 each, adding up to w * h) and ``members``. Changes nothing; two launches;
+        blocks like ``statistics``."""
+        rect = (0, 0, self.X, self.Y) if rect is None else rect
+        mask = _member_mask(self.n, members)
+        sel = _selected(self.n, members)
+        g, gram = _gram_struct(field, center, rect, len(sel))
+        self._chk(lib().wx_ensemble_gram(self._e, C.byref(g), None if mask is None else mask.ctypes.data))
+        return _gram_dict(g, gram, sel)
 
     def neighbourhood(self, field: str, channel: int, threshold: float, scales, truth: Optional["Handle"] = None, *, above: bool = True, rect=None,
                       members=None, wrap_x: bool = False, want=("nep",)) -> dict:

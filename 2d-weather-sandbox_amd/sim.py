@@ -377,6 +377,58 @@ class WeatherEnsemble:
         out = self._e.covariance(field, [np.asarray(values, np.float64)], source="prior", rect=rect, members=members, want=("slope", "corr"))
         return {"slope": out["slope"][0], "corr": out["corr"][0], "result": out["results"][0]}
 
+    def gram(self, field: str, rect=None, members=None, center="mean") -> dict:
+        """``engine.Ensemble.gram``: the selected members (at most 64) in member space -- per channel the n x n matrix of the exact
+        inner products, over the cells of ``rect``, of the members' deviations from their mean (``center`` "mean") or of their raw
+        values ("none"): ``gram`` (4, n, n) float64, the counts ``n_entered`` / ``n_excluded`` / ``n_overflow`` and ``members``."""
+        return self._e.gram(field, rect, members, center)
+
+    def distances(self, field: str, weights=(1, 1, 1, 1), *, rect=None, members=None, center="mean") -> np.ndarray:
+        """How far the selected members are from one another over ``rect``: the n x n matrix of sqrt(sum_c w_c (G_aa + G_bb - 2 G_ab))
+        from ``gram``, clipped at 0; ``weights`` put the channels on one scale (e.g. one over their variances). The distance between
+        two members does not depend on the centre; "mean" keeps the matrix entries small. The difference cancels: it costs about
+        2^-24 of G_aa -- the rounding of the float terms the sums are made of -- which two nearly equal members feel and which is
+        harmless for clustering."""
+        g = self.gram(field, rect, members, center)["gram"]
+        w = np.asarray(weights, np.float64).reshape(4)
+        m = np.tensordot(w, g, axes=(0, 0))
+        d = np.diag(m)
+        return np.sqrt(np.maximum(d[:, None] + d[None, :] - 2.0 * m, 0.0))
+
+    def medoid(self, field: str, weights=(1, 1, 1, 1), *, rect=None, members=None) -> int:
+        """The most representative member: the index of the selected member whose summed ``distances`` to the others is smallest
+        (the first of them if several are)."""
+        from .engine import _selected
+        d = self.distances(field, weights, rect=rect, members=members)
+        return int(_selected(len(self.members), members)[int(np.argmin(d.sum(axis=1)))])
+
+    def eofs(self, field: str, k: int = 3, weights=(1, 1, 1, 1), *, rect=None, members=None) -> dict:
+        """The leading ``k`` empirical orthogonal functions of ``field`` over ``rect``, by the member-space route: M = sum_c w_c G_c /
+        (n - 1) from ``gram`` has the non-zero eigenvalues of the (channel-weighted) spatial covariance, ``numpy.linalg.eigh`` of that
+        n x n matrix gives them, and ONE ``covariance`` call with the unit-variance principal-component scores as predictors turns
+        them into patterns -- so k <= 8. Returns ``eigenvalues`` (n, descending), ``explained`` (their fractions of the trace),
+        ``pcs`` (n, k: unit sample variance, the members in ascending index) and ``patterns`` (k, h, w, 4): the covariance of every
+        cell-channel with PC j, in the field's own units (the EOF times sqrt(eigenvalue), unweighted); NaN where a cell does not
+        enter. The sign of a pattern and its PC is eigh's."""
+        from .engine import ENS_COV_MAX, _selected
+        k = int(k)
+        if k < 1 or k > ENS_COV_MAX:
+            raise ValueError(f"eofs: k = {k}: 1 .. {ENS_COV_MAX} (WX_ENS_COV_MAX: the patterns come from one covariance call)")
+        out = self.gram(field, rect, members, "mean")
+        sel = _selected(len(self.members), members)
+        n = len(sel)
+        if k > n:
+            raise ValueError(f"eofs: k = {k} patterns from {n} members")
+        w = np.asarray(weights, np.float64).reshape(4)
+        lam, vec = np.linalg.eigh(np.tensordot(w, out["gram"], axes=(0, 0)) / (n - 1))
+        lam, vec = lam[::-1], vec[:, ::-1]
+        total = lam.sum()
+        pcs = vec[:, :k] * np.sqrt(n - 1.0)
+        values = np.zeros((k, len(self.members)), np.float64)
+        values[:, sel] = pcs.T
+        patterns = self._e.covariance(field, list(values), rect=rect, members=members, want=("cov",))["cov"]
+        return {"eigenvalues": lam, "explained": lam / total if total > 0 else np.full_like(lam, np.nan), "pcs": pcs, "patterns": patterns, "members": out["members"]}
+
     def analysis(self, observations, *, relax=None, inflate=None, **assimilate_kw) -> list:
         """One analysis step of a cycling filter: ``save_prior`` of the state fields with a non-zero gain (only with ``relax``), then
         ``assimilate(observations, **assimilate_kw)``, then the inflation -- ``relax`` = ("rtps", alpha) or ("rtpp", alpha): relaxation

@@ -1178,6 +1178,63 @@ int wx_ens_nbhd_cells(const wx_ens_nbhd *args, wx_ens_nbhd_result *out, int X, i
                       const uint8_t *member_mask);   /* host only, pure */
 int wx_ens_nbhd_max_radius(void);  /* == WX_ENS_NBHD_MAX_RADIUS */
 
+/* ---- (ABI 11, WX_HAVE_ENSEMBLE_GRAM) The members' Gram matrix on the device: the ensemble seen in MEMBER SPACE. Every call above looks
+ * at a cell across the members; this one looks at the members across the cells: the n x n matrix of inner products of the members'
+ * deviations over a rectangle, per channel. How far member i is from member j (G_ii + G_jj - 2 G_ij), which member is the most
+ * representative (the medoid), whether the members fall into two scenarios, how many independent directions the spread has left after
+ * ten analysis cycles (the rank of G), and the EOFs -- G / (n-1) has the non-zero eigenvalues of the spatial covariance, its
+ * eigenvectors are the principal-component scores, and wx_ensemble_covariance with those scores as WX_COV_PRED_VALUES turns them into
+ * the spatial patterns -- are a few lines of host arithmetic on a matrix of at most 64 x 64.
+ *
+ * THE DEFINITION (the kernels, wx_ens_gram_cells and the tests all evaluate it). The arithmetic of a cell is double, every operation
+ * rounded separately, a product is a value of its own in every build (as for wx_ensemble_covariance, whose first walk this reuses).
+ * "In member order": the n selected members k = 0 .. n-1 by ascending member index.
+ *   Eligibility. x_k is member k's value of channel c of the cell. The cell-channel is ELIGIBLE iff in every selected member the cell is
+ *   an air cell (channel 1 of its WX_FIELD_WALL_CUR texel != 0) and x_k is finite; otherwise it is EXCLUDED.
+ *   Centre. WX_GRAM_CENTER_MEAN: Sx = sum (double)x_k in member order from +0.0, xm = Sx / n. WX_GRAM_CENTER_NONE: xm = +0.0 (the raw
+ *   inner products). In both modes d_k = (double)x_k - xm.
+ *   Term. For a <= b: p_ab = (float)(d_a * d_b): one double product, then the C conversion (round to nearest; a product beyond the
+ *   float range converts to +-Inf, a tiny one to a subnormal float or to a zero).
+ *   Overflow. The cell-channel is OVERFLOW iff some diagonal term p_kk is not finite; then NONE of its terms enters. The conversion is
+ *   monotone and |d_a d_b| <= max(d_a^2, d_b^2), so |p_ab| <= max(p_aa, p_bb): an off-diagonal term of a cell-channel that is not
+ *   OVERFLOW is always finite, and the diagonal test is the whole test.
+ *   Sum. gram[c][a][b] = gram[c][b][a] = the correctly rounded double of the EXACT sum of p_ab over the cell-channels of the rectangle
+ *   that entered (eligible, not overflow) -- what Python's math.fsum returns --, taken with wx_diag's integer bins and its 320-bit
+ *   finish as wx_ens_score's sums are. So the matrix does not depend on the order of the cells, the launch shape or the build; it is
+ *   exactly symmetric and its diagonal is >= 0; with NONE it does not depend on the order of the members either (permuting the members
+ *   permutes the matrix bit for bit); with MEAN it inherits the member-order mean, as the covariance does. A sum over nothing is +0.0.
+ *   Counts per channel: n_entered + n_excluded + n_overflow = w*h.
+ *
+ * wx_ensemble_gram. Answered before the device is touched -- WX_E_INVALID: e or g NULL; a field other than WX_FIELD_BASE_CUR /
+ * WX_FIELD_WATER_CUR; an unknown center; gram NULL; fewer than two selected members with MEAN, fewer than one with NONE; more than
+ * WX_ENS_GRAM_MAX_MEMBERS selected. WX_E_RANGE: the rectangle lies outside the grid (no wrap). WX_E_STATE: a selected member was never
+ * uploaded (the message names it). Everything else as for wx_ensemble_covariance: member_mask has one byte per member (NULL = all), the
+ * work is ordered behind everything pending on the ensemble's stream, the call BLOCKS like wx_ensemble_sync and consumes and returns a
+ * member's pending report, its device buffers belong to the ensemble, and it CHANGES NOTHING a host can observe. n_selected is filled
+ * in. Two launches: the centres and the entry test of every cell-channel (kernel name "ensemble_gram_centre"), then the pairs (kernel
+ * name "ensemble_gram"); what leaves the device is integers; wx_profile on member 0 times both; DESIGN.md section 4.
+ * wx_ens_gram_cells (host only, pure): the same definition over whole X x Y grids the caller holds -- member i's `field` at field[i]
+ * (4 floats per cell) and wall[i] (4 bytes per cell). WX_E_INVALID / WX_E_RANGE as above, and WX_E_INVALID for n_members < 1, X or
+ * Y < 1, a NULL table, a NULL entry of a selected member. A refused call writes nothing.
+ * Out of scope: the snapshot of wx_ensemble_prior_save as a source; more than 64 members; the raw bins as an output, for merging
+ * rectangles (add the matrices of disjoint rectangles instead: one more rounding per entry). */
+#define WX_HAVE_ENSEMBLE_GRAM 1
+#define WX_ENS_GRAM_MAX_MEMBERS 64
+#define WX_GRAM_CENTER_MEAN 0   /* deviations from the members' mean of the cell-channel */
+#define WX_GRAM_CENTER_NONE 1   /* the raw values */
+typedef struct wx_ens_gram {
+  int32_t field;            /* WX_FIELD_BASE_CUR or WX_FIELD_WATER_CUR */
+  int32_t center;           /* WX_GRAM_CENTER_* */
+  int32_t x, y, w, h;       /* the rectangle; no wrap (WX_E_RANGE) */
+  double *gram;             /* 4 * n * n doubles: gram[(c*n + a)*n + b]; a, b: position among the selected members, ascending member index */
+  int64_t n_entered[4], n_excluded[4], n_overflow[4];   /* per channel; they add up to w*h */
+  int32_t n_selected, pad;
+} wx_ens_gram;
+int wx_ensemble_gram(wx_ensemble *e, wx_ens_gram *g, const uint8_t *member_mask /* n_members bytes, NULL = all */);
+int wx_ens_gram_cells(wx_ens_gram *g, int X, int Y, int n_members, const float *const *field,
+                      const int8_t *const *wall, const uint8_t *member_mask);   /* host only, pure */
+int wx_ens_gram_max_members(void);  /* == WX_ENS_GRAM_MAX_MEMBERS */
+
 /* Per-kernel device time from HIP events recorded on the handle's stream around every launch.
  * wx_profile(s, 1) starts collecting, wx_profile_read returns accumulated milliseconds and launch counts
  * for up to `cap` kernels (names via wx_kernel_name) and resets the accumulators. */

@@ -88,13 +88,14 @@ def parse():
     ap.add_argument("--inflate", default="", metavar="FIELD", help="time one inflation call per mode over the whole grid against read_rect + the host function (BASE_CUR or WATER_CUR)")
     ap.add_argument("--covariance", default="", metavar="FIELD", help="time one covariance call with 1 and with 8 point predictors over the whole grid against read_rect + numpy and the statistics kernel (BASE_CUR or WATER_CUR)")
     ap.add_argument("--neighbourhood", default="", metavar="FIELD", help="time one neighbourhood call (B members against member B of B + 1, five scales up to (16, 8), channel 1) against statistics planes + read_rect of the truth + numpy summed-area tables (BASE_CUR or WATER_CUR)")
+    ap.add_argument("--gram", default="", metavar="FIELD", help="time one Gram-matrix call over the whole grid against B read_rect calls + numpy and next to the statistics kernel (BASE_CUR or WATER_CUR)")
     ap.add_argument("--observations", type=int, default=40, help="observations per call with --assimilate (1 .. 256)")
     ap.add_argument("--spawn", action="store_true", help="time B members made from one stepped state: device-side broadcast + perturb against B uploads")
     ap.add_argument("--share", type=int, default=0, help="segment-height sweep: the members' launch shapes as for an ensemble of this many members "
                     "(1 = the lone handle's shape; 0 = the shipped rule, B). Needs the debug build: make -C csrc debug, WXSIM_LIB=.../variants/libwxsim_debug.so")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = "100x100x64,2500x300x8" if a.scores or a.inflate or a.covariance or a.neighbourhood else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
+        a.shapes = "100x100x64,2500x300x8,2500x300x24" if a.gram else "100x100x64,2500x300x8" if a.scores or a.inflate or a.covariance or a.neighbourhood else "100x100x64,2500x300x8,100x100x96" if a.quantiles else "100x100x8,100x100x64,2500x300x8" if a.assimilate else "100x100x64,2500x300x8,16000x500x2"
     return a
 
 
@@ -783,8 +784,106 @@ def time_covariance(a, pkg, ens, X, Y, B):
     return rec
 
 
+def _gram_deviations(fields, walls):
+    """(4, n, cells) float64, contiguous per channel: the deviations from the members' mean, 0 where a cell-channel does not enter
+    (the overflow test of the definition is left out: these fields hold nothing near 2^64)."""
+    import numpy as np
+    f = np.stack([np.float64(a) for a in fields])
+    air = np.all(np.stack([w[..., 1] != 0 for w in walls]), axis=0)
+    ok = air[..., None] & np.isfinite(f).all(axis=0)
+    d = np.where(ok, f - f.mean(axis=0), 0.0).reshape(f.shape[0], -1, 4)
+    return np.ascontiguousarray(np.moveaxis(d, 2, 0))
+
+
+def numpy_gram(fields, walls):
+    """The quick host route: float64, one matrix product per channel on contiguous arrays. Not the device's numbers: the products are
+    not rounded to float and BLAS sums in its own order."""
+    import numpy as np
+    d = _gram_deviations(fields, walls)
+    return np.stack([d[c] @ d[c].T for c in range(4)])
+
+
+def numpy_gram_terms(fields, walls):
+    """The numpy restatement of the definition without fsum: per pair a <= b the float32-rounded terms (d_a * d_b).astype(float32),
+    summed in float64 by numpy (pairwise, so not the exact sum)."""
+    import numpy as np
+    d = _gram_deviations(fields, walls)
+    n = d.shape[1]
+    g = np.zeros((4, n, n))
+    for c in range(4):
+        for a_ in range(n):
+            for b_ in range(a_, n):
+                g[c, a_, b_] = g[c, b_, a_] = (d[c, a_] * d[c, b_]).astype(np.float32).sum(dtype=np.float64)
+    return g
+
+
+def time_gram(a, pkg, ens, X, Y, B):
+    import statistics
+    import numpy as np
+    field = a.gram
+    ens.step(a.frame)
+    ens.sync()
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 0.25:  # clock conditioning, untimed (the first call also sizes the ensemble's staging buffers)
+        ens.gram(field)
+    ms = lambda t: round(1e3 * t, 3)  # noqa: E731
+    rec = {"field": field, "members": B, "calls": a.repeats}
+    ens[0].profile(True)
+    t_call = []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        got = ens.gram(field)
+        t_call.append(time.perf_counter() - t0)
+    prof = ens[0].profile_read()
+    ens[0].profile(False)
+    k_ms, k_n = prof.get("ensemble_gram", (0.0, 0))
+    p_ms, p_n = prof.get("ensemble_gram_centre", (0.0, 0))
+    rec["one_call_ms"] = {"slowest": ms(max(t_call)), "median": ms(statistics.median(t_call))}
+    rec["kernel_us"] = round(1e3 * k_ms / max(k_n, 1), 2)
+    rec["prepass_kernel_us"] = round(1e3 * p_ms / max(p_n, 1), 2)
+    rec["kernel_launches_timed"] = k_n
+    rec["pairs"] = B * (B + 1) // 2
+    rec["entered_fraction"] = [round(float(v) / (X * Y), 4) for v in got["n_entered"]]
+    # the statistics kernel of the same run: it reads the same member bytes once
+    ens[0].profile(True)
+    for _ in range(a.repeats):
+        ens.statistics(field, want=("mean", "variance"))
+    prof = ens[0].profile_read()
+    ens[0].profile(False)
+    s_ms, s_n = prof.get("ensemble_statistics", (0.0, 0))
+    s_us = 1e3 * s_ms / max(s_n, 1)
+    rec["statistics_kernel_us_mean_variance"] = round(s_us, 2)
+    rec["gram_kernels_over_statistics_kernel"] = round((rec["kernel_us"] + rec["prepass_kernel_us"]) / s_us, 2) if s_us > 0 else None
+    # the host route: B read_rect pairs + numpy
+    t_host, t_read = [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        fields, walls = [h.read_rect(field) for h in ens.members], [h.read_rect("WALL_CUR") for h in ens.members]
+        t1 = time.perf_counter()
+        host = numpy_gram(fields, walls)
+        t_read.append(t1 - t0)
+        t_host.append(time.perf_counter() - t0)
+    rec["read_numpy_route_ms"] = {"slowest": ms(max(t_host)), "median": ms(statistics.median(t_host)), "of_which_read_rect_median": ms(statistics.median(t_read))}
+    rec["speedup_median_over_read_numpy_route"] = round(statistics.median(t_host) / statistics.median(t_call), 2)
+    rec["speedup_median_over_read_rect_alone"] = round(statistics.median(t_read) / statistics.median(t_call), 2)
+    # the restatement without fsum (float32 terms per pair), on arrays already read: its arithmetic alone
+    t_terms = []
+    for _ in range(min(a.repeats, 3)):
+        t0 = time.perf_counter()
+        terms = numpy_gram_terms(fields, walls)
+        t_terms.append(time.perf_counter() - t0)
+    rec["numpy_float32_terms_per_pair_ms"] = {"slowest": ms(max(t_terms)), "median": ms(statistics.median(t_terms)), "runs": len(t_terms)}
+    rec["speedup_median_over_read_rect_plus_float32_terms"] = round((statistics.median(t_read) + statistics.median(t_terms)) / statistics.median(t_call), 2)
+    rec["largest_difference_from_float32_terms_over_sqrt_gaa_gbb"] = float(np.max(np.abs(got["gram"] - terms) / (np.sqrt(np.einsum("cii,cjj->cij", terms, terms)) + 1e-300)))
+    scale = np.sqrt(np.einsum("cii,cjj->cij", host, host)) + 1e-300
+    rec["largest_difference_from_numpy_over_sqrt_gaa_gbb"] = float(np.max(np.abs(got["gram"] - host) / scale))
+    return rec
+
+
 def main():
     a = parse()
+    if a.gram and (a.mode != "ensemble" or a.gram not in ("BASE_CUR", "WATER_CUR")):
+        sys.exit("--gram BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.covariance and (a.mode != "ensemble" or a.covariance not in ("BASE_CUR", "WATER_CUR")):
         sys.exit("--covariance BASE_CUR | WATER_CUR needs --mode ensemble")
     if a.inflate and (a.mode != "ensemble" or a.inflate not in ("BASE_CUR", "WATER_CUR")):
@@ -866,6 +965,10 @@ def main():
             continue
         if a.covariance:
             out["shapes"][spec] = {"members": B, "covariance": time_covariance(a, pkg, ens, X, Y, B)}
+            close()
+            continue
+        if a.gram:
+            out["shapes"][spec] = {"members": B, "gram": time_gram(a, pkg, ens, X, Y, B)}
             close()
             continue
         if a.assimilate:
